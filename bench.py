@@ -2,6 +2,7 @@
 """Benchmark of the radar_grid hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config METRIC|C2|C4|C5] [--fields F] [--mode csr|fused]
+                    [--dump-outputs DIR]
 
 One *step* = one pass of the per-volume hot path over one batch of synthetic input per GPU, inputs resident in HBM:
 mask fold + field interleave (rg_pack_fields_f32) -> gridding (the dominant kernel: rg_csr_compact_apply_packed_f32 =
@@ -24,6 +25,12 @@ anything touches the GPU; rank 0's JSON line is passed through) unless it alread
 which case WORLD_SIZE must equal ``--gpus``.
 
 Rank 0 prints ONE JSON line on stdout; progress goes to stderr.
+
+``--dump-outputs DIR``: after the timed steps, rank 0 writes what its last timed step computed -- the arrays a caller of
+the timed path receives (grids, COLMAX, argmax, CAPPI planes) -- as ``DIR/<name>.npy`` (float32, or float64 where float32
+would round), finite only: no-data NaN is written as 0 and recorded in ``DIR/<name>_nonfinite.npy``.  At most 64 MB in
+all: an array that does not fit its share is replaced by a fixed, seeded sample of its elements (the same positions in
+every run).  The inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -51,8 +58,10 @@ def log(*a):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1); ms_per_step is their mean wall time")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0) to DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--config", default="METRIC",
                     help="METRIC (default), C2, C4 -- see radar_processor_amd.synthetic.CONFIGS -- or C5 (batch of 8 "
                          "volumes per GPU through batch.VolumeBatch)")
@@ -103,7 +112,113 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-sample-pairs", type=float, default=1.5e9, help="upper bound on CSR pairs in the CPU sample")
     ap.add_argument("--cpu-workers", type=int, default=0,
                     help="processes of the all-core CPU leg (0 = min(usable cores, 16): the CPU share of a 1-GPU box)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed, for comparing two builds output for output
+# ---------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64_000_000 - (64 << 10)     # the files' total, less room for their .npy headers
+DUMP_SEED = 20240917
+
+
+def flatten_outputs(obj, prefix, found):
+    """Name every array of a step's result by its path: dict entries by key, list / tuple entries by position."""
+    if hasattr(obj, "detach") or isinstance(obj, np.ndarray):
+        found["".join(c if c.isalnum() or c in "._-" else "_" for c in prefix)] = obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            flatten_outputs(v, f"{prefix}_{k}" if prefix else str(k), found)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            flatten_outputs(v, f"{prefix}_{i}" if prefix else str(i), found)
+    return found
+
+
+def _named_planes(planes):
+    """One field's planes from a C5 step -- ``((colmax, argmax), cappi)`` from the reducer or the dict of
+    ``gridding.PlaneProducts`` -- under the names the other configurations use."""
+    if isinstance(planes, tuple):
+        return {"colmax": planes[0][0], "argmax": planes[0][1], "cappi4000": planes[1]}
+    named = {k: v for k, v in planes.items() if k != "cappi"}
+    named.update({f"cappi{alt:g}": v for alt, v in planes.get("cappi", {}).items()})
+    return named
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write ``{name: tensor or ndarray}`` to ``directory/<name>.npy``.  float64 stays float64, other floating arrays are
+    written as float32, integer ones as float32 when every value is exact in it (|v| <= 2**24), else as float64.
+
+    Every file holds finite numbers only.  The no-data NaN of the grids and planes (and any infinity) is written as 0,
+    and each floating array gets a companion ``<name>_nonfinite.npy`` (float32, same elements) that says what stood
+    there: 0 a finite value, 1 NaN, 2 +inf, 3 -inf.  The companion is written for every floating array, so that the set
+    of files does not depend on the data.
+
+    The byte budget goes to the 2-D planes first (all but an eighth of it, shared out smallest first), then to the 3-D
+    grids.  An array larger than its share is replaced by that many of its elements: one from each of that many equal
+    slices of the flattened array, at a seeded offset -- positions that depend only on the array's size, so every run
+    and every build samples alike.  Returns ``{name: {"shape", "dtype", "saved", "sampled", "nonfinite"}}``."""
+    os.makedirs(directory, exist_ok=True)
+    sizes = {k: int(np.prod(tuple(a.shape), dtype=np.int64)) for k, a in arrays.items()}
+    out_dtype, floating = {}, {}
+    for k, a in arrays.items():
+        name = str(a.dtype).replace("torch.", "")
+        floating[k] = "float" in name or "half" in name or name == "double"
+        if name in ("float64", "double"):
+            out_dtype[k] = np.float64
+        elif floating[k]:
+            out_dtype[k] = np.float32
+        else:
+            top = (a.abs().max().item() if hasattr(a, "detach") else np.abs(a).max()) if sizes[k] else 0
+            out_dtype[k] = np.float32 if int(top) <= (1 << 24) else np.float64
+    # bytes per saved element: the value, plus its float32 code in the companion file
+    per_elem = {k: np.dtype(out_dtype[k]).itemsize + (4 if floating[k] else 0) for k in arrays}
+    quota = {}
+
+    def share_out(names, room):
+        names = sorted(names, key=lambda k: sizes[k] * per_elem[k])
+        for i, k in enumerate(names):
+            quota[k] = min(sizes[k], room // (len(names) - i) // per_elem[k])
+            room -= quota[k] * per_elem[k]
+        return room
+    grids = [k for k, a in arrays.items() if len(a.shape) >= 3]
+    left = share_out([k for k in arrays if k not in grids], budget - (budget // 8 if grids else 0))
+    share_out(grids, left + (budget // 8 if grids else 0))
+    manifest = {}
+    for k, a in arrays.items():
+        n, m = sizes[k], quota[k]
+        flat = a.detach().reshape(-1) if hasattr(a, "detach") else np.asarray(a).reshape(-1)
+        if m < n:
+            rng = np.random.default_rng([DUMP_SEED, n])
+            idx = (np.arange(m, dtype=np.int64) * n) // m
+            idx += (rng.random(m) * (((np.arange(1, m + 1, dtype=np.int64) * n) // m) - idx)).astype(np.int64)
+            if hasattr(flat, "detach"):
+                import torch
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            else:
+                flat = flat[idx]
+        host = flat.cpu().numpy() if hasattr(flat, "detach") else flat
+        host = host.astype(out_dtype[k])                 # a copy: the caller's array is never changed
+        shape = tuple(a.shape) if m == n else (m,)
+        n_bad = 0
+        if floating[k]:
+            code = np.zeros(host.shape, dtype=np.float32)
+            code[np.isnan(host)] = 1.0
+            code[np.isposinf(host)] = 2.0
+            code[np.isneginf(host)] = 3.0
+            bad = code != 0
+            n_bad = int(bad.sum())
+            host[bad] = 0.0
+            np.save(os.path.join(directory, k + "_nonfinite.npy"), code.reshape(shape))
+        np.save(os.path.join(directory, k + ".npy"), host.reshape(shape))
+        manifest[k] = {"shape": list(a.shape), "dtype": str(a.dtype).replace("torch.", ""), "saved": int(host.size),
+                       "sampled": m < n, "nonfinite": n_bad}
+    return manifest
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -643,9 +758,13 @@ def run_rank(args):
             if timed:
                 pair[1].record()
                 events.append(pair)
+            res = {}
             for k in range(n_ff):
-                rg.column_argmax(grid4[k])
-                rg.constant_altitude_ppi(grid4[k], geom, 4000.0)
+                cmax, arg = rg.column_argmax(grid4[k])
+                cappi = rg.constant_altitude_ppi(grid4[k], geom, 4000.0)
+                res[f"v{my_vols[k // n_f]}_{field_names[k % n_f]}"] = {"grid": grid4[k], "colmax": cmax, "argmax": arg,
+                                                                       "cappi4000": cappi}
+            return res
 
     def barrier():
         torch.cuda.synchronize()
@@ -658,9 +777,19 @@ def run_rank(args):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(True)
+        last = None                       # the previous step's outputs go before the next step runs
+        last = step(True)
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:       # before anything below reuses the output buffers
+        if c5:
+            last = {f"v{b}": {field_names[i]: _named_planes(planes) for i, planes in enumerate(per_field)}
+                    for b, per_field in last.items()}
+        dumped = dump_outputs(args.dump_outputs, flatten_outputs(last, "", {}))
+        log(f"rank 0: outputs of the last timed step -> {args.dump_outputs} ({len(dumped)} arrays, "
+            f"{sum(1 for d in dumped.values() if d['sampled'])} sampled)")
+    del last
     per_rank_ms_per_step = [round(elapsed / args.steps * 1e3, 4)]
     if world > 1:
         # every rank's own wall time for the K steps (between the same two barriers), then the max the contract asks for
@@ -933,6 +1062,8 @@ def run_rank(args):
                                                 if gridder.compact is not None else "csr")}
         if c5_extra is not None:
             result["extras"]["c5"] = c5_extra
+        if dumped is not None:
+            result["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
         if n_gpus == 1 and args.mode == "csr" and not c5:
             # side measurement on the same inputs (not part of `value`): the CSR-free fused gridder (K2)
             try:

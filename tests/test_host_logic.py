@@ -504,6 +504,57 @@ class TestBenchLauncher:
         line = json.loads(res.stdout.decode().strip().splitlines()[-1])
         assert line["n_gpus"] == 3 and line["per_rank_kernel_ms"] == [10.0, 11.0, 12.0]
 
+    def test_steps_must_be_positive(self):
+        res = self._run(["--steps", "0"], {})
+        assert res.returncode == 2 and b"--steps must be >= 1" in res.stderr and not res.stdout.strip()
+
+    def test_dump_outputs_budget_and_sample(self, tmp_path):
+        """--dump-outputs: finite float32 / float64 files under 64 MB in all (no-data NaN and infinities written as 0,
+        their places coded in <name>_nonfinite.npy), the 2-D planes whole while they fit, a larger array replaced by a
+        sample at positions that depend only on its size (the same in every run and build)."""
+        import bench
+        rng = np.random.default_rng(3)
+        grid = rng.standard_normal((20, 1000, 1000)).astype(np.float32)
+        grid[grid > 2.5] = np.nan                              # no-data voxels, as the gridders leave them
+        grid[0, 0, :3] = [np.inf, -np.inf, np.nan]
+        colmax = np.nanmax(grid, axis=0)
+        step = {"v0_DBZH": {"grid": grid, "colmax": colmax, "argmax": np.nanargmax(np.nan_to_num(grid, nan=-9.0), axis=0)
+                            .astype(np.int32), "cappi4000": grid[7].copy()}, "big": np.arange(1 << 23, dtype=np.int64) << 31,
+                "edge": np.array([1.5, np.nan, np.inf, -np.inf])}
+        arrays = bench.flatten_outputs(step, "", {})
+        assert sorted(arrays) == ["big", "edge", "v0_DBZH_argmax", "v0_DBZH_cappi4000", "v0_DBZH_colmax", "v0_DBZH_grid"]
+        a = bench.dump_outputs(str(tmp_path / "a"), arrays)
+        b = bench.dump_outputs(str(tmp_path / "b"), arrays)
+        assert a == b and sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
+        assert sorted(f.name for f in (tmp_path / "a").iterdir()) == sorted(
+            [f"{k}.npy" for k in arrays] + [f"{k}_nonfinite.npy" for k in arrays if k not in ("big", "v0_DBZH_argmax")])
+        for f in (tmp_path / "a").iterdir():
+            got = np.load(f)
+            assert np.array_equal(got, np.load(tmp_path / "b" / f.name))
+            assert got.dtype in (np.float32, np.float64) and np.isfinite(got).all(), f.name
+        for name, rec in a.items():
+            got = np.load(tmp_path / "a" / f"{name}.npy")
+            assert got.dtype == (np.float64 if name in ("big", "edge") else np.float32) and got.size == rec["saved"]
+
+        def restored(name):
+            got = np.load(tmp_path / "a" / f"{name}.npy")
+            code = np.load(tmp_path / "a" / f"{name}_nonfinite.npy")
+            assert code.shape == got.shape and np.isin(code, (0, 1, 2, 3)).all() and (got[code != 0] == 0).all()
+            return np.where(code == 1, np.nan, np.where(code == 2, np.inf, np.where(code == 3, -np.inf, got)))
+        for name in ("v0_DBZH_colmax", "v0_DBZH_argmax", "v0_DBZH_cappi4000"):
+            assert not a[name]["sampled"]
+            back = np.load(tmp_path / "a" / f"{name}.npy") if name.endswith("argmax") else restored(name)
+            assert np.array_equal(back, arrays[name], equal_nan=True)
+        assert a["v0_DBZH_cappi4000"]["nonfinite"] == int((~np.isfinite(grid[7])).sum()) > 0
+        assert a["v0_DBZH_grid"]["sampled"] and a["big"]["sampled"]
+        got = restored("v0_DBZH_grid")
+        assert 0 < got.size < grid.size and np.isin(got[np.isfinite(got)], grid).all() and np.isnan(got).any()
+        edge = restored("edge")
+        assert edge.dtype == np.float64 and np.array_equal(edge, step["edge"], equal_nan=True) and a["edge"]["nonfinite"] == 3
+        big = np.load(tmp_path / "a" / "big.npy")           # values exact in float64, positions strictly increasing
+        assert (np.diff(big) > 0).all() and np.array_equal(big.astype(np.int64), big.astype(np.int64) >> 31 << 31)
+        assert not arrays["v0_DBZH_grid"][0, 0, 2] == arrays["v0_DBZH_grid"][0, 0, 2]      # the caller's arrays untouched
+
     def test_parent_refuses_more_ranks_than_gpus(self):
         import torch
         if torch.cuda.device_count() >= 8:
