@@ -450,6 +450,73 @@ int rg_csr_compact_apply_columns_f32(const void* indptr, int32_t indptr_is_i64, 
                                      int32_t window_cap, int32_t z_pieces, const int32_t* order, void* workspace,
                                      int64_t workspace_bytes, int32_t lanes_hint, rg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K1q  PLANES MODE: the column mode of K1p with a wider products epilogue, for callers that keep 2-D products only.
+ * Replaces, in one pass over the packed records, the read-back of the 3-D grid by radar_grid/products.py:462-490
+ * (column_max), :493-535 (column_min), :538-580 (column_mean), :361-412 (CAPPI: the two bracketing levels) and :168-314
+ * (constant_elevation_ppi: the per-pixel levels, sampled here and combined by rg_elevation_ppi_finish_f32).
+ * Arguments up to fill_value and after `req`: as rg_csr_compact_apply_columns_f32; 1-4 fields.  `req` (host memory):
+ *   out, level_planes / keep_lo / n_keep, col_max / col_arg, col_lo / col_hi: as rg_csr_compact_apply_columns_f32;
+ *   col_min   [n_fields][ny*nx] or NULL: NaN-ignoring minimum over planes col_lo .. col_hi -- the contract of
+ *             rg_column_reduce_f32(RG_COL_MIN), bit for bit (np.fmin in ascending level order, all NaN stays NaN);
+ *   col_mean  [n_fields][ny*nx] or NULL: NaN-ignoring mean over the same window -- float32 sum of the non-NaN values in
+ *             level order and their count, (float)((double)sum / (double)count): rg_column_reduce_f32(RG_COL_MEAN) bit
+ *             for bit.  The running sum cannot be split: col_mean needs z_pieces == 1 (RG_EINVAL otherwise);
+ *   n_sel     0 .. RG_MAX_SEL_PLANES per-pixel level selections (rg_elevation_ppi_plan_f32): sel_levels[s] is an int32
+ *             plane [ny*nx] of lo | hi << 16 or RG_PPI_SEL_NONE; the kernel stores the value of level lo at
+ *             sel_samples[f][s][0][pixel] and of level hi at sel_samples[f][s][1][pixel] (pixels with RG_PPI_SEL_NONE
+ *             are not written).  sel_samples is [n_fields][n_sel][2][ny*nx]; the grid needs fewer than 65535 planes.
+ * At least one of out / level_planes / col_max / col_min / col_mean / a selection must be given.  With z_pieces > 1 the
+ * partial maxima (value + arg) and minima (value) live in `workspace` (rg_csr_planes_workspace_bytes) and are merged in
+ * ascending level order by a second small kernel.  The grids and every plane are the same BITS as the separate kernels
+ * applied to rg_csr_compact_apply_packed_f32's grid (tile = 0, same lanes_hint).
+ * ------------------------------------------------------------------------------------------------- */
+#define RG_MAX_SEL_PLANES 4
+#define RG_PPI_SEL_NONE (-1)
+
+typedef struct rg_plane_request {
+  float* out;
+  float* level_planes;
+  int32_t keep_lo, n_keep;
+  float* col_max;
+  int32_t* col_arg;
+  float* col_min;
+  float* col_mean;
+  int32_t col_lo, col_hi;
+  int32_t n_sel, reserved;
+  const int32_t* sel_levels[RG_MAX_SEL_PLANES];
+  float* sel_samples;
+} rg_plane_request;
+
+/* bytes of `workspace` for z_pieces level pieces: want_max (value + arg) and want_min (value) partial planes */
+int64_t rg_csr_planes_workspace_bytes(int64_t lines_per_plane, int64_t line_len, int32_t n_fields, int32_t z_pieces,
+                                      int32_t want_max, int32_t want_min);
+int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                    const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base, const int64_t* dict_ptr,
+                                    const int32_t* dict, int64_t n_vox, int64_t n_pairs, int64_t line_len,
+                                    int64_t lines_per_plane, const float* packed, int32_t n_fields, int32_t stride,
+                                    int64_t n_gates, float fill_value, const rg_plane_request* req, int32_t window_cap,
+                                    int32_t z_pieces, const int32_t* order, void* workspace, int64_t workspace_bytes,
+                                    int32_t lanes_hint, rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * a12p / a12f  constant-elevation PPI in two halves around K1q (radar_grid/products.py:168-314).  Scalars, xc / yc and
+ * the shape as rg_elevation_ppi_f32.
+ * plan:   sel[ny*nx] = lo_s | hi_s << 16 of products.py:280-294 (linear) or ks | ks << 16 of :263-268 (nearest), and
+ *         RG_PPI_SEL_NONE where the pixel is NaN whatever the grid holds (linear: target altitude outside [z_min, z_max],
+ *         :306-309; nearest: level outside the grid, :266); w_hi[ny*nx] (float64, linear only, else may be NULL) the
+ *         upper weight of :284.  nz < 65535.
+ * finish: `samples` [2][ny*nx] of one field (K1q's sel_samples[f][s]) -> `out` exactly as rg_elevation_ppi_f32 would
+ *         write it from the stored grid: double[ny*nx] w_lo * v_lo + w_hi * v_hi (linear) or float[ny*nx] v_lo (nearest),
+ *         NaN where sel is RG_PPI_SEL_NONE.  Both kernels share their per-pixel code with rg_elevation_ppi_f32.
+ * ------------------------------------------------------------------------------------------------- */
+int rg_elevation_ppi_plan_f32(const float* xc, const float* yc, int32_t nz, int32_t ny, int32_t nx, double cos_clamped,
+                              double sin_elev, double tan_elev, double ke_re, double ke_re_sq, double z_min, double z_max,
+                              double z_step, int32_t earth_curvature, int32_t linear, int32_t* sel, double* w_hi,
+                              rg_stream_t stream);
+int rg_elevation_ppi_finish_f32(const int32_t* sel, const double* w_hi, const float* samples, int64_t n_xy, int32_t linear,
+                                void* out, rg_stream_t stream);
+
 /* number of chunks of a grid of n_rows rows (negative rg_status when the sizes do not factor) */
 int64_t rg_csr_compact_chunks(int64_t n_rows, int64_t line_len, int64_t lines_per_plane);
 

@@ -53,6 +53,18 @@ class PlaneTest(Structure):
     _fields_ = [("plane", c_void_p), ("lo", c_float), ("hi", c_float), ("flags", c_int32)]
 
 
+RG_MAX_SEL_PLANES = 4       # level selections (constant-elevation PPIs) one planes-mode launch samples
+RG_PPI_SEL_NONE = -1
+
+
+class PlaneRequest(Structure):
+    """``rg_plane_request``: what one ``rg_csr_compact_apply_planes_f32`` launch produces (device pointers)."""
+    _fields_ = [("out", c_void_p), ("level_planes", c_void_p), ("keep_lo", c_int32), ("n_keep", c_int32),
+                ("col_max", c_void_p), ("col_arg", c_void_p), ("col_min", c_void_p), ("col_mean", c_void_p),
+                ("col_lo", c_int32), ("col_hi", c_int32), ("n_sel", c_int32), ("reserved", c_int32),
+                ("sel_levels", c_void_p * RG_MAX_SEL_PLANES), ("sel_samples", c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/radargrid_hip.h one to one
 SIGNATURES = {
     "rg_version": (c_int32, []),
@@ -99,6 +111,15 @@ SIGNATURES = {
                                                    c_int32, c_int64, c_float, c_void_p, c_void_p, c_int32, c_int32,
                                                    c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                                    c_void_p, c_int64, c_int32, c_void_p]),
+    "rg_csr_planes_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "rg_csr_compact_apply_planes_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, ctypes.c_uint32, c_void_p,
+                                                  c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32,
+                                                  c_int32, c_int64, c_float, POINTER(PlaneRequest), c_int32, c_int32,
+                                                  c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "rg_elevation_ppi_plan_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_double, c_double,
+                                            c_double, c_double, c_double, c_double, c_double, c_int32, c_int32, c_void_p,
+                                            c_void_p, c_void_p]),
+    "rg_elevation_ppi_finish_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "rg_csr_compact_chunks": (c_int64, [c_int64, c_int64, c_int64]),
     "rg_csr_compact_count": (c_int32, [c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                        c_void_p]),

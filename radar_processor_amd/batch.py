@@ -193,14 +193,14 @@ class VolumeBatch:
                    world_size=None, events: Optional[list] = None) -> Dict[int, object]:
         """Returns ``{volume index: grids [F, nz, ny, nx]}`` -- or ``{index: products(grids)}`` when a reducer is
         given, so that only 2-D planes outlive the pass.  ``products`` may also be a :class:`gridding.PlaneProducts`
-        (column maximum / argmax / CAPPIs): the result is then ``{index: [one dict of planes per field]}`` and, on the CSR
+        (column maximum / argmax / minimum / mean, CAPPIs, constant-elevation PPIs): the result is then ``{index: [one dict of planes per field]}`` and, on the CSR
         path of a large geometry and on request, the pass runs the gridding kernel's column mode with its products epilogue -- the 3-D grids
         are neither written nor read back (``gridding.grid_products_device``).  ``volumes`` is indexed by the GLOBAL volume number; only this
         rank's entries (``shard_indices``) are touched, the others may be ``None``.  ``events``: optional list that
         receives one ``(start, end)`` pair of stream events per gridding pass (mask fold + gridding kernel), for
         callers that time the kernel itself (``bench.py``)."""
         import torch
-        from .gridding import PlaneProducts, grid_fields_device, grid_products_device
+        from .gridding import PlaneProducts, grid_fields_device, grid_products_device, reduce_planes
         from .roi_grid import roi_grid_fields_device
         plane_spec = products if isinstance(products, PlaneProducts) else None
         if plane_spec is not None and self.fused:      # the CSR-free gridder has no epilogue: reduce its grids as usual
@@ -218,9 +218,12 @@ class VolumeBatch:
                             rec["colmax"], rec["argmax"] = got
                         else:
                             rec["colmax"] = got
+                    reduce_planes(_spec, g[k], geom_like, lo, hi, rec)           # column min / mean, PPIs
                     if _spec.cappi:
                         rec["cappi"] = {alt: gp.constant_altitude_ppi(g[k], geom_like, alt, _spec.interpolation)
                                         for alt in _spec.cappi}
+                    if "ppi" in rec:
+                        rec["ppi"] = rec.pop("ppi")                             # (key order of grid_products_device)
                     recs.append(rec)
                 return recs
             plane_spec = None

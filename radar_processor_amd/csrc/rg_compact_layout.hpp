@@ -53,12 +53,23 @@ struct RowwiseColumns {
   int pieces = 1, keep_lo = 0, n_keep = 0, col_lo = 0, col_hi = 0;
 };
 
+// ---- planes mode: the column mode with the wider epilogue (rg_csr_compact_apply_planes_f32) ----
+// A separate type, so that the column mode's kernel argument -- and its code -- stays what it was.
+struct RowwisePlanes : RowwiseColumns {
+  float* col_min = nullptr;                             // [pieces][F][n_xy] (pieces == 1: the caller's plane) or null
+  float* col_mean = nullptr;                            // [F][n_xy] or null (pieces == 1 only)
+  const int32_t* sel[RG_MAX_SEL_PLANES] = {};           // n_sel planes [n_xy]: lo | hi << 16, or RG_PPI_SEL_NONE
+  float* samples = nullptr;                             // [F][n_sel][2][n_xy]
+  int n_sel = 0;
+};
+
 }  // namespace rgl
 
 namespace {
 
 using rgl::ChunkGrid;
 using rgl::RowwiseColumns;
+using rgl::RowwisePlanes;
 using rg::f32x2;
 using rg::f32x4;
 using rsrc_t = __amdgpu_buffer_rsrc_t;
@@ -220,6 +231,13 @@ __device__ __forceinline__ void column_max_step(ColumnBest& acc, float v, int z)
   }
 }
 
+// np.fmin.reduce in level order without the index (rg_products.hip: step<false>): NaN = nothing seen yet, so the first non-NaN
+// level starts the reduction and a later one replaces it only when strictly smaller
+__device__ __forceinline__ void column_min_step(float& acc, float v) {
+  const bool keep = acc <= v || isnan(v);
+  if (!keep) acc = v;
+}
+
 }  // namespace
 
 // defined in rg_csr_compact.hip (next to the kernel), called by rg_csr_columns.hip
@@ -227,3 +245,7 @@ int rg_launch_rowwise_columns(int nf, bool i64, int window_cap, const void* indp
                               const rgl::ChunkGrid& cg, long n_vox, const float* packed, long n_gates, float fill, float* out,
                               hipStream_t s, const void* rec, const int64_t* rec_ptr, unsigned w_base, int rec_order,
                               int lanes_hint, const rgl::RowwiseColumns& cols);
+int rg_launch_rowwise_planes(int nf, bool i64, int window_cap, const void* indptr, const int64_t* dict_ptr, const int32_t* dict,
+                             const rgl::ChunkGrid& cg, long n_vox, const float* packed, long n_gates, float fill, float* out,
+                             hipStream_t s, const void* rec, const int64_t* rec_ptr, unsigned w_base, int rec_order,
+                             int lanes_hint, const rgl::RowwisePlanes& cols);

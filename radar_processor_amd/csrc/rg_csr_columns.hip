@@ -58,6 +58,20 @@ __global__ __launch_bounds__(256) void columns_merge_kernel(const float* __restr
   if (out_arg) out_arg[i] = idx;
 }
 
+// minimum of a column from the partial minima of its level pieces, merged in ascending level order (rg_products.hip:
+// merge<false>): NaN = the piece saw no value; a later piece wins only when strictly smaller
+__global__ __launch_bounds__(256) void planes_min_merge_kernel(const float* __restrict__ part_val, int pieces, long n_planes_xy,
+                                                               float* __restrict__ out_val) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_planes_xy) return;
+  float v = part_val[i];
+  for (int p = 1; p < pieces; ++p) {
+    const float bv = part_val[(size_t)p * n_planes_xy + i];
+    if (!isnan(bv) && (isnan(v) || bv < v)) v = bv;
+  }
+  out_val[i] = v;
+}
+
 }  // namespace
 
 extern "C" int64_t rg_csr_columns_workspace_bytes(int64_t lines_per_plane, int64_t line_len, int32_t n_fields,
@@ -152,6 +166,129 @@ extern "C" int rg_csr_compact_apply_columns_f32(const void* indptr, int32_t indp
     hipLaunchKernelGGL(columns_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part_val, part_arg, z_pieces, n,
                        col_max, col_arg);
     return rg::check_launch("rg_csr_compact_apply_columns_f32 (merge)");
+  }
+  return RG_OK;
+}
+
+// K1q  rg_csr_compact_apply_planes_f32: the column mode with the wider epilogue (csr_compact_rowwise_kernel<..., PLANES = true>):
+// COLMIN (radar_grid/products.py:493-535) and COLMEAN (:538-580) over the level window next to COLMAX, and the per-pixel
+// levels of constant-elevation PPIs (:168-314) stored as samples for rg_elevation_ppi_finish_f32.  The min merges over level
+// pieces like the max; the mean's float32 running sum cannot be split, so it takes one piece.
+// Roofline: HBM.  As rg_csr_compact_apply_columns_f32, plus F*4*Vxy per min / mean plane, 4*Vxy per selection read and at most
+// F*8*Vxy per selection written.
+extern "C" int64_t rg_csr_planes_workspace_bytes(int64_t lines_per_plane, int64_t line_len, int32_t n_fields, int32_t z_pieces,
+                                                 int32_t want_max, int32_t want_min) {
+  if (lines_per_plane <= 0 || line_len <= 0 || n_fields < 1 || n_fields > 4 || z_pieces < 1) return RG_EINVAL;
+  if (z_pieces == 1) return 0;
+  return (int64_t)z_pieces * n_fields * lines_per_plane * line_len * ((want_max ? 8 : 0) + (want_min ? 4 : 0));
+}
+
+extern "C" int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                               const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
+                                               const int64_t* dict_ptr, const int32_t* dict, int64_t n_vox, int64_t n_pairs,
+                                               int64_t line_len, int64_t lines_per_plane, const float* packed,
+                                               int32_t n_fields, int32_t stride, int64_t n_gates, float fill_value,
+                                               const rg_plane_request* req, int32_t window_cap, int32_t z_pieces,
+                                               const int32_t* order, void* workspace, int64_t workspace_bytes,
+                                               int32_t lanes_hint, rg_stream_t stream) {
+  RG_REQUIRE(req, RG_EINVAL, "rg_csr_compact_apply_planes_f32: null request");
+  RG_REQUIRE(rec_order == RG_REC_ORDER_SEGMENT || rec_order == RG_REC_ORDER_DISPATCH, RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: rec_order=%d is neither RG_REC_ORDER_SEGMENT nor RG_REC_ORDER_DISPATCH", rec_order);
+  RG_REQUIRE(n_fields >= 1 && n_fields <= 4, RG_EUNSUPPORTED, "rg_csr_compact_apply_planes_f32: n_fields=%d not in 1..4",
+             n_fields);
+  RG_REQUIRE(stride == stride_for(n_fields), RG_EINVAL, "rg_csr_compact_apply_planes_f32: stride=%d, expected %d for %d fields",
+             stride, stride_for(n_fields), n_fields);
+  RG_REQUIRE(indptr && dict_ptr && rec_ptr, RG_EINVAL, "rg_csr_compact_apply_planes_f32: null indptr/dict_ptr/rec_ptr");
+  RG_REQUIRE(req->n_sel >= 0 && req->n_sel <= RG_MAX_SEL_PLANES, RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: n_sel=%d outside 0..%d", req->n_sel, RG_MAX_SEL_PLANES);
+  for (int k = 0; k < req->n_sel; ++k)
+    RG_REQUIRE(req->sel_levels[k], RG_EINVAL, "rg_csr_compact_apply_planes_f32: sel_levels[%d] is null", k);
+  RG_REQUIRE(req->n_sel == 0 || req->sel_samples, RG_EINVAL, "rg_csr_compact_apply_planes_f32: %d selections, null sel_samples",
+             req->n_sel);
+  RG_REQUIRE(req->out || req->level_planes || req->col_max || req->col_min || req->col_mean || req->n_sel > 0, RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: nothing to produce");
+  RG_REQUIRE(n_vox >= 0 && n_pairs >= 0, RG_EINVAL, "rg_csr_compact_apply_planes_f32: negative size");
+  RG_REQUIRE(n_pairs == 0 || (records && dict && packed && n_gates > 0), RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: pairs present but records/dict/packed/n_gates missing");
+  RG_REQUIRE(packed && n_gates > 0, RG_EINVAL, "rg_csr_compact_apply_planes_f32: packed fields missing");
+  RG_REQUIRE(n_gates <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_planes_f32: n_gates exceeds int32 gate indices");
+  RG_REQUIRE(n_vox <= 0x3FFFFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_planes_f32: n_vox too large for one launch");
+  RG_REQUIRE(window_cap >= 0 && window_cap <= RG_COMPACT_MAX_WINDOW, RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: window_cap %d outside 0..%d", window_cap, RG_COMPACT_MAX_WINDOW);
+  RG_REQUIRE(rg::aligned16(records), RG_EALIGN, "rg_csr_compact_apply_planes_f32: records must be 16-byte aligned");
+  RG_REQUIRE(rg::aligned16(packed), RG_EALIGN, "rg_csr_compact_apply_planes_f32: packed must be 16-byte aligned");
+  RG_REQUIRE((w_base & 0x3FFFFFFu) == 0, RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: w_base=0x%08x must have its low 26 bits clear", w_base);
+  RG_REQUIRE(lanes_hint == 0 || (lanes_hint >= 1 && lanes_hint <= 64 && (lanes_hint & (lanes_hint - 1)) == 0) ||
+                 (lanes_hint > 70 && lanes_hint <= 99), RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: lanes_hint must be 0, a power of two up to 64, or 71..99");
+  RG_REQUIRE(!(req->col_mean && z_pieces != 1), RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: col_mean needs z_pieces == 1 (the float32 running sum cannot be split), got %d",
+             z_pieces);
+  RG_REQUIRE(!req->col_arg || req->col_max, RG_EINVAL, "rg_csr_compact_apply_planes_f32: col_arg needs col_max");
+  if (n_vox == 0) return RG_OK;
+  ChunkGrid cg;
+  RG_REQUIRE(make_chunk_grid(n_vox, line_len, lines_per_plane, &cg), RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: n_vox=%ld is not planes x lines_per_plane=%ld x line_len=%ld", (long)n_vox,
+             (long)lines_per_plane, (long)line_len);
+  RG_REQUIRE(chunk_count(cg) <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_planes_f32: too many chunks for one launch");
+  RG_REQUIRE(z_pieces >= 1 && z_pieces <= cg.n_planes, RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: z_pieces=%d outside 1..planes=%ld", z_pieces, (long)cg.n_planes);
+  RG_REQUIRE(req->n_sel == 0 || cg.n_planes < 0xFFFF, RG_EUNSUPPORTED,
+             "rg_csr_compact_apply_planes_f32: level selections need fewer than 65535 planes, the grid has %ld", (long)cg.n_planes);
+  RG_REQUIRE(!req->level_planes || (req->keep_lo >= 0 && req->n_keep >= 1 && req->keep_lo + (long)req->n_keep <= cg.n_planes),
+             RG_EINVAL, "rg_csr_compact_apply_planes_f32: kept levels [%d, %d) outside the grid's %ld planes", req->keep_lo,
+             req->keep_lo + req->n_keep, (long)cg.n_planes);
+  const bool any_col = req->col_max || req->col_min || req->col_mean;
+  RG_REQUIRE(!any_col || (req->col_lo >= 0 && req->col_lo <= req->col_hi && req->col_hi < cg.n_planes), RG_EINVAL,
+             "rg_csr_compact_apply_planes_f32: column window [%d, %d] outside the grid's %ld planes", req->col_lo, req->col_hi,
+             (long)cg.n_planes);
+  const long n_xy = cg.lines_per_plane * cg.line_len;
+  const bool split_max = req->col_max && z_pieces > 1, split_min = req->col_min && z_pieces > 1;
+  const long need_ws = (long)z_pieces * n_fields * n_xy * ((split_max ? 8 : 0) + (split_min ? 4 : 0));
+  RG_REQUIRE(need_ws == 0 || (workspace && workspace_bytes >= need_ws), RG_EWORKSPACE,
+             "rg_csr_compact_apply_planes_f32: workspace of %ld bytes needed for %d level pieces (rg_csr_planes_workspace_bytes)",
+             need_ws, z_pieces);
+  const long n_cols = (long)cg.nyg * cg.nsx;
+  RG_REQUIRE(n_cols * z_pieces <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_planes_f32: too many workgroups");
+  const size_t n_part = (size_t)z_pieces * n_fields * n_xy;
+  float* part_val = split_max ? static_cast<float*>(workspace) : nullptr;
+  int32_t* part_arg = split_max ? reinterpret_cast<int32_t*>(part_val + n_part) : nullptr;
+  float* part_min = split_min ? static_cast<float*>(workspace) + (split_max ? 2 * n_part : 0) : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  int st;
+  {
+    rgl::RowwisePlanes c;
+    c.order = order;
+    c.planes = req->level_planes;
+    c.col_val = part_val ? part_val : req->col_max;
+    c.col_arg = part_val ? part_arg : req->col_arg;
+    c.n_xy = n_xy;
+    c.n_cols = (unsigned)n_cols;
+    c.pieces = z_pieces;
+    c.keep_lo = req->level_planes ? req->keep_lo : 0;
+    c.n_keep = req->level_planes ? req->n_keep : 0;
+    c.col_lo = any_col ? req->col_lo : 0;
+    c.col_hi = any_col ? req->col_hi : -1;
+    c.col_min = part_min ? part_min : req->col_min;
+    c.col_mean = req->col_mean;
+    for (int k = 0; k < RG_MAX_SEL_PLANES; ++k) c.sel[k] = k < req->n_sel ? req->sel_levels[k] : nullptr;
+    c.samples = req->n_sel ? req->sel_samples : nullptr;
+    c.n_sel = req->n_sel;
+    st = rg_launch_rowwise_planes(n_fields, indptr_is_i64 != 0, window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates,
+                                  fill_value, req->out, s, records, rec_ptr, w_base, rec_order, lanes_hint, c);
+  }
+  if (st != RG_OK) return st;
+  const long n = (long)n_fields * n_xy;
+  const dim3 g((unsigned)((n + 255) / 256)), b(256);
+  if (part_val) {
+    hipLaunchKernelGGL(columns_merge_kernel, g, b, 0, s, part_val, part_arg, z_pieces, n, req->col_max, req->col_arg);
+    st = rg::check_launch("rg_csr_compact_apply_planes_f32 (max merge)");
+    if (st != RG_OK) return st;
+  }
+  if (part_min) {
+    hipLaunchKernelGGL(planes_min_merge_kernel, g, b, 0, s, part_min, z_pieces, n, req->col_min);
+    return rg::check_launch("rg_csr_compact_apply_planes_f32 (min merge)");
   }
   return RG_OK;
 }

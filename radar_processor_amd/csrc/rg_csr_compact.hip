@@ -537,23 +537,34 @@ constexpr int kRowwiseChunksPerBlock = 1;   // consecutive chunks one workgroup 
 #undef RG_ROWWISE_WAVES8
 #define RG_ROWWISE_WAVES8 1
 #endif
-#define RG_ROWWISE_BOUNDS __launch_bounds__(64 * kH, (NF == 1 ? RG_ROWWISE_WAVES1 : NF == 3 ? RG_ROWWISE_WAVES3 : NF >= 5 ? RG_ROWWISE_WAVES8 : 1))
+// COLS == 2 (planes mode): the wider epilogue is held to the column mode's wavefronts per SIMD for two to four fields (5, 4, 4) and
+// to at least 5 for one field.  Measured (-Rpass-analysis=kernel-resource-usage, no scratch): 80 / 90 / 112 / 120 VGPRs for
+// 1-4 fields, i.e. 6 / 5 / 4 / 4 wavefronts per SIMD -- the column mode's 77 / 83 / 101 / 107 keep the same counts.
+#define RG_ROWWISE_BOUNDS __launch_bounds__(64 * kH, (COLS == 2 ? (NF <= 2 ? 5 : 4) :                                           \
+                                                      NF == 1 ? RG_ROWWISE_WAVES1 : NF == 3 ? RG_ROWWISE_WAVES3 : NF >= 5 ? RG_ROWWISE_WAVES8 : 1))
 // COLS (rg_csr_compact_apply_columns_f32, csrc/rg_csr_columns.hip): the chunks a workgroup takes one after the other are
 // not consecutive blocks of the dispatch order but the LEVELS of one column of chunks -- the same (line group, segment)
 // patch from plane z0 to z1 - 1 of its level piece -- so that lane == row sees the voxels of its (y, x) column in ascending
 // level order and can keep the column maximum / first argmax in registers and store selected levels as planes; `out`
 // may then be null (products only: the 3-D grid is never written).  Everything between a chunk's row pointers and its
 // row sums is the same code: the same bits.
+// COLS = 1: the column mode; COLS = 2, PLANES (rg_csr_compact_apply_planes_f32, csrc/rg_csr_columns.hip): the column mode
+// with the wider epilogue -- per field the
+// running minimum and the float32 sum + count of the mean next to the maximum, and up to RG_MAX_SEL_PLANES per-pixel level
+// selections whose levels lane == row stores as samples.  Only `if constexpr (PLANES)` code and a kernel argument of its own
+// (RowwisePlanes), so the column mode itself compiles to what it was.
 // REGS: where the row sums wait for lane == row -- -1 = the field count's default (RowwiseConfig<NF>::regs), 0 = the LDS
 // array, 1 = registers.  Four fields: registers cost 99 VGPRs (4 wavefronts per SIMD), the LDS array 95 (5 wavefronts) and
 // 8 KiB of LDS per workgroup -- the launcher picks the array wherever the LDS still admits five workgroups per CU.
-template <typename IndT, int NF, int STRIDE, int DIAG = 0, bool COLS = false, int REGS = -1>
+template <typename IndT, int NF, int STRIDE, int DIAG = 0, int COLS = 0, int REGS = -1>
 __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     const IndT* __restrict__ indptr, const int64_t* __restrict__ dict_ptr, const int32_t* __restrict__ dict, ChunkGrid cg,
     const float* __restrict__ packed, unsigned last_gate, float fill, int window_cap, long n_vox, float* __restrict__ out,
     const rg_u32x4* __restrict__ rec, const int64_t* __restrict__ rec_ptr, unsigned w_base, int lanes_hint,
-    int rec_order, unsigned n_chunks, int chunks_per_block, const RowwiseColumns cols) {
+    int rec_order, unsigned n_chunks, int chunks_per_block, const std::conditional_t<COLS == 2, RowwisePlanes, RowwiseColumns> cols) {
   static_assert(NF >= 1 && NF <= 8 && STRIDE == stride_for(NF), "passes of 1-8 fields");
+  constexpr bool PLANES = COLS == 2;
+  static_assert(!PLANES || NF <= 4, "the planes mode is the column mode of 1-4 fields");
   using Cfg = RowwiseConfig<NF>;
   constexpr int KPRE = Cfg::kpre;
   // Record prefetch (experiment builds only; measured SLOWER, EXPERIMENTS.md R4.11): touch loads -- one dword per 64 bytes, never
@@ -627,6 +638,13 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   unsigned col_yg = 0, col_sx = 0, col_piece = 0;
   int col_z0 = 0;
   ColumnBest best[COLS ? NF : 1];
+  // PLANES: running minimum, float32 sum and count of the mean (per field)
+  float pmin[PLANES ? NF : 1], psum[PLANES ? NF : 1];
+  int pcnt[PLANES ? NF : 1];
+  if constexpr (PLANES) {
+#pragma unroll
+    for (int f = 0; f < NF; ++f) { pmin[f] = __builtin_nanf(""); psum[f] = 0.0f; pcnt[f] = 0; }
+  }
   if constexpr (COLS) {
     const unsigned item = cols.order ? (unsigned)cols.order[blockIdx.x] : blockIdx.x;
     col_piece = item / cols.n_cols;
@@ -1166,6 +1184,16 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
 #endif
   }
   if constexpr (kPrefetch > 0) asm volatile("" : : "v"(pf_d0), "v"(pf_d1));      // the touches end here
+  // PLANES: the selection words of lane == row, read again at every level (from L2: 4 bytes per selection and row) rather than
+  // kept in registers through the streaming loop, where they would cost two fields a wavefront per SIMD
+  // (32-bit pixel offsets from wave-uniform bases: the loads and stores take the scalar-base form, no 64-bit address per lane)
+  int psel[PLANES ? RG_MAX_SEL_PLANES : 1];
+  unsigned pxy = 0;
+  if constexpr (PLANES) {
+    pxy = (unsigned)(r0 - (long)(col_z0 + cb) * cols.n_xy) + (unsigned)lane;
+#pragma unroll
+    for (int s = 0; s < RG_MAX_SEL_PLANES; ++s) psel[s] = (s < cols.n_sel && lane < nrows) ? cols.sel[s][pxy] : RG_PPI_SEL_NONE;
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1215,6 +1243,24 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
         if (cols.planes && z >= cols.keep_lo && z < cols.keep_lo + cols.n_keep)
           cols.planes[((size_t)f * cols.n_keep + (z - cols.keep_lo)) * cols.n_xy + (r0 - (long)z * cols.n_xy) + lane] = val;
         if (cols.col_val && z >= cols.col_lo && z <= cols.col_hi) column_max_step(best[f], val, z);
+        if constexpr (PLANES) {
+          if (z >= cols.col_lo && z <= cols.col_hi) {
+            if (cols.col_min) column_min_step(pmin[f], val);
+            if (cols.col_mean) {                    // np.nanmean: NaN -> 0, float32 adds in level order (rg_products.hip)
+              const bool nan = isnan(val);
+              psum[f] = __fadd_rn(psum[f], nan ? 0.0f : val);
+              pcnt[f] += nan ? 0 : 1;
+            }
+          }
+#pragma unroll
+          for (int s = 0; s < RG_MAX_SEL_PLANES; ++s) {
+            if (s < cols.n_sel) {
+              float* const smp = cols.samples + ((size_t)(f * cols.n_sel + s) * 2) * cols.n_xy;    // [f][s][0 | 1][pixel]
+              if (z == (psel[s] & 0xFFFF)) smp[pxy] = val;
+              if (z == (int)((unsigned)psel[s] >> 16)) smp[cols.n_xy + pxy] = val;
+            }
+          }
+        }
       } else {
         out[(size_t)f * n_vox + r0 + lane] = s.y > 0.0f ? (float)((double)s.x / (double)s.y) : fill;
       }
@@ -1230,7 +1276,20 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     }
   }
   }   // chunks of this workgroup
-  if constexpr (COLS) {
+  if constexpr (PLANES) {
+    if (lane < col_nrows) {
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        const size_t o = ((size_t)col_piece * NF + f) * cols.n_xy + col_xy;
+        if (cols.col_val) {
+          cols.col_val[o] = best[f].v;
+          if (cols.col_arg) cols.col_arg[o] = best[f].idx;
+        }
+        if (cols.col_min) cols.col_min[o] = pmin[f];
+        if (cols.col_mean) cols.col_mean[o] = (float)((double)psum[f] / (double)pcnt[f]);      // 0 / 0 -> NaN; one piece
+      }
+    }
+  } else if constexpr (COLS) {
     if (cols.col_val && lane < col_nrows) {
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
@@ -1282,23 +1341,23 @@ int launch_rowwise(int window_cap, const void* indptr, const int64_t* dict_ptr, 
 }  // namespace
 
 // Column mode of the row-wise kernel: the launcher rg_csr_columns.hip calls (declared in rg_compact_layout.hpp).
-template <typename IndT, int NF>
+template <typename IndT, int NF, bool PLANES = false, typename Cols = RowwiseColumns>
 static int launch_rowwise_columns_t(int window_cap, const void* indptr, const int64_t* dict_ptr, const int32_t* dict,
                                     const ChunkGrid& cg, long n_vox, const float* packed, long n_gates, float fill, float* out,
                                     hipStream_t s, const void* rec, const int64_t* rec_ptr, unsigned w_base, int rec_order,
-                                    int lanes_hint, const RowwiseColumns& cols) {
+                                    int lanes_hint, const Cols& cols) {
   constexpr int STRIDE = stride_for(NF);
   constexpr int WS = rowwise_entry_words<NF>();
   constexpr int kRegsCols = -1;      // (four fields with the row sums in LDS: 108 instead of 111 VGPRs, the same 4 wavefronts)
   constexpr long kStatic = RowwiseConfig<NF>::regs ? 16 : (long)kH * 64 * NF * 8;
   const long room = (65536 - kStatic - 256) / (4 * WS) - 1;
   if (window_cap > room) window_cap = (int)room;
-  hipLaunchKernelGGL((csr_compact_rowwise_kernel<IndT, NF, STRIDE, 0, true, kRegsCols>), dim3(cols.n_cols * (unsigned)cols.pieces),
+  hipLaunchKernelGGL((csr_compact_rowwise_kernel<IndT, NF, STRIDE, 0, PLANES ? 2 : 1, kRegsCols>), dim3(cols.n_cols * (unsigned)cols.pieces),
                      dim3(64 * kH), ((size_t)(window_cap + 1) * WS * sizeof(float) + 15) / 16 * 16, s,
                      static_cast<const IndT*>(indptr), dict_ptr, dict, cg, packed, (unsigned)(n_gates - 1), fill, window_cap, n_vox,
                      out, static_cast<const rg_u32x4*>(rec), rec_ptr, w_base, lanes_hint, rec_order,
                      (unsigned)chunk_count(cg), 1, cols);
-  return rg::check_launch("rg_csr_compact_apply_columns_f32");
+  return rg::check_launch(PLANES ? "rg_csr_compact_apply_planes_f32" : "rg_csr_compact_apply_columns_f32");
 }
 
 int rg_launch_rowwise_columns(int nf, bool i64, int window_cap, const void* indptr, const int64_t* dict_ptr, const int32_t* dict,
@@ -1323,6 +1382,31 @@ int rg_launch_rowwise_columns(int nf, bool i64, int window_cap, const void* indp
     default: return RG_COLS(int32_t, 4);
   }
 #undef RG_COLS
+}
+
+// Planes mode (rg_csr_compact_apply_planes_f32): the same launch with the wider epilogue.
+int rg_launch_rowwise_planes(int nf, bool i64, int window_cap, const void* indptr, const int64_t* dict_ptr, const int32_t* dict,
+                             const ChunkGrid& cg, long n_vox, const float* packed, long n_gates, float fill, float* out,
+                             hipStream_t s, const void* rec, const int64_t* rec_ptr, unsigned w_base, int rec_order,
+                             int lanes_hint, const RowwisePlanes& cols) {
+#define RG_PLANES(IND_, NF_) \
+  launch_rowwise_columns_t<IND_, NF_, true>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, rec,  \
+                                            rec_ptr, w_base, rec_order, lanes_hint, cols)
+  if (i64) {
+    switch (nf) {
+      case 1: return RG_PLANES(int64_t, 1);
+      case 2: return RG_PLANES(int64_t, 2);
+      case 3: return RG_PLANES(int64_t, 3);
+      default: return RG_PLANES(int64_t, 4);
+    }
+  }
+  switch (nf) {
+    case 1: return RG_PLANES(int32_t, 1);
+    case 2: return RG_PLANES(int32_t, 2);
+    case 3: return RG_PLANES(int32_t, 3);
+    default: return RG_PLANES(int32_t, 4);
+  }
+#undef RG_PLANES
 }
 
 namespace {

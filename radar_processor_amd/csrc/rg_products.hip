@@ -1,5 +1,7 @@
 // K3  column reduce (COLMAX / COLMIN / COLMEAN, optional arg index)  -- radar_grid/products.py:420-580
 // K4  CAPPI linear interpolation between two levels                  -- radar_grid/products.py:406-412
+// constant-elevation PPI from the stored grid, and in two halves around the planes mode of the row-wise kernel (plan: the
+// levels each pixel reads; finish: combine the two samples)           -- radar_grid/products.py:168-314
 //
 // Roofline: HBM, pure streaming.  Algorithmic bytes: K3 4*(z_hi-z_lo+1)*Vxy read + 4*Vxy (+4*Vxy arg)
 // written; K4 8*Vxy read + 4*Vxy written.
@@ -180,6 +182,46 @@ __device__ __forceinline__ double ppi_target_z(const PpiArgs& a, float x, float 
   return (double)hd * a.tan_e + 0.0;                                           // products.py:165
 }
 
+// The per-pixel plan of a PPI: the levels a pixel reads (products.py:280-294 linear, :263-268 nearest), the upper weight
+// (linear, :284) and whether the pixel takes a value at all (linear: :306-309; nearest: :266).  Shared by
+// elevation_ppi_kernel (stored grid) and ppi_plan_kernel (rg_csr_compact_apply_planes_f32 samples the levels).
+struct PpiPixel {
+  long lo_s, hi_s;   // clamped levels (nearest: both ks)
+  double w_hi;       // linear only
+  bool in_range;
+};
+
+template <bool LINEAR>
+__device__ __forceinline__ PpiPixel ppi_plan_pixel(const PpiArgs& a, float x, float y) {
+  PpiPixel p;
+  const double tz = ppi_target_z(a, x, y);
+  const double zf = (tz - a.z_min) / a.z_step;                                 // products.py:263,279
+  if constexpr (LINEAR) {
+    const double fl = floor(zf);
+    const long lo = (long)fl, hi = lo + 1;                                     // products.py:280-281
+    p.w_hi = zf - (double)lo;                                                  // products.py:284
+    p.lo_s = lo < 0 ? 0 : (lo > a.nz - 1 ? a.nz - 1 : lo);                     // products.py:293-294
+    p.hi_s = hi < 0 ? 0 : (hi > a.nz - 1 ? a.nz - 1 : hi);
+    p.in_range = !(tz < a.z_min || tz > a.z_max);                              // products.py:306,309
+  } else {
+    const double rn = rint(zf);                                                // np.round: half to even
+    const long k = (long)rn;
+    p.in_range = k >= 0 && k < a.nz;                                           // products.py:266
+    p.lo_s = p.hi_s = k < 0 ? 0 : (k > a.nz - 1 ? a.nz - 1 : k);
+    p.w_hi = 0.0;
+  }
+  return p;
+}
+
+// products.py:285,303 (float64, NaN off the grid's altitudes) and :271-272 (float32 nearest level)
+__device__ __forceinline__ double ppi_combine_linear(double w_hi, float v_lo, float v_hi, bool in_range) {
+  const double w_lo = 1.0 - w_hi;                                              // products.py:285
+  double r = w_lo * (double)v_lo + w_hi * (double)v_hi;                        // products.py:303
+  if (!in_range) r = __builtin_nan("");                                        // products.py:306,309
+  return r;
+}
+__device__ __forceinline__ float ppi_combine_nearest(float v, bool in_range) { return in_range ? v : __builtin_nanf(""); }
+
 template <bool LINEAR>
 __global__ __launch_bounds__(rg::kBlock) void elevation_ppi_kernel(const float* __restrict__ grid,
                                                                    const float* __restrict__ xc,
@@ -189,25 +231,35 @@ __global__ __launch_bounds__(rg::kBlock) void elevation_ppi_kernel(const float* 
   const long n_xy = (long)a.ny * a.nx;
   if (i >= n_xy) return;
   const int ix = (int)(i % a.nx), iy = (int)(i / a.nx);
-  const double tz = ppi_target_z(a, xc[ix], yc[iy]);
-  const double zf = (tz - a.z_min) / a.z_step;                                 // products.py:263,279
-  if constexpr (LINEAR) {
-    const double fl = floor(zf);
-    const long lo = (long)fl, hi = lo + 1;                                     // products.py:280-281
-    const double w_hi = zf - (double)lo, w_lo = 1.0 - w_hi;                    // products.py:284-285
-    const long lo_s = lo < 0 ? 0 : (lo > a.nz - 1 ? a.nz - 1 : lo);            // products.py:293-294
-    const long hi_s = hi < 0 ? 0 : (hi > a.nz - 1 ? a.nz - 1 : hi);
-    const double v_lo = (double)grid[lo_s * n_xy + i], v_hi = (double)grid[hi_s * n_xy + i];
-    double r = w_lo * v_lo + w_hi * v_hi;                                      // products.py:303
-    if (tz < a.z_min || tz > a.z_max) r = __builtin_nan("");                  // products.py:306,309
-    out64[i] = r;
-  } else {
-    const double rn = rint(zf);                                                // np.round: half to even
-    const long k = (long)rn;
-    const bool valid = k >= 0 && k < a.nz;                                     // products.py:266
-    const long ks = k < 0 ? 0 : (k > a.nz - 1 ? a.nz - 1 : k);
-    out32[i] = valid ? grid[ks * n_xy + i] : __builtin_nanf("");              // products.py:271-272
-  }
+  const PpiPixel p = ppi_plan_pixel<LINEAR>(a, xc[ix], yc[iy]);
+  if constexpr (LINEAR) out64[i] = ppi_combine_linear(p.w_hi, grid[p.lo_s * n_xy + i], grid[p.hi_s * n_xy + i], p.in_range);
+  else out32[i] = ppi_combine_nearest(grid[p.lo_s * n_xy + i], p.in_range);
+}
+
+// rg_elevation_ppi_plan_f32: the plan as selection words (lo_s | hi_s << 16, RG_PPI_SEL_NONE where the pixel is NaN) + w_hi
+template <bool LINEAR>
+__global__ __launch_bounds__(rg::kBlock) void ppi_plan_kernel(const float* __restrict__ xc, const float* __restrict__ yc,
+                                                              PpiArgs a, int32_t* __restrict__ sel, double* __restrict__ w_hi) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n_xy = (long)a.ny * a.nx;
+  if (i >= n_xy) return;
+  const int ix = (int)(i % a.nx), iy = (int)(i / a.nx);
+  const PpiPixel p = ppi_plan_pixel<LINEAR>(a, xc[ix], yc[iy]);
+  sel[i] = p.in_range ? (int32_t)((unsigned)p.lo_s | ((unsigned)p.hi_s << 16)) : RG_PPI_SEL_NONE;
+  if constexpr (LINEAR) w_hi[i] = p.w_hi;
+}
+
+// rg_elevation_ppi_finish_f32: samples [2][n_xy] of the pixel's two levels -> the PPI value
+template <bool LINEAR>
+__global__ __launch_bounds__(rg::kBlock) void ppi_finish_kernel(const int32_t* __restrict__ sel, const double* __restrict__ w_hi,
+                                                                const float* __restrict__ samples, long n_xy,
+                                                                double* __restrict__ out64, float* __restrict__ out32) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_xy) return;
+  const bool in_range = sel[i] != RG_PPI_SEL_NONE;
+  const float v_lo = in_range ? samples[i] : 0.0f;       // pixels without a selection were never sampled
+  if constexpr (LINEAR) out64[i] = ppi_combine_linear(w_hi[i], v_lo, in_range ? samples[n_xy + i] : 0.0f, in_range);
+  else out32[i] = ppi_combine_nearest(v_lo, in_range);
 }
 
 template <int OP>
@@ -288,4 +340,44 @@ extern "C" int rg_elevation_ppi_f32(const float* grid, const float* xc, const fl
   else
     hipLaunchKernelGGL(elevation_ppi_kernel<false>, g, b, 0, s, grid, xc, yc, a, (double*)nullptr, static_cast<float*>(out));
   return rg::check_launch("rg_elevation_ppi_f32");
+}
+
+static void ppi_args(PpiArgs* a, double cos_clamped, double sin_elev, double tan_elev, double ke_re, double ke_re_sq,
+                     double z_min, double z_max, double z_step, int32_t earth_curvature, int32_t nz, int32_t ny, int32_t nx) {
+  a->cos_c = cos_clamped; a->sin_e = sin_elev; a->tan_e = tan_elev; a->ke_re = ke_re; a->ke_re2 = ke_re_sq;
+  a->z_min = z_min; a->z_max = z_max; a->z_step = z_step; a->curved = earth_curvature != 0; a->nz = nz; a->ny = ny; a->nx = nx;
+}
+
+extern "C" int rg_elevation_ppi_plan_f32(const float* xc, const float* yc, int32_t nz, int32_t ny, int32_t nx,
+                                         double cos_clamped, double sin_elev, double tan_elev, double ke_re, double ke_re_sq,
+                                         double z_min, double z_max, double z_step, int32_t earth_curvature, int32_t linear,
+                                         int32_t* sel, double* w_hi, rg_stream_t stream) {
+  RG_REQUIRE(xc && yc && sel, RG_EINVAL, "rg_elevation_ppi_plan_f32: null pointer");
+  RG_REQUIRE(!linear || w_hi, RG_EINVAL, "rg_elevation_ppi_plan_f32: linear interpolation needs w_hi");
+  RG_REQUIRE(nz >= 1 && nz < 0xFFFF && ny >= 1 && nx >= 1, RG_EINVAL, "rg_elevation_ppi_plan_f32: bad shape (%d,%d,%d)", nz, ny,
+             nx);
+  RG_REQUIRE(z_step != 0.0, RG_EINVAL, "rg_elevation_ppi_plan_f32: z_step is zero");
+  PpiArgs a;
+  ppi_args(&a, cos_clamped, sin_elev, tan_elev, ke_re, ke_re_sq, z_min, z_max, z_step, earth_curvature, nz, ny, nx);
+  const long n_xy = (long)ny * nx;
+  const dim3 g((unsigned)((n_xy + rg::kBlock - 1) / rg::kBlock)), b(rg::kBlock);
+  hipStream_t s = (hipStream_t)stream;
+  if (linear) hipLaunchKernelGGL(ppi_plan_kernel<true>, g, b, 0, s, xc, yc, a, sel, w_hi);
+  else hipLaunchKernelGGL(ppi_plan_kernel<false>, g, b, 0, s, xc, yc, a, sel, (double*)nullptr);
+  return rg::check_launch("rg_elevation_ppi_plan_f32");
+}
+
+extern "C" int rg_elevation_ppi_finish_f32(const int32_t* sel, const double* w_hi, const float* samples, int64_t n_xy,
+                                           int32_t linear, void* out, rg_stream_t stream) {
+  RG_REQUIRE(sel && samples && out, RG_EINVAL, "rg_elevation_ppi_finish_f32: null pointer");
+  RG_REQUIRE(!linear || w_hi, RG_EINVAL, "rg_elevation_ppi_finish_f32: linear interpolation needs w_hi");
+  RG_REQUIRE(n_xy >= 0, RG_EINVAL, "rg_elevation_ppi_finish_f32: bad size");
+  if (n_xy == 0) return RG_OK;
+  const dim3 g((unsigned)((n_xy + rg::kBlock - 1) / rg::kBlock)), b(rg::kBlock);
+  hipStream_t s = (hipStream_t)stream;
+  if (linear)
+    hipLaunchKernelGGL(ppi_finish_kernel<true>, g, b, 0, s, sel, w_hi, samples, (long)n_xy, static_cast<double*>(out), (float*)nullptr);
+  else
+    hipLaunchKernelGGL(ppi_finish_kernel<false>, g, b, 0, s, sel, w_hi, samples, (long)n_xy, (double*)nullptr, static_cast<float*>(out));
+  return rg::check_launch("rg_elevation_ppi_finish_f32");
 }

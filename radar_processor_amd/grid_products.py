@@ -168,6 +168,24 @@ def constant_altitude_ppi(grid, geometry: GridGeometry, altitude: float, interpo
     return _finish(out, as_numpy)
 
 
+def _ppi_scalars(geometry: GridGeometry, elevation_angle: float, interpolation: str, earth_curvature: bool, ke: float):
+    """The host half of a constant-elevation PPI (``radar_grid/products.py:168-314``): shape, the float32 coordinate tables
+    (NumPy arrays) and the scalars NumPy evaluates once, in the argument order of ``rg_elevation_ppi_f32``."""
+    if interpolation not in ("linear", "nearest"):
+        raise ValueError(f"Unknown interpolation method: {interpolation}")
+    nz, ny, nx = (int(v) for v in geometry.grid_shape)
+    z_min, z_max = geometry.grid_limits[0]
+    (y_lo, y_hi), (x_lo, x_hi) = geometry.grid_limits[1], geometry.grid_limits[2]
+    z_step = (z_max - z_min) / (nz - 1) if nz > 1 else 1.0
+    el = np.radians(elevation_angle)
+    r_eff = ke * EARTH_RADIUS
+    xc = np.linspace(x_lo, x_hi, nx, dtype="float32")
+    yc = np.linspace(y_lo, y_hi, ny, dtype="float32")
+    scalars = (float(np.maximum(np.cos(el), 0.01)), float(np.sin(el)), float(np.tan(el)), float(r_eff), float(r_eff**2),
+               float(z_min), float(z_max), float(z_step), int(bool(earth_curvature)), int(interpolation == "linear"))
+    return (nz, ny, nx), xc, yc, scalars
+
+
 def constant_elevation_ppi(grid, geometry: GridGeometry, elevation_angle: float, interpolation: str = "linear",
                            earth_curvature: bool = True, ke: float = EFFECTIVE_RADIUS_FACTOR):
     """PPI at a constant elevation angle sampled from the 3-D grid (``radar_grid/products.py:168-314``).
@@ -177,28 +195,62 @@ def constant_elevation_ppi(grid, geometry: GridGeometry, elevation_angle: float,
     ``[z_min, z_max]``), ``'nearest'`` samples the nearest level and returns float32.  Runs in
     ``rg_elevation_ppi_f32``; bit-identical to the reference's NumPy evaluation.
     """
-    if interpolation not in ("linear", "nearest"):
-        raise ValueError(f"Unknown interpolation method: {interpolation}")
-    nz, ny, nx = (int(v) for v in geometry.grid_shape)
-    z_min, z_max = geometry.grid_limits[0]
-    (y_lo, y_hi), (x_lo, x_hi) = geometry.grid_limits[1], geometry.grid_limits[2]
-    z_step = (z_max - z_min) / (nz - 1) if nz > 1 else 1.0
-    el = np.radians(elevation_angle)
-    r_eff = ke * EARTH_RADIUS
+    (nz, ny, nx), xc_h, yc_h, scalars = _ppi_scalars(geometry, elevation_angle, interpolation, earth_curvature, ke)
     torch = _native.torch_mod()
     lib = _native.load_library()
     g, as_numpy = _to_device_grid(grid)
-    xc = torch.from_numpy(np.linspace(x_lo, x_hi, nx, dtype="float32")).to(g.device)
-    yc = torch.from_numpy(np.linspace(y_lo, y_hi, ny, dtype="float32")).to(g.device)
+    xc = torch.from_numpy(xc_h).to(g.device)
+    yc = torch.from_numpy(yc_h).to(g.device)
     linear = interpolation == "linear"
     out = torch.empty((ny, nx), dtype=torch.float64 if linear else torch.float32, device=g.device)
     with torch.cuda.device(g.device):
-        _native.check(lib.rg_elevation_ppi_f32(
-            _native.ptr(g), _native.ptr(xc), _native.ptr(yc), nz, ny, nx, float(np.maximum(np.cos(el), 0.01)),
-            float(np.sin(el)), float(np.tan(el)), float(r_eff), float(r_eff**2), float(z_min), float(z_max),
-            float(z_step), int(bool(earth_curvature)), int(linear), _native.ptr(out), _native.stream_ptr()),
-            "rg_elevation_ppi_f32")
+        _native.check(lib.rg_elevation_ppi_f32(_native.ptr(g), _native.ptr(xc), _native.ptr(yc), nz, ny, nx, *scalars,
+                                               _native.ptr(out), _native.stream_ptr()), "rg_elevation_ppi_f32")
     return _finish(out, as_numpy)
+
+
+def ppi_plan(geometry: GridGeometry, elevation_angle: float, interpolation: str = "linear", earth_curvature: bool = True,
+             ke: float = EFFECTIVE_RADIUS_FACTOR, device=None):
+    """``(sel, w_hi)`` of a constant-elevation PPI on ``device`` (``rg_elevation_ppi_plan_f32``): int32 ``[ny, nx]`` words
+    ``lo | hi << 16`` naming the level(s) each pixel reads (``RG_PPI_SEL_NONE`` where it is NaN whatever the grid holds) and
+    the float64 upper weight (``None`` for ``'nearest'``).  What a products-only pass needs to sample a PPI while it walks the
+    columns; cached on the geometry per (device, angle, interpolation, curvature, ke)."""
+    torch = _native.torch_mod()
+    dev = _native.canonical_device(device)
+    key = (str(dev), float(elevation_angle), interpolation, bool(earth_curvature), float(ke))
+    cache = geometry.__dict__.setdefault("_ppi_plans", {})
+    hit = cache.get(key)
+    if hit is not None:
+        return hit
+    (nz, ny, nx), xc_h, yc_h, scalars = _ppi_scalars(geometry, elevation_angle, interpolation, earth_curvature, ke)
+    lib = _native.load_library()
+    linear = interpolation == "linear"
+    with torch.cuda.device(dev):
+        xc = torch.from_numpy(xc_h).to(dev)
+        yc = torch.from_numpy(yc_h).to(dev)
+        sel = torch.empty((ny, nx), dtype=torch.int32, device=dev)
+        w_hi = torch.empty((ny, nx), dtype=torch.float64, device=dev) if linear else None
+        _native.check(lib.rg_elevation_ppi_plan_f32(_native.ptr(xc), _native.ptr(yc), nz, ny, nx, *scalars, _native.ptr(sel),
+                                                    _native.ptr(w_hi), _native.stream_ptr()), "rg_elevation_ppi_plan_f32")
+    if len(cache) >= 64:                 # a handful of angles per geometry is the norm; never grow without bound
+        cache.clear()
+    cache[key] = (sel, w_hi)
+    return sel, w_hi
+
+
+def ppi_finish(plan, samples, interpolation: str = "linear"):
+    """The PPI plane from the two level samples a products-only pass stored for one field (``samples`` ``[2, ny, nx]``
+    float32, device) and its ``ppi_plan``: ``rg_elevation_ppi_finish_f32`` -- the bits ``constant_elevation_ppi`` returns
+    from the stored grid (float64 for ``'linear'``, float32 for ``'nearest'``)."""
+    torch = _native.torch_mod()
+    sel, w_hi = plan
+    linear = interpolation == "linear"
+    out = torch.empty(tuple(sel.shape), dtype=torch.float64 if linear else torch.float32, device=sel.device)
+    lib = _native.load_library()
+    _native.check(lib.rg_elevation_ppi_finish_f32(_native.ptr(sel), _native.ptr(w_hi), _native.ptr(samples), sel.numel(),
+                                                  int(linear), _native.ptr(out), _native.stream_ptr()),
+                  "rg_elevation_ppi_finish_f32")
+    return out
 
 
 def _level_window(nz, z_min_idx, z_max_idx, z_min_alt, z_max_alt, geometry):

@@ -29,6 +29,7 @@ import numpy as np
 from . import _native
 from .gate_filters import GateFilter
 from .grid_geometry import GridGeometry
+from .grid_products import EFFECTIVE_RADIUS_FACTOR
 
 logger = logging.getLogger("radar_grid.interpolate")
 
@@ -262,6 +263,60 @@ class CsrGridder:
         return (base - (0 if store_grid else self.n_fields * 4 * self.n_vox)
                 + self.n_fields * 4 * ny * nx * (int(n_keep) + (2 if colmax else 0)))
 
+    def apply_planes(self, out=None, fill_value: float = np.nan, level_planes=None, keep_lo: int = 0, col_max=None, col_arg=None,
+                     col_min=None, col_mean=None, col_window=None, sel_levels: Sequence = (), sel_samples=None,
+                     z_pieces: int = 0, lanes_hint: int = 0, ordered: bool = True) -> None:
+        """One pass of ``rg_csr_compact_apply_planes_f32``: :meth:`apply_columns` with the wider epilogue -- next to ``out`` /
+        ``level_planes`` / ``col_max`` / ``col_arg`` (same meaning), ``col_min`` and ``col_mean`` ``[F, ny, nx]``
+        (``column_min`` / ``column_mean`` over ``col_window``) and up to ``RG_MAX_SEL_PLANES`` per-pixel level selections
+        (``sel_levels``: int32 ``[ny, nx]`` tensors from ``grid_products.ppi_plan``) whose levels land in ``sel_samples``
+        ``[F, n_sel, 2, ny, nx]`` for ``grid_products.ppi_finish``.  ``col_mean`` takes one level piece (its float32 running
+        sum cannot be split): ``z_pieces`` is then 1."""
+        torch = _native.torch_mod()
+        if not self.has_columns_kernel:
+            raise _native.NativeError("the planes mode needs the packed records (1-4 fields, codable weights)")
+        csr, c = self.csr, self.compact
+        nz, ny, nx = self.grid_shape
+        n_sel = len(sel_levels)
+        if n_sel > _native.RG_MAX_SEL_PLANES:
+            raise ValueError(f"at most {_native.RG_MAX_SEL_PLANES} level selections per launch, got {n_sel}")
+        lo, hi = (0, nz - 1) if col_window is None else (int(col_window[0]), int(col_window[1]))
+        pieces, order = self._column_plan(1 if col_mean is not None else z_pieces)
+        if not ordered:
+            order = None
+        ws = None
+        if (col_max is not None or col_min is not None) and pieces > 1:
+            nbytes = int(self.lib.rg_csr_planes_workspace_bytes(ny, nx, self.n_fields, pieces, int(col_max is not None),
+                                                                int(col_min is not None)))
+            ws = getattr(self, "_columns_ws", None)
+            if ws is None or ws.numel() < nbytes:
+                ws = self._columns_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        req = _native.PlaneRequest(out=_native.ptr(out), level_planes=_native.ptr(level_planes), keep_lo=int(keep_lo),
+                                   n_keep=0 if level_planes is None else int(level_planes.shape[1]),
+                                   col_max=_native.ptr(col_max), col_arg=_native.ptr(col_arg), col_min=_native.ptr(col_min),
+                                   col_mean=_native.ptr(col_mean), col_lo=lo, col_hi=hi, n_sel=n_sel,
+                                   sel_samples=_native.ptr(sel_samples))
+        for k, sel in enumerate(sel_levels):
+            req.sel_levels[k] = _native.ptr(sel)
+        _native.check(self.lib.rg_csr_compact_apply_planes_f32(
+            _native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(c.rec), _native.ptr(c.rec_ptr), c.rec_order, c.w_base,
+            _native.ptr(c.dict_ptr), _native.ptr(c.dict), self.n_vox, csr.n_pairs, nx, ny, _native.ptr(self.packed),
+            self.n_fields, self.stride, self.n_gates, float(np.float32(fill_value)), ctypes.byref(req), self.window, pieces,
+            _native.ptr(order), _native.ptr(ws), 0 if ws is None else int(ws.numel()), int(lanes_hint), _native.stream_ptr()),
+            "rg_csr_compact_apply_planes_f32")
+
+    def planes_bytes(self, store_grid: bool, n_keep: int = 0, colmax: bool = False, argmax: bool = False,
+                     colmin: bool = False, colmean: bool = False, n_sel: int = 0) -> Optional[int]:
+        """Bytes one ``apply_planes`` launch must move: the compact kernel's, minus the grids that are not stored, plus the
+        kept, max / arg / min / mean planes, the selection words read and (at most) two samples per selection written."""
+        base = self.compact_bytes()
+        if base is None:
+            return None
+        nz, ny, nx = self.grid_shape
+        per_field = int(n_keep) + int(bool(colmax)) + int(bool(argmax)) + int(bool(colmin)) + int(bool(colmean)) + 2 * int(n_sel)
+        return (base - (0 if store_grid else self.n_fields * 4 * self.n_vox) + self.n_fields * 4 * ny * nx * per_field
+                + 4 * ny * nx * int(n_sel))
+
     def algorithmic_bytes(self) -> int:
         """Bytes one ``apply`` launch must move: index + weight per pair, the row pointers,
         each field's values + mask once, each output grid once."""
@@ -451,38 +506,80 @@ class PlaneProducts:
     """The 2-D products a products-only pass keeps of every gridded field (``grid_products_device``,
     ``batch.VolumeBatch.grid_shard(products=PlaneProducts(...))``): the column maximum over a level window
     (``radar_grid/products.py:420-490``; same window arguments as ``column_max``), optionally the level that attains it
-    (``column_argmax``), and CAPPIs at the given altitudes (``products.py:317-415``).  With these and nothing else wanted,
-    the 3-D grid never has to exist in HBM: the gridding kernel, walking grid columns, keeps the running maximum in registers
-    and stores only the levels the CAPPIs blend."""
+    (``column_argmax``), the column minimum / mean over the same window (``column_min`` :493-535, ``column_mean`` :538-580),
+    CAPPIs at the given altitudes (``products.py:317-415``) and constant-elevation PPIs at the given angles (``ppi``,
+    ``constant_elevation_ppi`` :168-314).  With these and nothing else wanted, the 3-D grid never has to exist in HBM: the
+    gridding kernel, walking grid columns, keeps the running maximum / minimum / sum in registers and stores only the levels
+    the CAPPIs blend and the levels each PPI pixel reads."""
 
     def __init__(self, colmax: bool = True, argmax: bool = True, cappi: Sequence[float] = (), interpolation: str = "linear",
                  z_min_idx: Optional[int] = None, z_max_idx: Optional[int] = None, z_min_alt: Optional[float] = None,
-                 z_max_alt: Optional[float] = None, fused: Optional[bool] = None):
+                 z_max_alt: Optional[float] = None, fused: Optional[bool] = None, colmin: bool = False, colmean: bool = False,
+                 ppi: Sequence[float] = (), ppi_interpolation: str = "linear", earth_curvature: bool = True,
+                 ke: float = EFFECTIVE_RADIUS_FACTOR):
         """``fused``: ``True`` = take the planes out of the gridding kernel (no 3-D grid in HBM: the memory-saving way),
         ``False`` = grid, then reduce with the separate kernels, ``None`` = whichever the build measured faster (the same
-        planes either way, bit for bit)."""
+        planes either way, bit for bit).  ``ppi``: elevation angles (degrees); ``ppi_interpolation`` / ``earth_curvature`` /
+        ``ke`` as in ``constant_elevation_ppi`` ('linear' planes are float64, 'nearest' float32)."""
         if interpolation not in ("linear", "nearest"):
             raise ValueError(f"Unknown interpolation method: {interpolation}")
+        if ppi_interpolation not in ("linear", "nearest"):
+            raise ValueError(f"Unknown interpolation method: {ppi_interpolation}")
         self.colmax = bool(colmax or argmax)
         self.argmax = bool(argmax)
         self.cappi = tuple(float(a) for a in cappi)
         self.interpolation = interpolation
         self.window = (z_min_idx, z_max_idx, z_min_alt, z_max_alt)
         self.fused = fused
+        self.colmin = bool(colmin)
+        self.colmean = bool(colmean)
+        self.ppi = tuple(float(e) for e in ppi)
+        self.ppi_interpolation = ppi_interpolation
+        self.earth_curvature = bool(earth_curvature)
+        self.ke = float(ke)
+
+    @property
+    def columns(self) -> bool:
+        """Any product over the level window."""
+        return self.colmax or self.colmin or self.colmean
+
+    @property
+    def needs_planes_mode(self) -> bool:
+        """Products the column mode's epilogue (``rg_csr_compact_apply_columns_f32``) does not compute: the fused pass runs
+        ``rg_csr_compact_apply_planes_f32`` instead."""
+        return self.colmin or self.colmean or bool(self.ppi)
+
+
+def reduce_planes(products: PlaneProducts, grid, geometry, lo: int, hi: int, rec: dict) -> dict:
+    """The separate-kernel route of the products ``rg_csr_compact_apply_columns_f32`` does not compute, for one stored grid
+    ``[nz, ny, nx]`` (device): ``colmin`` / ``colmean`` over levels ``lo .. hi`` and ``ppi`` -- added to ``rec``."""
+    from . import grid_products as gp
+    if products.colmin:
+        rec["colmin"] = gp._column("min", grid, lo, hi, None, None, None)
+    if products.colmean:
+        rec["colmean"] = gp._column("mean", grid, lo, hi, None, None, None)
+    if products.ppi:
+        rec["ppi"] = {e: gp.constant_elevation_ppi(grid, geometry, e, products.ppi_interpolation, products.earth_curvature,
+                                                   products.ke) for e in products.ppi}
+    return rec
 
 
 def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Optional[Sequence] = None, shared_mask=None,
                          products: Optional[PlaneProducts] = None, fill_value: float = np.nan, fused: Optional[bool] = None):
     """Grid device-resident fields and return ONLY 2-D products: a list with one ``dict`` per field --
-    ``{"colmax": [ny, nx] float32, "argmax": [ny, nx] int32, "cappi": {altitude: [ny, nx] float32}}`` (keys present as
-    requested by ``products``).  The planes are bit-identical to ``column_argmax`` / ``constant_altitude_ppi`` applied to
-    the grid ``grid_fields_device`` returns for the same pass.
+    ``{"colmax": [ny, nx] float32, "argmax": [ny, nx] int32, "colmin": [ny, nx] float32, "colmean": [ny, nx] float32,
+    "cappi": {altitude: [ny, nx] float32}, "ppi": {angle: [ny, nx] float64 / float32}}`` (keys present as requested by
+    ``products``).  The planes are bit-identical to ``column_argmax`` / ``column_min`` / ``column_mean`` /
+    ``constant_altitude_ppi`` / ``constant_elevation_ppi`` applied to the grid ``grid_fields_device`` returns for the same
+    pass.
 
     ``fused=True``: on large geometries (packed records present) every group of up to four field-volumes runs as ONE launch
     of the row-wise kernel in column mode with its products epilogue -- no 3-D grid is written or read back (640 MB each
     way per field on the bench grid), so a pass needs no grid memory at all; it takes about as long as gridding + reducing
-    separately (measured, see below).  Default (``fused=None``) and ``fused=False``: grid as usual, reduce with the separate
-    kernels."""
+    separately (measured, see below).  COLMAX / argmax / CAPPI alone run ``rg_csr_compact_apply_columns_f32``; a request
+    with a column minimum, mean or PPI runs ``rg_csr_compact_apply_planes_f32`` (a mean keeps each column in one workgroup;
+    more than ``RG_MAX_SEL_PLANES`` PPIs take further launches of it, each gridding the fields again).  Default
+    (``fused=None``) and ``fused=False``: grid as usual, reduce with the separate kernels."""
     from . import grid_products as gp
     torch = _native.torch_mod()
     products = products if products is not None else PlaneProducts()
@@ -498,7 +595,7 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
         masks = [None] * n_fields
     nz, ny, nx = (int(s) for s in geometry.grid_shape)
     lo, hi = gp._level_window(nz, *products.window, geometry)
-    if products.colmax and lo > hi:
+    if products.columns and lo > hi:
         raise ValueError(f"empty level window [{lo}, {hi}]")
     plans = {alt: gp.cappi_plan(geometry.grid_limits[0], nz, alt, products.interpolation) for alt in products.cappi}
     for alt, plan in plans.items():
@@ -508,6 +605,7 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
     needed = sorted({k for plan in plans.values() if plan[0] != "outside" for k in ((plan[1], plan[1] + 1) if plan[0] == "blend"
                                                                                     else (plan[1],))})
     keep_lo, n_keep = (needed[0], needed[-1] - needed[0] + 1) if needed else (0, 0)
+    angles = list(dict.fromkeys(products.ppi))
     n_gates = int(fields[0].numel())
     results = []
     with torch.cuda.device(dev):
@@ -524,11 +622,15 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
             # saves costs -- 8.2 vs 8.1 ms for one field, 10.7 vs 10.5 for three, 11.4 vs 11.2 for four on the bench grid --
             # so the epilogue is the MEMORY-saving choice (no F x 640 MB of grid) and is taken on request, not by default
             run_fused = (gridder.has_columns_kernel and (nf >= _COLUMNS_FUSE_MIN_FIELDS if fused is None else bool(fused)))
+            fused_planes = {}
             if run_fused:
                 cmax = torch.empty((nf, ny, nx), dtype=torch.float32, device=dev) if products.colmax else None
                 carg = torch.empty((nf, ny, nx), dtype=torch.int32, device=dev) if products.argmax else None
                 planes = torch.empty((nf, n_keep, ny, nx), dtype=torch.float32, device=dev) if n_keep else None
-                if cmax is None and planes is None:      # nothing but out-of-range CAPPIs
+                if products.needs_planes_mode:
+                    fused_planes = _fused_planes_pass(gridder, products, geometry, fill_value, planes, keep_lo, cmax, carg,
+                                                      (lo, hi), angles)
+                elif cmax is None and planes is None:      # nothing but out-of-range CAPPIs
                     pass
                 else:
                     gridder.apply_columns(out=None, fill_value=fill_value, level_planes=planes, keep_lo=keep_lo, col_max=cmax,
@@ -551,6 +653,13 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
                         rec["colmax"], rec["argmax"] = got if products.argmax else (got, None)
                         if not products.argmax:
                             del rec["argmax"]
+                if run_fused:
+                    for key in ("colmin", "colmean"):
+                        if key in fused_planes:
+                            rec[key] = fused_planes[key][k]
+                else:
+                    reduce_planes(products, grids[k], geometry, lo, hi, rec)
+                    ppi_recs = rec.pop("ppi", None)
                 if products.cappi:
                     rec["cappi"] = {}
                     for alt, plan in plans.items():
@@ -565,8 +674,48 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
                                                                         float(np.float32(plan[2])), float(np.float32(plan[3])),
                                                                         _native.ptr(out), _native.stream_ptr()), "rg_cappi_lerp_f32")
                             rec["cappi"][alt] = out
+                if products.ppi:
+                    rec["ppi"] = fused_planes["ppi"][k] if run_fused else ppi_recs
                 results.append(rec)
     return results
+
+
+def _fused_planes_pass(gridder: CsrGridder, products: PlaneProducts, geometry: GridGeometry, fill_value, planes, keep_lo,
+                       cmax, carg, window, angles) -> dict:
+    """The planes-mode launches of one field group (``grid_products_device``): the first computes every column product, the
+    kept levels and the samples of the first ``RG_MAX_SEL_PLANES`` PPIs; any further PPIs take one more launch per
+    ``RG_MAX_SEL_PLANES``.  Returns ``{"colmin": [F, ny, nx], "colmean": [F, ny, nx], "ppi": [one {angle: plane} per field]}``
+    (keys as requested)."""
+    from . import grid_products as gp
+    torch = _native.torch_mod()
+    dev = gridder.dev
+    nf = gridder.n_fields
+    _, ny, nx = gridder.grid_shape
+    got = {}
+    cmin = torch.empty((nf, ny, nx), dtype=torch.float32, device=dev) if products.colmin else None
+    cmean = torch.empty((nf, ny, nx), dtype=torch.float32, device=dev) if products.colmean else None
+    ppi_plans = [gp.ppi_plan(geometry, e, products.ppi_interpolation, products.earth_curvature, products.ke, dev)
+                 for e in angles]
+    cap = _native.RG_MAX_SEL_PLANES
+    groups = [list(range(g0, min(len(angles), g0 + cap))) for g0 in range(0, len(angles), cap)] or [[]]
+    per_field = [{} for _ in range(nf)]
+    for gi, group in enumerate(groups):
+        first = gi == 0
+        samples = torch.empty((nf, len(group), 2, ny, nx), dtype=torch.float32, device=dev) if group else None
+        gridder.apply_planes(out=None, fill_value=fill_value, level_planes=planes if first else None, keep_lo=keep_lo,
+                             col_max=cmax if first else None, col_arg=carg if first else None,
+                             col_min=cmin if first else None, col_mean=cmean if first else None, col_window=window,
+                             sel_levels=[ppi_plans[i][0] for i in group], sel_samples=samples)
+        for j, i in enumerate(group):
+            for k in range(nf):
+                per_field[k][angles[i]] = gp.ppi_finish(ppi_plans[i], samples[k, j], products.ppi_interpolation)
+    if cmin is not None:
+        got["colmin"] = cmin
+    if cmean is not None:
+        got["colmean"] = cmean
+    if products.ppi:
+        got["ppi"] = per_field
+    return got
 
 
 def _to_host(t) -> np.ndarray:
