@@ -20,7 +20,9 @@
 //     constants live in its registers, its sums never leave it -- and tests 4 records per step (LDS broadcast
 //     reads).  float32 d2 decides membership whenever it is clear of the rim by 2e-6; inside that band the lane
 //     falls back to the reference's exact float64 `d2 < r2` (compute.py:69-74), so the neighbour set equals the
-//     CSR builder's.  Weight in float32 (|rel err| < 2e-6).  The packed field slots of a gate are fetched once,
+//     CSR builder's.  Barnes and uniform weights in float32 (|rel err| < 2e-6); the Cressman numerator r2 - d2
+//     from the float64 d2 (from the float32 d2 it cancels at the rim: a hit there could weigh 0 or less), its
+//     denominator in float32 (|rel err| < 5e-7).  The packed field slots of a gate are fetched once,
 //     when the gate is queued, and parked in a second LDS ring one candidate step later; the dense stage reads
 //     records and values from LDS one step ahead of its arithmetic;
 //   * per block two wavefront shuffles fold the 4 record slots; 16 lanes store 16 consecutive voxels per field.
@@ -48,7 +50,8 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 }
 
 
-// float32 weight from the float32 d2 (compute.py:82-87); relative error < 2e-6
+// float32 weight from the float32 d2 (compute.py:82-87): Barnes (>= e^-4 inside the ROI) and uniform; relative error
+// < 2e-6.  Not Cressman, whose numerator r2 - d2 cancels near the rim (grid mode takes it from the float64 d2).
 // inv_r2q: Barnes -- MINUS log2(e) * 4 / r2, so that exp(-d2 / (r2 / 4)) is one multiply and one v_exp_f32 (= 2^x)
 template <int W>
 __device__ __forceinline__ float weight_from_f32(float d2f, float r2f, float inv_r2q) {
@@ -228,7 +231,16 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
           cursor += __popcll(hits & vox_lanes);
         } else {
           if (in) {
-            const float w = weight_from_f32<W>(d2f, r2f, inv_r2q);
+            float w;
+            if constexpr (W == RG_W_CRESSMAN) {
+              // (r2 - d2) / (r2 + d2), compute.py:85: the numerator cancels at the rim -- from the float32 d2 it can be 0 or
+              // negative for a gate the float64 test admitted.  Numerator from the reference's float64 d2 (unfused, as the
+              // test: r2 - d2 > 0 for every hit), rounded once; denominator in float32 (no cancellation): |rel err| < 5e-7
+              const double ex = (double)g.x - x, ey = (double)g.y - y, ez = (double)g.z - z;
+              w = (float)(r2 - (ex * ex + ey * ey + ez * ez)) / (r2f + d2f);                // compute.py:72,85
+            } else {
+              w = weight_from_f32<W>(d2f, r2f, inv_r2q);
+            }
             if constexpr (!VRING) load_packed<STRIDE>(packed, (unsigned)g.index, val);   // one gather per hit
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
