@@ -46,7 +46,7 @@ def gate_validity(gate_z: np.ndarray, radar_altitude: float, toa: float) -> Tupl
 
 def build_geometry(gate_x, gate_y, gate_z, grid_shape, grid_limits, radar_altitude=0.0,
                    min_radius=250.0, beam_factor=0.01746, weighting="barnes2", toa=17000.0,
-                   chunk_pairs: int = 8_000_000):
+                   chunk_pairs: int = 8_000_000, exact_weights: bool = False):
     """Brute-force restatement of ``compute_grid_geometry`` (compute.py:106-284).
 
     Membership is the reference's: gate valid (``z_rel <= toa``) and ``d2 < r2`` with everything in
@@ -57,7 +57,8 @@ def build_geometry(gate_x, gate_y, gate_z, grid_shape, grid_limits, radar_altitu
 
     Rows are returned sorted by ascending gate index (the reference's order is KD-tree traversal order;
     tests canonicalise both before comparing).  Returns ``(indptr int64[V+1], gate_indices int32[P],
-    weights float32[P])``.
+    weights float32[P])``; with ``exact_weights`` the weights are the float64 values before that rounding (the
+    ``w`` of :func:`voxel_stats`).
 
     Intended for small grids / windows: gates are pre-filtered to the grid's bounding box grown by the
     largest ROI, then tested densely in chunks.
@@ -111,19 +112,65 @@ def build_geometry(gate_x, gate_y, gate_z, grid_shape, grid_limits, radar_altitu
             counts[iz * ny * nx + s: iz * ny * nx + e] = np.bincount(rr, minlength=e - s)
             d2h = d2[rr, cc]
             r2h = np.broadcast_to(r2, d2.shape)[rr, cc]
-            if weighting == "barnes2":
-                w = (np.exp(-d2h / (r2h / 4)) + 1e-5).astype("float32")
-            elif weighting == "cressman":
-                w = ((r2h - d2h) / (r2h + d2h)).astype("float32")
-            else:
-                w = np.ones(d2h.shape[0], dtype="float32")
+            w = roi_weight_f64(d2h, r2h, weighting)
+            if not exact_weights:
+                w = w.astype("float32")
             idx_parts.append(cand[cc].astype(np.int32))
             w_parts.append(w)
     indptr = np.zeros(n_vox + 1, dtype=np.int64)
     np.cumsum(counts, out=indptr[1:])
     gate_indices = np.concatenate(idx_parts) if idx_parts else np.zeros(0, dtype=np.int32)
-    weights = np.concatenate(w_parts) if w_parts else np.zeros(0, dtype=np.float32)
+    weights = np.concatenate(w_parts) if w_parts else np.zeros(0, dtype=np.float64 if exact_weights else np.float32)
     return indptr, gate_indices, weights
+
+
+def roi_weight_f64(d2, r2, weighting: str) -> np.ndarray:
+    """compute.py:82-87 in float64, before the rounding to float32: Barnes ``exp(-d2 / (r2 / 4)) + 1e-5``, Cressman
+    ``(r2 - d2) / (r2 + d2)``, nearest 1."""
+    d2 = np.asarray(d2, dtype=np.float64)
+    if weighting == "barnes2":
+        return np.exp(-d2 / (np.asarray(r2, dtype=np.float64) / 4)) + 1e-5
+    if weighting == "cressman":
+        return (r2 - d2) / (r2 + d2)
+    if weighting == "nearest":
+        return np.ones(d2.shape, dtype=np.float64)
+    raise ValueError(f"Unknown weighting function: {weighting}")
+
+
+def pair_geometry(indptr, gate_indices, gate_x, gate_y, gate_z, grid_shape, grid_limits, radar_altitude=0.0,
+                  min_radius=250.0, beam_factor=0.01746):
+    """Per CSR pair, the quantities build_geometry computes: float32 gate coordinates (z relative to the radar, in the
+    gate's dtype as compute.py:182), float32 voxel centres, the float64 ``d2`` and the voxel's float64 ``r2``.  Returns a
+    dict of arrays [P] (``gx gy gz vx vy vz`` float32, ``d2 r2`` float64) -- for recomputing weights from any CSR."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    gate_indices = np.asarray(gate_indices, dtype=np.int64)
+    nz, ny, nx = grid_shape
+    zc = axis_coords_f32(grid_limits[0][0], grid_limits[0][1], nz)
+    yc = axis_coords_f32(grid_limits[1][0], grid_limits[1][1], ny)
+    xc = axis_coords_f32(grid_limits[2][0], grid_limits[2][1], nx)
+    z_rel, _ = gate_validity(np.asarray(gate_z), radar_altitude, 0.0)
+    row = np.repeat(np.arange(nz * ny * nx, dtype=np.int64), np.diff(indptr))
+    iz, rem = np.divmod(row, ny * nx)
+    iy, ix = np.divmod(rem, nx)
+    g = dict(gx=np.asarray(gate_x, dtype=np.float32)[gate_indices], gy=np.asarray(gate_y, dtype=np.float32)[gate_indices],
+             gz=np.asarray(z_rel, dtype=np.float32)[gate_indices], vx=xc[ix], vy=yc[iy], vz=zc[iz])
+    ex = g["gx"].astype(np.float64) - g["vx"]
+    ey = g["gy"].astype(np.float64) - g["vy"]
+    ez = g["gz"].astype(np.float64) - g["vz"]
+    g["d2"] = ex * ex + ey * ey + ez * ez
+    vx, vy, vz = (g[k].astype(np.float64) for k in ("vx", "vy", "vz"))
+    r = np.maximum(min_radius, np.sqrt(vx ** 2 + vy ** 2 + vz ** 2) * beam_factor)
+    g["r2"] = r * r
+    return g
+
+
+def pair_weights_f64(indptr, gate_indices, gate_x, gate_y, gate_z, grid_shape, grid_limits, radar_altitude=0.0,
+                     min_radius=250.0, beam_factor=0.01746, weighting="barnes2") -> np.ndarray:
+    """The float64 weight of every pair of a CSR (any row order), recomputed from the coordinates: what the reference
+    rounds to float32, and the ``w`` of :func:`voxel_stats`."""
+    g = pair_geometry(indptr, gate_indices, gate_x, gate_y, gate_z, grid_shape, grid_limits, radar_altitude, min_radius,
+                      beam_factor)
+    return roi_weight_f64(g["d2"], g["r2"], weighting)
 
 
 def canonical_rows(indptr, gate_indices, weights):
@@ -183,6 +230,102 @@ def csr_apply_f64(indptr, gate_indices, weights, field_values, field_mask, grid_
     ok = den > 0
     out[ok] = (num[ok] / den[ok]).astype(np.float32)
     return out.reshape(grid_shape)
+
+
+# --------------------------------------------------------------------------------------------------
+# per-voxel error bound of a float32 weighted mean, whatever the order of its additions
+# --------------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24                    # unit roundoff of float32 (round to nearest)
+
+# delta: relative error of the float32 weights a gridding path multiplies with, against the float64 weights of
+# compute.py:82-87 (pair_weights_f64).  CSR paths are fed the reference's weights, float32 roundings of those values;
+# K2 (rg_roi_grid_f32) computes its own: the budgets stated in rg_roi_grid.hip.  Uniform weights are exact.
+DELTA_CSR = {"barnes2": U32, "cressman": U32, "nearest": 0.0}
+K2_WEIGHT_BUDGET = {"barnes2": 2e-6, "cressman": 5e-7, "nearest": 0.0}
+DELTA_K2 = {"barnes2": K2_WEIGHT_BUDGET["barnes2"], "cressman": K2_WEIGHT_BUDGET["cressman"] + U32, "nearest": 0.0}
+
+
+def voxel_stats(indptr, gate_indices, weights, field_values, field_mask, n_vox=None) -> dict:
+    """Per voxel, over its unmasked neighbours with float64 weights ``w`` (pair_weights_f64 / build_geometry(...,
+    exact_weights=True); any row order): the exact mean ``m = sum w v / sum w``, ``S = sum w |v| / sum w``,
+    ``D = sum w |v - m| / sum w`` and the live neighbour count ``n``.  ``m`` is NaN where no neighbour is live (the
+    gridders' fill) and where a live value is NaN / inf (it poisons the float32 sums as well).  float64 [V] arrays."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    n_vox = indptr.shape[0] - 1 if n_vox is None else int(n_vox)
+    gi = np.asarray(gate_indices, dtype=np.int64)
+    live = ~np.asarray(field_mask, dtype=bool)[gi]
+    row = np.repeat(np.arange(n_vox, dtype=np.int64), np.diff(indptr))[live]
+    w = np.asarray(weights, dtype=np.float64)[live]
+    v = np.asarray(field_values, dtype=np.float32)[gi[live]].astype(np.float64)
+    n = np.bincount(row, minlength=n_vox)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        W = np.bincount(row, weights=w, minlength=n_vox)
+        m = np.bincount(row, weights=w * v, minlength=n_vox) / W
+        S = np.bincount(row, weights=w * np.abs(v), minlength=n_vox) / W
+        D = np.bincount(row, weights=w * np.abs(v - m[row]), minlength=n_vox) / W
+    m[~(W > 0)] = np.nan
+    return dict(m=m, S=S, D=D, n=n)
+
+
+def gamma(k) -> np.ndarray:
+    """gamma_k = k u / (1 - k u), u = 2^-24 (Higham's constant for k float32 roundings)."""
+    ku = np.asarray(k, dtype=np.float64) * U32
+    return ku / (1.0 - ku)
+
+
+def mean_error_bound(stats: dict, delta: float) -> np.ndarray:
+    """Largest |got - m| of a float32 gridder for each voxel of ``stats`` (voxel_stats), ``delta`` the relative error
+    of the path's weights (DELTA_CSR / DELTA_K2):
+
+        |got - m| <= gamma_{n+1} (S + |m|) + 2u |m| + delta D (1 + 2 delta)
+
+    Model: weights ``w'_i = w_i (1 + e_i)``, |e_i| <= delta; one float32 product ``w'_i v_i`` per live pair; the products
+    and the weights summed in float32 in ANY order and tree shape (masked pairs add exact zeros, which round nothing); the
+    quotient of the two sums formed in float32, or in float64 and rounded once to float32.
+
+    Derivation.  A leaf of an n-leaf addition tree passes through at most n - 1 roundings, so (Higham, Lemma 3.1)
+        N' = sum w'_i v_i (1 + f_i),  |f_i| <= gamma_n     (the product's rounding and n - 1 additions)
+        W' = sum w'_i (1 + g_i),      |g_i| <= gamma_{n-1}.
+    With W = sum w_i and sum w_i (v_i - m) = 0:
+        N' - m W' = sum w_i (v_i - m) e_i + sum w'_i v_i f_i - m sum w'_i g_i,
+        |N' - m W'| <= W [delta D + (1 + delta) (gamma_n S + gamma_{n-1} |m|)]   and   W' >= W (1 - delta)(1 - gamma_{n-1}),
+    so q = N' / W' satisfies |q - m| <= E = [delta D + (1 + delta)(gamma_n S + gamma_{n-1} |m|)] / ((1 - delta)(1 - gamma_{n-1})).
+    The division and the rounding to float32 add at most u' |q| <= u' (|m| + E), u' = u (1 + 2^-28) (a float64 quotient
+    rounded to float32), hence
+        |got - m| <= E (1 + u') + u' |m|.                                                                    (*)
+    To first order (*) is gamma_n S + (gamma_{n-1} + u) |m| + delta D; the stated form adds u (S + |m|) + u |m| + 2 delta^2 D,
+    which covers the second-order terms (delta + gamma_{n-1} + u')(gamma_n S + delta D + gamma_{n-1} |m|) while
+    n (3 delta + 2 n u) <= 1 -- every voxel of this project's grids but rows of thousands of neighbours at the radar.  The
+    function returns the larger of the stated form and (*), so it holds for every n.
+
+    ``m`` is the mean with exact weights: the bound does not depend on the add order, so it holds for every path alike and
+    for the reference's own float32 grids (DELTA_CSR).  Where ``m`` is NaN the bound is NaN: NaN patterns are compared
+    exactly instead (bound_ratio)."""
+    m = np.abs(np.asarray(stats["m"], dtype=np.float64))
+    S = np.asarray(stats["S"], dtype=np.float64)
+    D = np.asarray(stats["D"], dtype=np.float64)
+    n = np.asarray(stats["n"], dtype=np.float64)
+    d = float(delta)
+    stated = gamma(n + 1) * (S + m) + 2 * U32 * m + d * D * (1 + 2 * d)
+    g0 = gamma(np.maximum(n - 1, 0))
+    u1 = U32 * (1 + 2.0 ** -28)
+    e = (d * D + (1 + d) * (gamma(n) * S + g0 * m)) / ((1 - d) * (1 - g0))
+    return np.maximum(stated, e * (1 + u1) + u1 * m)
+
+
+def bound_ratio(got, stats: dict, delta: float) -> np.ndarray:
+    """|got - m| / mean_error_bound per voxel (flattened): 0 where ``got`` equals ``m`` or both are NaN, +inf where
+    exactly one of them is NaN -- NaN patterns must match exactly, so a voxel filled by one side only fails any bar."""
+    got = np.asarray(got, dtype=np.float32).ravel()
+    m = np.asarray(stats["m"], dtype=np.float64).ravel()
+    out = np.where(np.isnan(got) != np.isnan(m), np.inf, 0.0)
+    fin = ~np.isnan(m) & ~np.isnan(got)
+    b = mean_error_bound({k: np.asarray(v).ravel()[fin] for k, v in stats.items()}, delta)
+    err = np.abs(got[fin].astype(np.float64) - m[fin])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out[fin] = np.where(err == 0, 0.0, err / b)
+    return out
+
 
 ROWWISE_TARGET = {1: 4, 2: 4, 3: 6, 4: 8, 5: 8, 6: 8, 7: 8, 8: 12}   # records per lane and row the row-wise kernel aims for
 ROWWISE_KPRE = {n: 3 for n in range(1, 9)}  # records per lane and step (batch slots), by field count

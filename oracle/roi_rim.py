@@ -339,3 +339,31 @@ def relabel(cloud: RimCloud, grid_shape, grid_limits, min_radius: float, beam_fa
         rim = voxel_rim(xc[ix], yc[iy], zc[iz], min_radius, beam_factor)
         out[i] = classify(cloud.gx[i:i + 1], cloud.gy[i:i + 1], cloud.gz[i:i + 1], rim)[0]
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# the CSR-free gridder's float32 weights (grid mode of roi_block_kernel), emulated per pair
+# --------------------------------------------------------------------------------------------------
+def k2_weights_f32(pairs: dict, weighting: str, cressman_numerator: str = "f64") -> np.ndarray:
+    """The float32 weight grid mode multiplies with, for every pair of ``pairs`` (radar_grid_oracle.pair_geometry):
+
+    * barnes2: ``exp2f(d2f * inv_r2q) + 1e-5f`` with ``inv_r2q = (float)(-log2(e) * 4 / r2)``, d2f as :func:`d2f_kernel`
+      and exp2 rounded correctly (the hardware's v_exp_f32 may differ by an ulp);
+    * cressman: ``(float)(r2 - d2) / (r2f + d2f)``, numerator from the float64 d2; ``cressman_numerator='f32'`` gives the
+      all-float32 ``(r2f - d2f) / (r2f + d2f)`` the kernel used before, whose numerator cancels at the rim;
+    * nearest: 1."""
+    n = pairs["d2"].shape[0]
+    if weighting == "nearest":
+        return np.ones(n, dtype=np.float32)
+    d2f = d2f_kernel(pairs["gx"], pairs["gy"], pairs["gz"], pairs["vx"], pairs["vy"], pairs["vz"])
+    r2 = pairs["r2"]
+    r2f = r2.astype(np.float32)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        if weighting == "barnes2":
+            inv_r2q = (-1.4426950408889634 * 4.0 / r2).astype(np.float32)
+            t = (d2f * inv_r2q).astype(np.float32)
+            return (np.exp2(t.astype(np.float64)).astype(np.float32) + _F32(1e-5)).astype(np.float32)
+        if weighting == "cressman":
+            num = (r2 - pairs["d2"]).astype(np.float32) if cressman_numerator == "f64" else (r2f - d2f).astype(np.float32)
+            return (num / (r2f + d2f).astype(np.float32)).astype(np.float32)
+    raise ValueError(weighting)

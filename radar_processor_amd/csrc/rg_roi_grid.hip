@@ -20,9 +20,12 @@
 //     constants live in its registers, its sums never leave it -- and tests 4 records per step (LDS broadcast
 //     reads).  float32 d2 decides membership whenever it is clear of the rim by 2e-6; inside that band the lane
 //     falls back to the reference's exact float64 `d2 < r2` (compute.py:69-74), so the neighbour set equals the
-//     CSR builder's.  Barnes and uniform weights in float32 (|rel err| < 2e-6); the Cressman numerator r2 - d2
-//     from the float64 d2 (from the float32 d2 it cancels at the rim: a hit there could weigh 0 or less), its
-//     denominator in float32 (|rel err| < 5e-7).  The packed field slots of a gate are fetched once,
+//     CSR builder's.  Barnes and uniform weights in float32 (Barnes |rel err| < 2e-6 against compute.py's float64
+//     weight, uniform exact); the Cressman numerator r2 - d2 from the float64 d2 (from the float32 d2 it cancels at
+//     the rim: a hit there could weigh 0 or less), its denominator in float32 (|rel err| < 5e-7).  These budgets are
+//     the delta of the per-voxel error bound (oracle.mean_error_bound) every grid of this kernel is tested against, and
+//     are observed directly by tests/test_gpu_mean_bounds.py's two-gate probes (worst measured: Barnes 5.1e-7,
+//     Cressman 1.6e-7, uniform 0).  The packed field slots of a gate are fetched once,
 //     when the gate is queued, and parked in a second LDS ring one candidate step later; the dense stage reads
 //     records and values from LDS one step ahead of its arithmetic;
 //   * per block two wavefront shuffles fold the 4 record slots; 16 lanes store 16 consecutive voxels per field.
@@ -51,7 +54,8 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 
 
 // float32 weight from the float32 d2 (compute.py:82-87): Barnes (>= e^-4 inside the ROI) and uniform; relative error
-// < 2e-6.  Not Cressman, whose numerator r2 - d2 cancels near the rim (grid mode takes it from the float64 d2).
+// < 2e-6 (d2f and inv_r2q carry a few u each; 2^x turns the exponent's absolute error, up to 5.8 * 6u, into a relative
+// one of ln 2 times that).  Not Cressman, whose numerator r2 - d2 cancels near the rim (grid mode takes it from the float64 d2).
 // inv_r2q: Barnes -- MINUS log2(e) * 4 / r2, so that exp(-d2 / (r2 / 4)) is one multiply and one v_exp_f32 (= 2^x)
 template <int W>
 __device__ __forceinline__ float weight_from_f32(float d2f, float r2f, float inv_r2q) {

@@ -83,10 +83,45 @@ def test_c2_fused_gridder_equals_csr_path(c2):
         scale = float(torch.nan_to_num(f[i], nan=0.0).abs().max())
         d = torch.nan_to_num(k1[i] - k2[i], nan=0.0).abs().max()
         assert float(d) <= 1e-5 * scale, n
+    # and on every voxel within oracle.mean_error_bound of the float64 mean over the CSR's weights (float32 roundings of
+    # the exact ones: K2's delta is its budget plus u)
+    worst = _c2_k2_within_the_bound(c2, k2, f, m, qc)
+    print("c2 K2 worst err/bound", worst)
     # masking more gates can only remove voxels, never add them
     plain = rg.grid_fields_device(geom, f[:1], m[:1])
     assert bool((torch.isfinite(k1[0]) <= torch.isfinite(plain[0])).all())
     assert int(torch.isfinite(k1[0]).sum()) < int(torch.isfinite(plain[0]).sum())
+
+
+def _c2_k2_within_the_bound(c2, k2, fields, masks, shared):
+    """Per level, in torch float64 on the device: m, S, D, n of every voxel from geom.device_csr with the CSR's float32
+    weights widened, then oracle.bound_ratio on the host.  Returns the worst err / bound per field."""
+    torch, geom, dev = c2["torch"], c2["geom"], c2["dev"]
+    csr = geom.device_csr(dev)
+    nz, ny, nx = c2["cfg"]["grid_shape"]
+    per = ny * nx
+    ip = csr.indptr.to(torch.int64)
+    delta = oracle.DELTA_K2["barnes2"] + oracle.U32
+    worst = [0.0] * len(fields)
+    for iz in range(nz):
+        p0, p1 = int(ip[iz * per]), int(ip[(iz + 1) * per])
+        row = torch.repeat_interleave(torch.arange(per, device=dev), ip[iz * per + 1:(iz + 1) * per + 1] - ip[iz * per:(iz + 1) * per])
+        gi = csr.gate_indices[p0:p1].long()
+        w_all = csr.weights[p0:p1].double()
+        for i, (f, msk) in enumerate(zip(fields, masks)):
+            live = (msk[gi] == 0) & (shared[gi] == 0)
+            r, w, v = row[live], w_all[live], f[gi[live]].double()
+            acc = lambda x: torch.zeros(per, dtype=torch.float64, device=dev).index_add_(0, r, x)
+            W = acc(w)
+            mean = acc(w * v) / W
+            st = dict(m=mean, S=acc(w * v.abs()) / W, D=acc(w * (v - mean[r]).abs()) / W,
+                      n=torch.zeros(per, dtype=torch.int64, device=dev).index_add_(0, r, torch.ones_like(r)))
+            st["m"] = torch.where(W > 0, st["m"], torch.full_like(W, float("nan")))
+            st = {k: t.cpu().numpy() for k, t in st.items()}
+            ratio = oracle.bound_ratio(k2[i, iz].cpu().numpy(), st, delta)
+            worst[i] = max(worst[i], float(ratio.max(initial=0)))
+            assert worst[i] <= 1.0, (i, iz, worst[i], int((ratio > 1).sum()))
+    return worst
 
 
 def test_c2_products_consistency_and_oracle_rows(c2):
@@ -728,6 +763,23 @@ def test_metric_fused_gridder_and_products(metric):
     assert bool((torch.isnan(grid) == torch.isnan(k2)).all())
     scale = float(torch.nan_to_num(metric["f"], nan=0.0).abs().max())
     assert float(torch.nan_to_num(grid - k2, nan=0.0).abs().max()) <= 1e-5 * scale
+    # whole y-rows, every voxel within oracle.mean_error_bound of the float64 mean over the CSR's weights widened (float32
+    # roundings of the exact ones: K2's delta is its budget plus u); rows past 2^31 pairs and the last row included
+    csr = geom.device_csr(dev)
+    data = metric["f"].cpu().numpy()
+    excl = metric["m"].cpu().numpy().astype(bool)
+    ip_rows = csr.indptr[::nx].cpu().numpy()
+    worst = 0.0
+    for r in (0, nz * ny // 2 + 7, int(np.searchsorted(ip_rows, 2 ** 31)), 37 * ny + 1500, nz * ny - 1):
+        v0 = r * nx
+        ip = csr.indptr[v0:v0 + nx + 1].cpu().numpy().astype(np.int64)
+        idx = csr.gate_indices[int(ip[0]):int(ip[-1])].cpu().numpy()
+        w = csr.weights[int(ip[0]):int(ip[-1])].cpu().numpy().astype(np.float64)
+        st = oracle.voxel_stats(ip - ip[0], idx, w, data, excl)
+        ratio = oracle.bound_ratio(k2.view(-1)[v0:v0 + nx].cpu().numpy(), st, oracle.DELTA_K2["barnes2"] + oracle.U32)
+        worst = max(worst, float(ratio.max(initial=0)))
+        assert worst <= 1.0, (r, worst)
+    print("metric K2 rows, worst err/bound", worst)
     del k2
     grid = grid[0]
     cmax, arg = rg.column_argmax(grid)

@@ -91,6 +91,23 @@ def test_c4_rowwise_grid_equals_csr_free_gridder_on_every_voxel(c4):
     scale = float(f[torch.isfinite(f) & (c4["m"] == 0)].abs().max())
     worst = float(torch.nan_to_num(grid - k2, nan=0.0).abs().max())
     assert worst <= 1e-5 * scale, worst
+    # whole y-rows, every voxel within oracle.mean_error_bound of the float64 mean over the decoded weights widened (each
+    # within one ulp of the oracle's float32 weight, test_c4_decode_against_the_brute_force_builder: delta = K2's budget + 3u)
+    csr, compact = c4["geom"].device_csr(dev), c4["geom"].device_compact(dev)
+    nz, ny, nx = cfg["grid_shape"]
+    data = f.cpu().numpy()
+    excl = c4["m"].cpu().numpy().astype(bool)
+    bound_worst = 0.0
+    for iz, iy in ((0, 3), (nz // 2, ny // 2), (8, 1710), (20, 1000), (nz - 1, ny - 5)):
+        v0 = (iz * ny + iy) * nx
+        ip = csr.indptr[v0:v0 + nx + 1].cpu().numpy().astype(np.int64)
+        idx = compact.decode(csr, v0, v0 + nx).cpu().numpy()
+        w = compact.decode_weights(csr, v0, v0 + nx).cpu().numpy().astype(np.float64)
+        st = oracle.voxel_stats(ip - ip[0], idx, w, data, excl)
+        ratio = oracle.bound_ratio(k2.view(-1)[v0:v0 + nx].cpu().numpy(), st, oracle.DELTA_K2["barnes2"] + 3 * oracle.U32)
+        bound_worst = max(bound_worst, float(ratio.max(initial=0)))
+        assert bound_worst <= 1.0, (iz, iy, bound_worst)
+    print("C4 K2 rows, worst err/bound", bound_worst)
     assert 0.6 < float(torch.isfinite(grid).float().mean()) < 0.9
     again = rg.grid_fields_device(c4["geom"], [c4["f"]], [c4["m"]])[0]         # a fixed order: the same bits run to run
     assert bool(torch.equal(again.view(torch.int32), grid.view(torch.int32)))

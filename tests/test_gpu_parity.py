@@ -269,10 +269,64 @@ def test_reference_grid_relative_error(rg):
         report[kernel] = dict(per_field=worst, total=total)
         # the floor is a rarity, not a crutch: at most one filled voxel in a thousand needs it
         assert total["needed_floor"] <= 1e-3 * total["voxels"], (kernel, total)
+    report["k2"] = _k2_relative_error(rg, dev)                  # K2 computes its own weights: its bars are its own
     os.makedirs("gpurun_out", exist_ok=True)
     with open(os.path.join("gpurun_out", "parity_relerr.json"), "w") as fh:
         json.dump(report, fh, indent=1)
     print("parity_relerr", json.dumps(report))
+
+
+def _k2_relative_error(rg, dev):
+    """K2 (rg_roi_grid_f32) on the fixtures of test_reference_grid_relative_error.  Its float32 weights carry up to the
+    budget rg_roi_grid.hip states (oracle.K2_WEIGHT_BUDGET), so "significant" voxels whose mean cancels (S / |m| in the
+    hundreds) may leave 1e-5 on the data alone; the bars are instead: every voxel within oracle.mean_error_bound of the
+    float64 mean (delta = oracle.DELTA_K2), and a purely relative error <= 1e-5 against the reference's grid, with no
+    floor, wherever the voxel is well conditioned (S <= 10 |m|, S = sum w|v| / sum w).  Returns the report entry."""
+    import torch
+    worst = {}
+    total = dict(voxels=0, conditioned=0, needed_floor=0, max_err_over_bound=0.0)
+    for name in golden_names("g2_") + golden_names("g3_") + golden_names("g6_"):
+        meta, ref = load_golden(name)
+        vol = volume_for(meta)
+        shape, limits = grid_spec(meta)
+        kw = builder_kwargs(meta)
+        weighting = kw.pop("weighting")
+        idx = reference_indices(name, meta, ref)
+        w64 = oracle.pair_weights_f64(ref["indptr"], idx, vol.gate_x, vol.gate_y, vol.gate_z, shape, limits,
+                                      radar_altitude=kw["radar_altitude"], min_radius=kw["min_radius"],
+                                      beam_factor=kw["beam_factor"], weighting=weighting)
+        search = rg.RoiSearch(vol.gate_x, vol.gate_y, vol.gate_z, shape, limits, device=dev, **kw)
+        for fname in meta["fields"]:
+            data, mask = oracle.merge_masks(vol.fields[fname])
+            scale = _atol(data, mask) / ATOL_FRAC
+            f_t = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+            m_t = torch.from_numpy(mask.astype(np.uint8)).to(dev)
+            got = rg.roi_grid_fields_device(search, [f_t], [m_t], weighting=weighting)[0].cpu().numpy().ravel()
+            want = ref[f"grid_{fname}"].ravel()
+            filled = np.isfinite(want)
+            np.testing.assert_array_equal(np.isfinite(got), filled)
+            st = oracle.voxel_stats(ref["indptr"], idx, w64, data, mask)
+            ratio = oracle.bound_ratio(got, st, oracle.DELTA_K2[weighting])
+            assert ratio.max(initial=0) <= 1.0, (name, fname, float(ratio.max()))
+            err = np.abs(got[filled].astype(np.float64) - want[filled].astype(np.float64))
+            mag = np.abs(want[filled].astype(np.float64))
+            cond = st["S"][filled] <= 10.0 * np.abs(st["m"][filled])
+            sig = mag > 1e-3 * scale
+            rel = float((err[cond] / mag[cond]).max()) if cond.any() else 0.0
+            needed = int((err > RTOL * mag).sum())
+            rec = worst.setdefault(fname, dict(max_rel_conditioned=0.0, max_rel_significant=0.0, needed_floor=0, voxels=0,
+                                               max_err_over_bound=0.0))
+            rec["max_rel_conditioned"] = max(rec["max_rel_conditioned"], rel)
+            rec["max_rel_significant"] = max(rec["max_rel_significant"],
+                                             float((err[sig] / mag[sig]).max()) if sig.any() else 0.0)   # reported only
+            rec["needed_floor"] += needed
+            rec["voxels"] += int(filled.sum())
+            rec["max_err_over_bound"] = max(rec["max_err_over_bound"], float(ratio.max(initial=0)))
+            total["voxels"] += int(filled.sum()); total["conditioned"] += int(cond.sum()); total["needed_floor"] += needed
+            total["max_err_over_bound"] = max(total["max_err_over_bound"], rec["max_err_over_bound"])
+            assert rel <= RTOL, ("k2", name, fname, rel)          # no absolute floor on well-conditioned voxels
+    assert total["conditioned"] >= 0.9 * total["voxels"], total
+    return dict(per_field=worst, total=total)
 
 
 @pytest.mark.parametrize("n_fields", [1, 2, 3, 4, 5, 8, 11])
