@@ -126,8 +126,7 @@ int rg_csr_apply_f32(const void* indptr, int32_t indptr_is_i64, const int32_t* g
                      float fill_value, float* out, rg_stream_t stream);
 /* same kernel with the pipeline tile selected explicitly: variant = 0 (what rg_csr_apply_f32 runs) or 128, 192, 256, 320,
  * 384, 512 pairs per step (right answers, another order of the float32 adds; used by the bit-identity tests of the compact
- * kernels).  Anything else is RG_EINVAL in the product library; the tuning / timing-only variants of earlier rounds exist
- * only in -DRG_EXPERIMENTS builds (tools/build_experiments.py). */
+ * kernels).  Anything else is RG_EINVAL. */
 int rg_csr_apply_f32_ex(const void* indptr, int32_t indptr_is_i64, const int32_t* gate_idx, const float* weights,
                         int64_t n_vox, int64_t n_pairs, int64_t line_len,
                         const float* packed, int32_t n_fields, int32_t stride, int64_t n_gates,
@@ -343,9 +342,8 @@ int rg_grid_filter(const void* src, int32_t data_is_f64, int64_t n, int32_t flag
  * window_cap: how many dictionary entries (of `stride` floats) a workgroup keeps in LDS (<= RG_COMPACT_MAX_WINDOW,
  * clamped to what fits next to the kernel's own LDS); chunks with a longer dictionary gather per pair from memory, so
  * any value is correct and the choice only affects speed.  tile: pairs per pipeline step, 0 = default (= the tile of
- * rg_csr_apply_f32 for the same field count; other values change the order of the float32 adds).  Timing-only
- * ablations (901-909, results wrong by construction) and the block-rotation override exist only in -DRG_EXPERIMENTS builds
- * (tools/build_experiments.py); the product library answers RG_EINVAL.
+ * rg_csr_apply_f32 for the same field count; other values change the order of the float32 adds); any other tile is
+ * RG_EINVAL.
  * line_len <= 0 means one line of n_vox rows, lines_per_plane <= 0 one plane.
  * ------------------------------------------------------------------------------------------------- */
 #ifndef RG_COMPACT_LINES
@@ -393,12 +391,10 @@ int rg_csr_compact_apply_f32(const void* indptr, int32_t indptr_is_i64, const ui
  *               against 2 x 10.5 for two passes of four) keep 40 bytes of LDS per window entry: worth it where the
  *               geometry's window is <= 768 entries (the Python layer decides: gridding.fields_per_pass).
  *   tile = 384  the TILE kernel of rg_csr_compact_apply_f32 over the same records: the results of rg_csr_apply_f32 for the
- *               same fields, bit for bit (576 / 768: single-field tuning variants of it).
+ *               same fields, bit for bit.
  *   tile = 2000 + h   row-wise with a diagnostic lane split: h = 1, 2, 4 .. 64 lanes per row, or h = 71 .. 99 = 70 + t to
  *               aim for t records per lane and row (another split = another order of the adds; right answers).
- *   tile = 2100 .. 2199 (timing-only ablations: no store, no record loads ... -- WRONG results by construction) and
- *   2201 .. 2264 (several chunks per workgroup) are compiled only into -DRG_EXPERIMENTS builds (tools/build_experiments.py);
- *   the product library answers RG_EINVAL.
+ *   Any other tile is RG_EINVAL.
  * window_cap as for rg_csr_compact_apply_f32; the row-wise kernel keeps one entry more (an all-EXCLUDED sentinel). */
 #define RG_REC_ORDER_SEGMENT 0
 #define RG_REC_ORDER_DISPATCH 1

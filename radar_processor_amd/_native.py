@@ -12,9 +12,9 @@ import threading
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_void_p)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# The product loads the in-tree library and nothing else: no environment override.  Measurement scripts that want an
-# experiment build (tools/build_experiments.py) assign ``_native.LIB_PATH`` themselves before the first load; the ABI
-# check below applies to them as well.
+# The product loads the in-tree library and nothing else: no environment override.  Measurement scripts that want
+# another build of the library (tools/exp_rowwise.py --libs) assign ``_native.LIB_PATH`` themselves before the first
+# load; the ABI check below applies to them as well.
 LIB_PATH = os.path.join(HERE, "csrc", "libradargrid_hip.so")
 ABI_VERSION = 104          # include/radargrid_hip.h: RG_VERSION -- load_library refuses a library built from another header
 

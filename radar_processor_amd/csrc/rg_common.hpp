@@ -25,17 +25,6 @@ inline int check_launch(const char* what) {
 
 constexpr int kWave = 64;        // CDNA4 wavefront
 constexpr int kBlock = 256;      // 4 waves per workgroup
-constexpr int kNumXcd = 8;       // MI355X: 8 XCDs, workgroups dealt round-robin
-
-// Bijective XCD-aware remap (cdna_hip_programming.md T1): workgroups b and b+8 share an XCD, so give
-// every XCD one contiguous slab of the logical index space -> neighbouring voxel chunks (which gather the
-// same gates) hit the same 4 MiB L2.
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
-  const unsigned q = nblk / kNumXcd, r = nblk % kNumXcd;
-  const unsigned xcd = bid % kNumXcd, k = bid / kNumXcd;
-  const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + k;
-}
 
 __device__ __forceinline__ uint32_t f32_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
 __device__ __forceinline__ float bits_f32(uint32_t v) { return __builtin_bit_cast(float, v); }

@@ -15,9 +15,6 @@ using rg_u32x4 = unsigned __attribute__((ext_vector_type(4)));
 __device__ rg_u32x4 rg_buffer_load_v4u32(__amdgpu_buffer_rsrc_t, int voffset, int soffset, int aux)
     __asm("llvm.amdgcn.raw.ptr.buffer.load.v4i32");
 
-__device__ unsigned rg_buffer_load_u32(__amdgpu_buffer_rsrc_t, int voffset, int soffset, int aux)
-    __asm("llvm.amdgcn.raw.ptr.buffer.load.i32");
-
 // v_mul_legacy_f32 by intrinsic name (this clang has no __builtin_amdgcn_fmul_legacy): 0 * x = +0 for EVERY x, NaN and
 // infinity included; any other product is the IEEE one.
 __device__ float rg_fmul_legacy(float, float) __asm("llvm.amdgcn.fmul.legacy");
@@ -150,45 +147,15 @@ bool make_chunk_grid(int64_t n_rows, int64_t line_len, int64_t lines_per_plane, 
 
 // ---- per-field-count configuration of the row-wise kernels (see rg_csr_compact.hip for what the knobs mean) ----
 template <int NF> struct RowwiseConfig;
-template <> struct RowwiseConfig<1> { static constexpr int kpre = 3, target = 4; static constexpr bool narrow = false, regs = false; };
-template <> struct RowwiseConfig<2> { static constexpr int kpre = 3, target = 4; static constexpr bool narrow = false, regs = false; };
-// Tuning knobs of three fields: fixed in the product library; -DRG_EXPERIMENTS builds (tools/build_experiments.py) may
-// override them with -DRG_ROWWISE_KPRE3=.. etc. for A/B measurements.
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_KPRE3)
-#undef RG_ROWWISE_KPRE3
-#define RG_ROWWISE_KPRE3 3
-#endif
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_TARGET3)
-#undef RG_ROWWISE_TARGET3
-#define RG_ROWWISE_TARGET3 6
-#endif
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_REGS3)
-#undef RG_ROWWISE_REGS3
-#define RG_ROWWISE_REGS3 true
-#endif
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_NARROW3)
-#undef RG_ROWWISE_NARROW3
-#define RG_ROWWISE_NARROW3 true
-#endif
-template <> struct RowwiseConfig<3> { static constexpr int kpre = RG_ROWWISE_KPRE3, target = RG_ROWWISE_TARGET3; static constexpr bool narrow = RG_ROWWISE_NARROW3, regs = RG_ROWWISE_REGS3; };
-template <> struct RowwiseConfig<4> { static constexpr int kpre = 3, target = 8; static constexpr bool narrow = false, regs = true; };
+template <> struct RowwiseConfig<1> { static constexpr int kpre = 3, target = 4; static constexpr bool regs = false; };
+template <> struct RowwiseConfig<2> { static constexpr int kpre = 3, target = 4; static constexpr bool regs = false; };
+template <> struct RowwiseConfig<3> { static constexpr int kpre = 3, target = 6; static constexpr bool regs = true; };
+template <> struct RowwiseConfig<4> { static constexpr int kpre = 3, target = 8; static constexpr bool regs = true; };
 // Five to eight fields (one pass over the records for up to eight volumes of the same geometry: batch.VolumeBatch)
-template <> struct RowwiseConfig<5> { static constexpr int kpre = 3, target = 8; static constexpr bool narrow = false, regs = true; };
-template <> struct RowwiseConfig<6> { static constexpr int kpre = 3, target = 8; static constexpr bool narrow = false, regs = true; };
-template <> struct RowwiseConfig<7> { static constexpr int kpre = 3, target = 8; static constexpr bool narrow = false, regs = true; };
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_KPRE8)
-#undef RG_ROWWISE_KPRE8
-#define RG_ROWWISE_KPRE8 3
-#endif
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_TARGET8)
-#undef RG_ROWWISE_TARGET8
-#define RG_ROWWISE_TARGET8 12
-#endif
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_REGS8)
-#undef RG_ROWWISE_REGS8
-#define RG_ROWWISE_REGS8 true
-#endif
-template <> struct RowwiseConfig<8> { static constexpr int kpre = RG_ROWWISE_KPRE8, target = RG_ROWWISE_TARGET8; static constexpr bool narrow = false, regs = RG_ROWWISE_REGS8; };
+template <> struct RowwiseConfig<5> { static constexpr int kpre = 3, target = 8; static constexpr bool regs = true; };
+template <> struct RowwiseConfig<6> { static constexpr int kpre = 3, target = 8; static constexpr bool regs = true; };
+template <> struct RowwiseConfig<7> { static constexpr int kpre = 3, target = 8; static constexpr bool regs = true; };
+template <> struct RowwiseConfig<8> { static constexpr int kpre = 3, target = 12; static constexpr bool regs = true; };
 
 // Byte-mask window entries: the window holds v' = the value, or +0 where the gate is excluded, and one BYTE per field that is
 // 1 / 0 = usable / excluded.  A pair then costs, per field, half a packed multiply and half a packed add (sum w*v': w * +0 = +0,
@@ -199,16 +166,10 @@ template <> struct RowwiseConfig<8> { static constexpr int kpre = RG_ROWWISE_KPR
 // Measured with the pairs of a record taken one at a time (the asm fences of the kernel; without them the wider entries
 // cost a wavefront per SIMD and the gain): three / four fields -4 ... -5 % on the bench grid, -1 ... -4 % on config 2
 // (19 % fewer VALU instructions: profiles/r04_bytemask_*.json); five fields and more have no other form.
-// RG_ROWWISE_BYTEMASK = the smallest field count that uses it (experiment builds: 5 = the select + legacy-multiply form
-// for three and four fields).
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_BYTEMASK)
-#undef RG_ROWWISE_BYTEMASK
-#define RG_ROWWISE_BYTEMASK 3
-#endif
-template <int NF> constexpr bool rowwise_bytemask() { return NF >= 5 || (NF >= 3 && NF >= RG_ROWWISE_BYTEMASK); }
+template <int NF> constexpr bool rowwise_bytemask() { return NF >= 3; }
 // 4-byte words of LDS per window entry of the row-wise kernel: values, then masks
 template <int NF> constexpr int rowwise_value_words() {
-  return rowwise_bytemask<NF>() ? (NF <= 4 ? 4 : 8) : RowwiseConfig<NF>::narrow ? 3 : NF <= 2 ? 2 : 4;
+  return rowwise_bytemask<NF>() ? (NF <= 4 ? 4 : 8) : 2;     // one field: (v', m); two fields: the two values
 }
 template <int NF> constexpr int rowwise_mask_words() { return !rowwise_bytemask<NF>() || NF == 3 ? 0 : NF == 4 ? 1 : 2; }
 template <int NF> constexpr int rowwise_entry_words() { return rowwise_value_words<NF>() + rowwise_mask_words<NF>(); }

@@ -41,36 +41,10 @@ namespace {
 
 using rg::load_packed;
 
-// XCD placement of the 64-row chunks (speed only, never correctness):
-//   kXcdNone   workgroup b -> logical block b: neighbouring blocks land on different XCDs (round-robin deal),
-//              perfectly balanced when pair density varies with height, every L2 sees the same gate window;
-//   kXcdGroup  groups of 32 consecutive logical blocks stay on one XCD, groups rotate over the XCDs;
-//   kXcdSlab   one contiguous eighth of the grid per XCD (best L2 locality, worst balance: top levels are
-//              sparse, so the XCDs that own them idle -- measured 30 % slower on the bench grid).
-constexpr int kXcdNone = 0, kXcdGroup = 1, kXcdSlab = 2;
-
-template <int MODE>
-__device__ __forceinline__ unsigned place_block(unsigned bid, unsigned nblk) {
-  if constexpr (MODE == kXcdSlab) {
-    return rg::xcd_remap(bid, nblk);
-  } else if constexpr (MODE == kXcdGroup) {
-    constexpr unsigned S = 32;
-    const unsigned super = S * rg::kNumXcd;
-    const unsigned full = nblk / super * super;  // only whole super-groups are permuted (bijective)
-    if (bid >= full) return bid;
-    const unsigned base = bid / super * super, r = bid % super;
-    return base + (r % rg::kNumXcd) * S + r / rg::kNumXcd;
-  } else {
-    return bid;
-  }
-}
-
-// tuning / diagnostic flags (template parameter FLAGS)
-constexpr int kNoGather = 1;     // timing-only ablation: skip the gather (results are wrong by construction)
-[[maybe_unused]] constexpr int kWpb1 = 256, kWpb2 = 512, kWpb8 = 768;  // dyn kernel only: waves per workgroup (default 4)
-constexpr int kStages3 = 1024;   // dyn kernel only: three CSR tiles in flight per wavefront instead of two
-constexpr int wpb_of(int flags) { return (flags & 768) == 256 ? 1 : (flags & 768) == 512 ? 2 : (flags & 768) == 768 ? 8 : 4; }
-
+// Measured and rejected (single field, bench grid; EXPERIMENTS.md, K1 table): one contiguous eighth of the grid per XCD
+// (+30 %: the XCDs that own the sparse top levels idle); groups of 32 blocks per XCD, 1 / 2 / 8 wavefronts per workgroup
+// instead of 4, a third CSR tile in flight, tiles of 256-640 pairs (all within 2 %).  What ships: round-robin XCDs (with
+// the segment rotation below), 4 wavefronts, two stages, 384-pair tiles (72 VGPRs).
 using f32x2 = float __attribute__((ext_vector_type(2)));
 
 // The kernel: the phases above, with
@@ -114,16 +88,16 @@ __device__ __forceinline__ void buffer_load_packed(rsrc_t r, unsigned gate, floa
   }
 }
 
-template <typename IndT, int NF, int STRIDE, int TILE, int XCD, int FLAGS>
-__global__ __launch_bounds__(64 * wpb_of(FLAGS)) void csr_apply_dyn_kernel(
+template <typename IndT, int NF, int STRIDE, int TILE>
+__global__ __launch_bounds__(64 * 4) void csr_apply_dyn_kernel(
     const IndT* __restrict__ indptr, const int32_t* __restrict__ gidx, const float* __restrict__ wts,
     long n_vox, long line_len, unsigned segs_per_line, unsigned n_segs, unsigned rot_step,
     const float* __restrict__ packed, unsigned last_gate, float fill, float* __restrict__ out) {
   static_assert(TILE % 64 == 0, "a wave handles 64 pairs per step");
   constexpr int IT = TILE / 64;
   static_assert(IT * 256 <= 4096, "the tile's loads are told apart by a 12-bit immediate offset");
-  constexpr int WPB = wpb_of(FLAGS);
-  constexpr int NST = (FLAGS & kStages3) ? 3 : 2;   // tiles of CSR in flight per wavefront
+  constexpr int WPB = 4;
+  constexpr int NST = 2;   // tiles of CSR in flight per wavefront
   __shared__ __attribute__((aligned(16))) float tile_all[WPB][TILE * rg::tile_floats(NF, STRIDE)];
   __shared__ f32x2 rowacc_all[WPB][64 * NF];
   const int lane = threadIdx.x & 63;
@@ -131,7 +105,7 @@ __global__ __launch_bounds__(64 * wpb_of(FLAGS)) void csr_apply_dyn_kernel(
   float* tile = tile_all[wv];
   f32x2* rowacc = rowacc_all[wv];
 
-  const unsigned blk = place_block<XCD>(blockIdx.x, gridDim.x);
+  const unsigned blk = blockIdx.x;
   // segment index: line-major, segs_per_line segments of <= 64 rows per line.  32-bit arithmetic: a 64-bit division
   // costs a few hundred instructions per wavefront on this ISA.
   const unsigned seg0 = blk * WPB + wv;
@@ -190,14 +164,7 @@ __global__ __launch_bounds__(64 * wpb_of(FLAGS)) void csr_apply_dyn_kernel(
     };
     auto gather = [&](const Stage& sg, Values& val) {
 #pragma unroll
-      for (int it = 0; it < IT; ++it) {
-        if constexpr ((FLAGS & kNoGather) != 0) {   // timing-only ablation
-#pragma unroll
-          for (int f = 0; f < STRIDE; ++f) val.v[it][f] = __builtin_bit_cast(float, sg.ci[it]);
-        } else {
-          buffer_load_packed<STRIDE>(rp, (unsigned)sg.ci[it], val.v[it]);
-        }
-      }
+      for (int it = 0; it < IT; ++it) buffer_load_packed<STRIDE>(rp, (unsigned)sg.ci[it], val.v[it]);
     };
     auto step = [&](int t, Stage& cur, const Stage& nxt, const Values& val, Values& val_nxt) {
       gather(nxt, val_nxt);
@@ -240,10 +207,10 @@ __global__ __launch_bounds__(64 * wpb_of(FLAGS)) void csr_apply_dyn_kernel(
   }
 }
 
-template <typename IndT, int NF, int STRIDE, int TILE, int XCD, int FLAGS>
+template <typename IndT, int NF, int STRIDE, int TILE>
 int launch_dyn(const void* indptr, const int32_t* gidx, const float* wts, long n_vox, long line_len, const float* packed,
                long n_gates, float fill, float* out, hipStream_t s) {
-  constexpr int WPB = wpb_of(FLAGS);
+  constexpr int WPB = 4;
   const long segs_per_line = (line_len + 63) / 64;
   const long n_segs = (n_vox / line_len) * segs_per_line;
   if (n_segs > 0xFFFFFFF0L) {
@@ -251,7 +218,7 @@ int launch_dyn(const void* indptr, const int32_t* gidx, const float* wts, long n
     return RG_EUNSUPPORTED;
   }
   const long blocks = (n_segs + WPB - 1) / WPB;
-  hipLaunchKernelGGL((csr_apply_dyn_kernel<IndT, NF, STRIDE, TILE, XCD, FLAGS>), dim3((unsigned)blocks), dim3(64 * WPB),
+  hipLaunchKernelGGL((csr_apply_dyn_kernel<IndT, NF, STRIDE, TILE>), dim3((unsigned)blocks), dim3(64 * WPB),
                      0, s, static_cast<const IndT*>(indptr), gidx, wts, n_vox, line_len, (unsigned)segs_per_line,
                      (unsigned)n_segs, kSegmentRotation, packed,
                      (unsigned)(n_gates - 1), fill, out);
@@ -261,63 +228,47 @@ int launch_dyn(const void* indptr, const int32_t* gidx, const float* wts, long n
 template <typename IndT>
 int dispatch(int nf, int variant, const void* indptr, const int32_t* gidx, const float* wts, long n_vox, long line_len,
              const float* packed, long n_gates, float fill, float* out, hipStream_t s) {
-#define RG_KD(NF_, ST_, TILE_, XCD_, FLAGS_) \
-  launch_dyn<IndT, NF_, ST_, TILE_, XCD_, FLAGS_>(indptr, gidx, wts, n_vox, line_len, packed, n_gates, fill, out, s)
+#define RG_KD(NF_, ST_, TILE_) \
+  launch_dyn<IndT, NF_, ST_, TILE_>(indptr, gidx, wts, n_vox, line_len, packed, n_gates, fill, out, s)
   // `variant`: 0 = what ships.  128/256/384/512 select the pipeline tile explicitly (A/B timing, and the bit-identity
-  // tests of rg_csr_compact_apply_f32 with a non-default tile); the other codes are single-field tuning variants
-  // (tools/tune_k1.py).
+  // tests of rg_csr_compact_apply_f32 with a non-default tile).
   if (nf == 1) {
     switch (variant) {
-#ifdef RG_EXPERIMENTS   // tuning variants and the timing-only ablation: experiment builds (tools/build_experiments.py) only
-      case 8: return RG_KD(1, 1, 512, kXcdSlab, 0);       // XCD placement
-      case 16: return RG_KD(1, 1, 512, kXcdGroup, 0);
-      case 18: return RG_KD(1, 1, 256, kXcdNone, 0);
-      case 23: return RG_KD(1, 1, 448, kXcdNone, 0);
-      case 9: return RG_KD(1, 1, 512, kXcdNone, 0);
-      case 17: return RG_KD(1, 1, 640, kXcdNone, 0);
-      case 19: return RG_KD(1, 1, 512, kXcdNone, kWpb1);  // waves per workgroup
-      case 20: return RG_KD(1, 1, 512, kXcdNone, kWpb2);
-      case 21: return RG_KD(1, 1, 512, kXcdNone, kWpb8);
-      case 22: return RG_KD(1, 1, 512, kXcdNone, kStages3);   // three CSR tiles in flight
-      case 24: return RG_KD(1, 1, 384, kXcdNone, kStages3);
-      case 25: return RG_KD(1, 1, 256, kXcdNone, kStages3);
-      case 28: return RG_KD(1, 1, 512, kXcdNone, kNoGather);  // timing-only ablation: no field gather (wrong results)
-#endif
-      case 128: return RG_KD(1, 1, 128, kXcdNone, 0);     // pipeline tile (right answers; another order of the float32 adds)
-      case 256: return RG_KD(1, 1, 256, kXcdNone, 0);
-      case 512: return RG_KD(1, 1, 512, kXcdNone, 0);
-      default: return RG_KD(1, 1, 384, kXcdNone, 0);   // 384-pair tiles: same speed as 512 or slightly better, 72 VGPRs
+      case 128: return RG_KD(1, 1, 128);     // pipeline tile (right answers; another order of the float32 adds)
+      case 256: return RG_KD(1, 1, 256);
+      case 512: return RG_KD(1, 1, 512);
+      default: return RG_KD(1, 1, 384);   // 384-pair tiles: same speed as 512 or slightly better, 72 VGPRs
     }
   }
   switch (nf) {
     case 2:
       switch (variant) {
-        case 128: return RG_KD(2, 2, 128, kXcdNone, 0);
-        case 256: return RG_KD(2, 2, 256, kXcdNone, 0);
-        case 512: return RG_KD(2, 2, 512, kXcdNone, 0);
-        default: return RG_KD(2, 2, 384, kXcdNone, 0);
+        case 128: return RG_KD(2, 2, 128);
+        case 256: return RG_KD(2, 2, 256);
+        case 512: return RG_KD(2, 2, 512);
+        default: return RG_KD(2, 2, 384);
       }
     case 3:
       switch (variant) {
-        case 128: return RG_KD(3, 4, 128, kXcdNone, 0);
-        case 192: return RG_KD(3, 4, 192, kXcdNone, 0);
-        case 256: return RG_KD(3, 4, 256, kXcdNone, 0);
-        case 320: return RG_KD(3, 4, 320, kXcdNone, 0);
+        case 128: return RG_KD(3, 4, 128);
+        case 192: return RG_KD(3, 4, 192);
+        case 256: return RG_KD(3, 4, 256);
+        case 320: return RG_KD(3, 4, 320);
         // config 2 / bench grid, ms: 256 -> 2.48 / 17.5, 320 -> 2.37 / 16.9, 384 -> 2.39 / 17.1; 384 = 2 x 192 pairs is
         // also what the packed stream of the compact kernel needs (same tile = same bits)
-        default: return RG_KD(3, 4, 384, kXcdNone, 0);
+        default: return RG_KD(3, 4, 384);
       }
     case 4:
       switch (variant) {
-        case 128: return RG_KD(4, 4, 128, kXcdNone, 0);
-        case 256: return RG_KD(4, 4, 256, kXcdNone, 0);
-        case 320: return RG_KD(4, 4, 320, kXcdNone, 0);
-        default: return RG_KD(4, 4, 384, kXcdNone, 0);
+        case 128: return RG_KD(4, 4, 128);
+        case 256: return RG_KD(4, 4, 256);
+        case 320: return RG_KD(4, 4, 320);
+        default: return RG_KD(4, 4, 384);
       }
-    case 5: return RG_KD(5, 8, 128, kXcdNone, 0);
-    case 6: return RG_KD(6, 8, 128, kXcdNone, 0);
-    case 7: return RG_KD(7, 8, 128, kXcdNone, 0);
-    default: return RG_KD(8, 8, 128, kXcdNone, 0);
+    case 5: return RG_KD(5, 8, 128);
+    case 6: return RG_KD(6, 8, 128);
+    case 7: return RG_KD(7, 8, 128);
+    default: return RG_KD(8, 8, 128);
   }
 #undef RG_KD
 }
@@ -344,11 +295,9 @@ extern "C" int rg_csr_apply_f32_ex(const void* indptr, int32_t indptr_is_i64, co
              (long)n_gates, stride);
   RG_REQUIRE(n_vox <= 0x3FFFFFFFFFL, RG_EUNSUPPORTED, "rg_csr_apply_f32: n_vox too large for one launch");
   RG_REQUIRE(rg::aligned16(packed), RG_EALIGN, "rg_csr_apply_f32: packed must be 16-byte aligned");
-#ifndef RG_EXPERIMENTS
   RG_REQUIRE(variant == 0 || variant == 128 || variant == 192 || variant == 256 || variant == 320 || variant == 384 ||
                  variant == 512, RG_EINVAL,
              "rg_csr_apply_f32_ex: variant must be 0 (default) or a pipeline tile of 128, 192, 256, 320, 384 or 512 pairs");
-#endif
   if (n_vox == 0) return RG_OK;
   if (line_len <= 0) line_len = n_vox;   // no grid lines known: one line, plain 64-row segments
   RG_REQUIRE(n_vox % line_len == 0, RG_EINVAL, "rg_csr_apply_f32: n_vox=%ld is not a multiple of line_len=%ld",

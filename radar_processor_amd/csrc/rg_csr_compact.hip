@@ -34,11 +34,9 @@
 
 namespace {
 
-// ABLATE (timing-only diagnostics, results wrong by construction): 1 = no row phase, 2 = no products and no row phase
-// (the values still have to be looked up: they are summed into the output), 3 = neither products, row phase nor window
 // PACKED: positions and weights come from 16-byte records of three pairs each (see rg_csr_compact_pack) instead of the
 // 2-byte position and 4-byte weight arrays: 5.33 instead of 6 bytes per pair, one dwordx4 per lane and 192 pairs.
-template <typename IndT, int NF, int STRIDE, int TILE, int ABLATE = 0, int AUX = 0, bool PACKED = false>
+template <typename IndT, int NF, int STRIDE, int TILE, bool PACKED = false>
 __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
     const IndT* __restrict__ indptr, const uint16_t* __restrict__ lidx, const float* __restrict__ wts,
     const int64_t* __restrict__ dict_ptr, const int32_t* __restrict__ dict, ChunkGrid cg,
@@ -111,14 +109,14 @@ __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
       const long r_t = t / 3;               // tiles are multiples of 192 pairs = 64 records
       const rsrc_t rr = make_rsrc(rec + rec_b + r_t, (rec_n - r_t) * 16);
 #pragma unroll
-      for (int k = 0; k < IT / 3; ++k) sgs.r[k] = rg_buffer_load_v4u32(rr, lane * 16 + k * 1024, 0, AUX);
+      for (int k = 0; k < IT / 3; ++k) sgs.r[k] = rg_buffer_load_v4u32(rr, lane * 16 + k * 1024, 0, 0);
     } else {
       const rsrc_t ri = make_rsrc(li + t, ((long)span - t) * 2);
       const rsrc_t rw = make_rsrc(wi + t, ((long)span - t) * 4);
 #pragma unroll
       for (int it = 0; it < IT; ++it) {
-        sgs.ci[it] = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(ri, lane2 + it * 128, 0, AUX);
-        sgs.cw[it] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, lane4 + it * 256, 0, AUX));
+        sgs.ci[it] = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(ri, lane2 + it * 128, 0, 0);
+        sgs.cw[it] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, lane4 + it * 256, 0, 0));
       }
     }
   };
@@ -151,7 +149,7 @@ __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
   stream(st[1], TILE);
 
   // ---- the chunk's field window: one gather per DISTINCT gate --------------------------------------------
-  if (windowed && ABLATE != 4) {
+  if (windowed) {
     for (int i = threadIdx.x; i < nd_all; i += 64 * kH) {
       const unsigned g0 = (unsigned)cdict[i];
       const unsigned g = g0 < last_gate ? g0 : last_gate;   // clamp: never fault
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
       }
     }
   }
-  if constexpr (ABLATE != 4) __syncthreads();
+  __syncthreads();
 
   // The tile loop exists twice -- values from the LDS window, or (over-wide chunk) position -> gate -> value from memory
   // -- selected once per workgroup: a uniform branch INSIDE the unrolled loads made this compiler drop the register
@@ -187,9 +185,7 @@ __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
       for (int it = 0; it < IT; ++it) {
         const int pos = ci[it] < nd_last ? ci[it] : nd_last;
         if constexpr (kWindowed) {
-          if constexpr (ABLATE >= 3) {
-            val[it][0] = __builtin_bit_cast(float, pos);
-          } else if constexpr (STRIDE == 1) {
+          if constexpr (STRIDE == 1) {
             val[it][0] = window[pos];
           } else if constexpr (STRIDE == 2) {
             const f32x2 q = reinterpret_cast<const f32x2*>(window)[pos];
@@ -212,17 +208,14 @@ __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
       }
       // ---- products of tile t -> LDS (layout and arithmetic: rg_row_phase.hpp) ----------------------------------
 #pragma unroll
-      for (int it = 0; it < IT; ++it) {
-        if constexpr (ABLATE >= 2) rowacc[lane * NF].x += val[it][0] * cw[it];
-        else rg::store_products<NF, STRIDE>(tile, TILE, eidx(it), cw[it], val[it]);
-      }
+      for (int it = 0; it < IT; ++it) rg::store_products<NF, STRIDE>(tile, TILE, eidx(it), cw[it], val[it]);
       stream(cur, t + 2 * TILE);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
       // ---- dynamic row phase (shared with rg_csr_apply_f32: same lane split, same float32 adds) ----------------
-      if constexpr (ABLATE == 0) rg::row_phase<NF, STRIDE, TILE>(tile, rowacc, t, rs_o, re_o, lane);
+      rg::row_phase<NF, STRIDE, TILE>(tile, rowacc, t, rs_o, re_o, lane);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -263,7 +256,7 @@ struct PackedStream {   // the packed form of positions + weights (rg_csr_compac
   int order = RG_REC_ORDER_SEGMENT;
 };
 
-template <typename IndT, int NF, int TILE, int ABLATE = 0, int AUX = 0, bool PACKED = false>
+template <typename IndT, int NF, int TILE, bool PACKED = false>
 int launch_nf(int window_cap, const void* indptr, const uint16_t* lidx, const float* wts, const int64_t* dict_ptr,
               const int32_t* dict, const ChunkGrid& cg, long n_vox, const float* packed, long n_gates, float fill,
               float* out, hipStream_t s, PackedStream ps = PackedStream()) {
@@ -273,7 +266,7 @@ int launch_nf(int window_cap, const void* indptr, const uint16_t* lidx, const fl
   constexpr int WS = NF == 3 ? 3 : STRIDE;   // floats per window entry (see the kernel)
   const long room = (65536 - (long)static_lds<IndT, NF, TILE>() - 256) / (4 * WS);
   if (window_cap > room) window_cap = (int)(room < 0 ? 0 : room);
-  hipLaunchKernelGGL((csr_compact_kernel<IndT, NF, STRIDE, TILE, ABLATE, AUX, PACKED>), dim3((unsigned)chunk_count(cg)),
+  hipLaunchKernelGGL((csr_compact_kernel<IndT, NF, STRIDE, TILE, PACKED>), dim3((unsigned)chunk_count(cg)),
                      dim3(64 * kH), ((size_t)window_cap * WS * sizeof(float) + 15) / 16 * 16, s,
                      static_cast<const IndT*>(indptr), lidx, wts, dict_ptr, dict, cg, packed, (unsigned)(n_gates - 1), fill,
                      window_cap, n_vox, out, ps.rec, ps.rec_ptr, ps.w_base, ps.order);
@@ -290,17 +283,6 @@ int launch(int nf, int tile, int window_cap, const void* indptr, const uint16_t*
   switch (nf) {
     case 1:
       switch (tile) {
-#ifdef RG_EXPERIMENTS   // timing-only ablations (tools/exp_nf1.py): results wrong by construction, never in the product library
-        case 901: return launch_nf<IndT, 1, 384, 1>(window_cap, indptr, lidx, wts, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s);
-        case 902: return launch_nf<IndT, 1, 384, 2>(window_cap, indptr, lidx, wts, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s);
-        case 903: return launch_nf<IndT, 1, 384, 3>(window_cap, indptr, lidx, wts, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s);
-        case 909: return launch_nf<IndT, 1, 384, 4>(window_cap, indptr, lidx, wts, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s);
-        case 904: return launch_nf<IndT, 1, 384, 3, 2>(window_cap, indptr, lidx, wts, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s);
-        case 905: return launch_nf<IndT, 1, 384, 0, 2>(window_cap, indptr, lidx, wts, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s);
-        case 906: return launch_nf<IndT, 1, 384, 0, 1>(window_cap, indptr, lidx, wts, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s);
-        case 907: return launch_nf<IndT, 1, 384, 0, 3>(window_cap, indptr, lidx, wts, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s);
-        case 908: return launch_nf<IndT, 1, 512, 3>(window_cap, indptr, lidx, wts, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s);
-#endif
         case 128: return RG_K1C(1, 128);
         case 256: return RG_K1C(1, 256);
         case 512: return RG_K1C(1, 512);
@@ -360,15 +342,7 @@ extern "C" int rg_csr_compact_apply_f32(const void* indptr, int32_t indptr_is_i6
              "rg_csr_compact_apply_f32: pairs present but local_idx/weights/dict/packed/n_gates missing");
   RG_REQUIRE(n_gates <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_f32: n_gates exceeds int32 gate indices");
   RG_REQUIRE(n_vox <= 0x3FFFFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_f32: n_vox too large for one launch");
-#ifdef RG_EXPERIMENTS
-  const int32_t rot_override = tile / 1000;   // diagnostic: tile = 1000 * rotation + tile selects the block rotation
-  tile %= 1000;
-  const bool ablation = tile >= 901 && tile <= 909;
-#else
-  const int32_t rot_override = 0;
-  const bool ablation = false;
-#endif
-  RG_REQUIRE(tile == 0 || tile == 128 || tile == 192 || tile == 256 || tile == 320 || tile == 384 || tile == 512 || ablation,
+  RG_REQUIRE(tile == 0 || tile == 128 || tile == 192 || tile == 256 || tile == 320 || tile == 384 || tile == 512,
              RG_EINVAL, "rg_csr_compact_apply_f32: tile must be 0 (default), 128, 192, 256, 320, 384 or 512");
   RG_REQUIRE(window_cap >= 0 && window_cap <= RG_COMPACT_MAX_WINDOW, RG_EINVAL,
              "rg_csr_compact_apply_f32: window_cap %d outside 0..%d", window_cap, RG_COMPACT_MAX_WINDOW);
@@ -379,7 +353,6 @@ extern "C" int rg_csr_compact_apply_f32(const void* indptr, int32_t indptr_is_i6
              "rg_csr_compact_apply_f32: n_vox=%ld is not planes x lines_per_plane=%ld x line_len=%ld", (long)n_vox,
              (long)lines_per_plane, (long)line_len);
   RG_REQUIRE(chunk_count(cg) <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_f32: too many chunks for one launch");
-  if (rot_override > 0) cg.rot_step = (unsigned)rot_override;
   hipStream_t s = (hipStream_t)stream;
   if (indptr_is_i64)
     return launch<int64_t>(n_fields, tile, window_cap, indptr, local_idx, weights, dict_ptr, dict, cg, n_vox, packed,
@@ -510,8 +483,6 @@ extern "C" int rg_csr_compact_pack(const void* indptr, int32_t indptr_is_i64, co
 // Per field count (measured on config 2 and the bench grid, profiles/r02_rowwise_sweep.json; three fields re-tuned in
 // round 3 after the instruction diet of the loop: 3 records per step instead of 2, -2 %, profiles/r03_cfg3_sweep.json):
 //   KPRE   records per lane and step;   kTarget  records per lane and row L aims for;
-//   kNarrow  12-byte window entries for three fields (three 4-byte LDS reads per pair instead of one 16-byte read,
-//            but a quarter less LDS per workgroup);
 //   kRegs    the row sums travel to lane == row by shuffle and wait in registers instead of an LDS array;
 //   one field: the window holds (value, 1) per gate, (0, 0) where it is excluded, and a pair contributes w * (v', m) --
 //            the same float32 values as selecting on the sentinel, in packed multiply / add instructions.
@@ -520,28 +491,12 @@ namespace {
 
 constexpr int kRowwiseChunksPerBlock = 1;   // consecutive chunks one workgroup takes (see the kernel: 1 measured best)
 
-// DIAG (timing-only diagnostics of tools/exp_placement4.py, results wrong by construction; one field only): bit 0 = the
-// window is not gathered (no dictionary / field reads), bit 1 = no output store, bit 2 / bit 3 = cache policy sc0 / nt on
-// the record loads, bit 4 = no record loads at all (the stream is replaced by a constant)
-// Workgroups per CU the compiler must leave room for (= wavefronts per SIMD: a workgroup is one wavefront per SIMD), per
-// field count; 1 = no constraint.  -DRG_ROWWISE_WAVES1=.. / 3=..: A/B builds (tools/gpu_r03_ab_slots.sh occ).
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_WAVES1)
-#undef RG_ROWWISE_WAVES1
-#define RG_ROWWISE_WAVES1 1
-#endif
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_WAVES3)
-#undef RG_ROWWISE_WAVES3
-#define RG_ROWWISE_WAVES3 1
-#endif
-#if !defined(RG_EXPERIMENTS) || !defined(RG_ROWWISE_WAVES8)
-#undef RG_ROWWISE_WAVES8
-#define RG_ROWWISE_WAVES8 1
-#endif
-// COLS == 2 (planes mode): the wider epilogue is held to the column mode's wavefronts per SIMD for two to four fields (5, 4, 4) and
-// to at least 5 for one field.  Measured (-Rpass-analysis=kernel-resource-usage, no scratch): 80 / 90 / 112 / 120 VGPRs for
-// 1-4 fields, i.e. 6 / 5 / 4 / 4 wavefronts per SIMD -- the column mode's 77 / 83 / 101 / 107 keep the same counts.
-#define RG_ROWWISE_BOUNDS __launch_bounds__(64 * kH, (COLS == 2 ? (NF <= 2 ? 5 : 4) :                                           \
-                                                      NF == 1 ? RG_ROWWISE_WAVES1 : NF == 3 ? RG_ROWWISE_WAVES3 : NF >= 5 ? RG_ROWWISE_WAVES8 : 1))
+// Workgroups per CU the compiler must leave room for (= wavefronts per SIMD: a workgroup is one wavefront per SIMD); 1 = no
+// constraint, which is what the row-wise kernel itself measured best with.  COLS == 2 (planes mode): the wider epilogue is
+// held to the column mode's wavefronts per SIMD for two to four fields (5, 4, 4) and to at least 5 for one field.  Measured
+// (-Rpass-analysis=kernel-resource-usage, no scratch): 80 / 90 / 112 / 120 VGPRs for 1-4 fields, i.e. 6 / 5 / 4 / 4
+// wavefronts per SIMD -- the column mode's 77 / 83 / 101 / 107 keep the same counts.
+#define RG_ROWWISE_BOUNDS __launch_bounds__(64 * kH, (COLS == 2 ? (NF <= 2 ? 5 : 4) : 1))
 // COLS (rg_csr_compact_apply_columns_f32, csrc/rg_csr_columns.hip): the chunks a workgroup takes one after the other are
 // not consecutive blocks of the dispatch order but the LEVELS of one column of chunks -- the same (line group, segment)
 // patch from plane z0 to z1 - 1 of its level piece -- so that lane == row sees the voxels of its (y, x) column in ascending
@@ -556,7 +511,7 @@ constexpr int kRowwiseChunksPerBlock = 1;   // consecutive chunks one workgroup 
 // REGS: where the row sums wait for lane == row -- -1 = the field count's default (RowwiseConfig<NF>::regs), 0 = the LDS
 // array, 1 = registers.  Four fields: registers cost 99 VGPRs (4 wavefronts per SIMD), the LDS array 95 (5 wavefronts) and
 // 8 KiB of LDS per workgroup -- the launcher picks the array wherever the LDS still admits five workgroups per CU.
-template <typename IndT, int NF, int STRIDE, int DIAG = 0, int COLS = 0, int REGS = -1>
+template <typename IndT, int NF, int STRIDE, int COLS = 0, int REGS = -1>
 __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     const IndT* __restrict__ indptr, const int64_t* __restrict__ dict_ptr, const int32_t* __restrict__ dict, ChunkGrid cg,
     const float* __restrict__ packed, unsigned last_gate, float fill, int window_cap, long n_vox, float* __restrict__ out,
@@ -567,30 +522,15 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   static_assert(!PLANES || NF <= 4, "the planes mode is the column mode of 1-4 fields");
   using Cfg = RowwiseConfig<NF>;
   constexpr int KPRE = Cfg::kpre;
-  // Record prefetch (experiment builds only; measured SLOWER, EXPERIMENTS.md R4.11): touch loads -- one dword per 64 bytes, never
-  // read -- of the segment's first kPrefetchHead bytes before the window fill and, when round rho begins, of the records of round
-  // rho + kPrefetch - 1, so that the real loads would hit in L2.
-#if defined(RG_EXPERIMENTS) && defined(RG_ROWWISE_PREFETCH)
-  constexpr int kPrefetch = NF >= RG_ROWWISE_PREFETCH_MIN_NF ? RG_ROWWISE_PREFETCH : 0;
-  constexpr int kPrefetchHead = RG_ROWWISE_PREFETCH_HEAD;
-#else
-  constexpr int kPrefetch = 0;
-  constexpr int kPrefetchHead = 0;
-#endif
   constexpr bool kByteMask = rowwise_bytemask<NF>();       // window entries = (v' ..., byte mask): rg_compact_layout.hpp
-  constexpr bool kNarrow = Cfg::narrow && !kByteMask, kRegs = REGS < 0 ? Cfg::regs : REGS != 0;
+  constexpr bool kRegs = REGS < 0 ? Cfg::regs : REGS != 0;
   // Five fields and more (never the column mode): a row's sums do not travel to lane == row and wait there (2 * NF registers
   // for the whole segment) -- when a round ends the L lanes of a row, which all hold all its sums after the butterfly, SHARE
   // the fields: lane `sub` divides fields sub, sub + L, ... (a select tree over the bits of sub picks them) and parks the VALUES
   // in 2 KiB of LDS per wavefront; lane == row stores them as whole row runs when the segment ends (storing per round wrote 16-32-row
   // pieces: 1.37x the grid's bytes in partial lines, +1.4 %).  The same sums, the same division: the same bits.
-#if defined(RG_EXPERIMENTS) && defined(RG_ROWWISE_SCATTER_MIN_NF)
-  constexpr bool kScatter = NF >= RG_ROWWISE_SCATTER_MIN_NF && !COLS;
-  constexpr int kFenceMinNF = RG_ROWWISE_FENCE_MIN_NF;
-#else
   constexpr bool kScatter = NF >= 5 && !COLS;        // three / four fields: measured slower (stores of 16 rows x 4 fields)
   constexpr int kFenceMinNF = 3;
-#endif
   // one field: the window holds (v', m) = (value, 1) of a gate, (0, 0) where it is excluded, so that a pair contributes
   // w * (v', m) -- the same float32 values as selecting on the EXCLUDED sentinel (w * 0 = +0, w * 1 = w) in two packed
   // instructions instead of a compare, two selects, a product and two adds
@@ -598,24 +538,18 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   extern __shared__ __attribute__((aligned(16))) float window[];   // window_cap + 1 entries of rowwise_entry_words<NF>() words
   // byte masks of four fields and more: the mask words of the window_cap + 1 entries lie behind their value entries
   constexpr int kVW = rowwise_value_words<NF>(), kMW = rowwise_mask_words<NF>();
-  // the mask byte of a usable field: 1 (read back with v_cvt_f32_ubyteN, one per field) or the fp8 (OCP e4m3) code of 1.0 (read
-  // back two fields at a time with v_cvt_pk_f32_fp8)
-#if defined(RG_EXPERIMENTS) && defined(RG_ROWWISE_MASK_UBYTE)
-  constexpr bool kMaskFp8 = false;
-#else
-  constexpr bool kMaskFp8 = true;
+  // the mask byte of a usable field: the fp8 (OCP e4m3) code of 1.0, read back two fields at a time with v_cvt_pk_f32_fp8
+  // (one conversion per field pair instead of a v_cvt_f32_ubyteN per field)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "the byte masks assume v_cvt_pk_f32_fp8 decodes OCP e4m3 (0x38 = 1.0), as on gfx950"
 #endif
-  constexpr unsigned kMaskOne = kMaskFp8 ? 0x38u : 1u;
+  constexpr unsigned kMaskOne = 0x38u;
   (void)kMW;
   unsigned* const maskw = reinterpret_cast<unsigned*>(window + (size_t)(window_cap + 1) * kVW);
   __shared__ f32x2 rowacc_all[kRegs ? 1 : kH][kRegs ? 2 : 64 * NF];
   // kScatter with kStage: the finished values of a segment wait in LDS ([row][8 fields], 2 KiB per wavefront) so that lane == row
   // stores whole 248-byte row runs per field at the segment's end instead of 16-32-row pieces per round
-#if defined(RG_EXPERIMENTS) && defined(RG_ROWWISE_NO_STAGE)
-  constexpr bool kStage = false;
-#else
   constexpr bool kStage = kScatter;
-#endif
   __shared__ __attribute__((aligned(16))) float stage_all[kStage ? kH : 1][kStage ? 64 * 8 : 4];
 
   const int lane = threadIdx.x & 63;
@@ -627,12 +561,12 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   unsigned wmask = 0x3FFFFFFu;
   asm volatile("" : "+v"(wmask));
 
-  // A workgroup takes chunks_per_block CONSECUTIVE blocks of the dispatch order, one after the other (default: 1).
-  // Round-3 experiment: the kernel's only store costs 5-15 % of the launch (tools/exp_placement4.py: 7.4 ms without it,
+  // A workgroup takes chunks_per_block CONSECUTIVE blocks of the dispatch order, one after the other (the launcher passes 1).
+  // Round-3 experiment (EXPERIMENTS.md): the kernel's only store costs 5-15 % of the launch (7.4 ms without it,
   // 7.8-8.7 with it, depending on where records and grid lie in memory), and the first suspect was its acknowledgement
   // at the end of every workgroup's life.  Letting it overlap the next chunk's work changed nothing (2 / 4 / 8 / 32
   // chunks per workgroup: +0.1 ... +0.3 ms, the extra barrier): the cost is the memory system's, a trickle of writes
-  // among the reads (tools/exp_placement5.py reproduces it with a bare read probe).  The loop stays as the knob it is.
+  // among the reads (tools/exp_placement5.py reproduces it with a bare read probe).
   // COLS: this workgroup's column piece (item = piece * columns + column; columns rotated per line group like the blocks of
   // the dispatch order, so that consecutive workgroups -- consecutive XCDs -- do not pin a column of the grid to one XCD)
   unsigned col_yg = 0, col_sx = 0, col_piece = 0;
@@ -702,9 +636,7 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     rec_b = rec_ptr[slot];
     rec_n = rec_ptr[slot + 1] - rec_b;
   }
-  // DIAG & 2048 (timing-only): every segment reads its records 1/7 closer to the array's start, so that neighbours' streams
-  // overlap by a seventh -- the same loads, 14 % fewer distinct bytes from HBM (what a 4.57-byte-per-pair record would stream)
-  const rsrc_t rr = make_rsrc(rec + ((DIAG & 2048) ? rec_b * 6 / 7 : rec_b), rec_n * 16);
+  const rsrc_t rr = make_rsrc(rec + rec_b, rec_n * 16);
   constexpr int kOutOfRange = 0x7FFFFFF0;            // byte offset no segment reaches: the load returns zeros
 
   // ---- lanes per row ------------------------------------------------------------------------------------------
@@ -730,15 +662,6 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     trips_row = o > trips_row ? o : trips_row;
   }
 
-  // ---- record prefetch (see run(): kPrefetch) -- the segment's first records are touched before the window fill -------
-  unsigned pf_d0 = 0, pf_d1 = 0;
-  if constexpr (kPrefetch > 0) {
-    if (span > 0) {
-      pf_d0 = rg_buffer_load_u32(rr, lane * 64, 0, 0);              // out-of-range pieces return 0 without a memory access
-      if constexpr (kPrefetchHead > 4096) pf_d1 = rg_buffer_load_u32(rr, 4096 + lane * 64, 0, 0);
-    }
-  }
-
   // ---- the chunk's field window + the sentinel entry ----------------------------------------------------------
   // kFillBatch entries per thread at a time: their dictionary reads are issued back to back, then their field gathers, then
   // the LDS stores -- two memory latencies per batch.  (Round 2 walked the entries one by one: dictionary read, wait, gather,
@@ -748,11 +671,7 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   // step's record loads in front of the fill and holding them across it (+22 VGPRs, a wavefront of occupancy: 7-17 %
   // slower), and throw-away loads of the same addresses to warm the L2 meanwhile (+1.4-2.8 %).
   if (windowed) {
-#if !defined(RG_EXPERIMENTS) || !defined(RG_FILL_BATCH)
-#undef RG_FILL_BATCH
-#define RG_FILL_BATCH 4                          // 1 / 2 / 8 measured: +2 % / +0.3 % / +0.5 % on config 2 (A/B builds)
-#endif
-    constexpr int kFillBatch = RG_FILL_BATCH;
+    constexpr int kFillBatch = 4;                // 1 / 2 / 8 measured: +2 % / +0.3 % / +0.5 % on config 2 (A/B builds)
     const int last_entry = nd_all > 0 ? nd_all - 1 : 0;
     const int32_t* __restrict__ cd = nd_all > 0 ? cdict : (const int32_t*)dict_ptr;   // never dereference an empty dictionary
     for (int i0 = threadIdx.x; i0 <= nd_all; i0 += 64 * kH * kFillBatch) {
@@ -760,18 +679,11 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
 #pragma unroll
       for (int u = 0; u < kFillBatch; ++u) {
         const int i = i0 + u * 64 * kH;
-        gate[u] = (DIAG & 1) ? 0u : (unsigned)cd[i < last_entry ? i : last_entry];
+        gate[u] = (unsigned)cd[i < last_entry ? i : last_entry];
       }
       float v[kFillBatch][STRIDE];
 #pragma unroll
-      for (int u = 0; u < kFillBatch; ++u) {
-        if constexpr (DIAG & 1) {
-#pragma unroll
-          for (int s = 0; s < STRIDE; ++s) v[u][s] = 1.0f;
-        } else {
-          rg::load_packed<STRIDE>(packed, gate[u] < last_gate ? gate[u] : last_gate, v[u]);
-        }
-      }
+      for (int u = 0; u < kFillBatch; ++u) rg::load_packed<STRIDE>(packed, gate[u] < last_gate ? gate[u] : last_gate, v[u]);
 #pragma unroll
       for (int u = 0; u < kFillBatch; ++u) {
         // branch-free: a thread past the end stores the sentinel into the sentinel's entry once more (same bits from every
@@ -801,17 +713,11 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
             reinterpret_cast<f32x4*>(window)[2 * i + 1] = (f32x4){vv[4], vv[5], vv[6], vv[7]};
             reinterpret_cast<uint2*>(maskw)[i] = make_uint2(m[0], m[1]);
           }
-        } else if constexpr (kNarrow) {
-          window[i * 3] = v[u][0]; window[i * 3 + 1] = v[u][1]; window[i * 3 + 2] = v[u][2];
         } else if constexpr (kPremask) {
           const bool good = rg::f32_bits(v[u][0]) != RG_EXCLUDED_BITS;
           reinterpret_cast<f32x2*>(window)[i] = good ? (f32x2){v[u][0], 1.0f} : (f32x2){0.0f, 0.0f};
-        } else if constexpr (STRIDE == 1) {
-          window[i] = v[u][0];
-        } else if constexpr (STRIDE == 2) {
+        } else {                                 // two fields
           reinterpret_cast<f32x2*>(window)[i] = (f32x2){v[u][0], v[u][1]};
-        } else {
-          reinterpret_cast<f32x4*>(window)[i] = (f32x4){v[u][0], v[u][1], v[u][2], v[u][3]};
         }
       }
     }
@@ -864,11 +770,8 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   };
   auto issue = [&](const Step& r, rg_u32x4 (&regs)[KPRE]) {
 #pragma unroll
-    for (int k = 0; k < KPRE; ++k) {
-      if constexpr (DIAG & 16) regs[k] = (rg_u32x4){0x3F00000u, 0x3F00000u, 0x3F00000u, (unsigned)lane};
-      else regs[k] = rg_buffer_load_v4u32(rr, (k << lgl) < r.rem ? r.off0 + 16 * (k << lgl) : kOutOfRange, 0,
-                                          (DIAG & 4) ? 1 : (DIAG & 8) ? 2 : 0);
-    }
+    for (int k = 0; k < KPRE; ++k)
+      regs[k] = rg_buffer_load_v4u32(rr, (k << lgl) < r.rem ? r.off0 + 16 * (k << lgl) : kOutOfRange, 0, 0);
   };
   auto run = [&](auto wtag) {
     constexpr bool kWindowed = decltype(wtag)::value;
@@ -878,19 +781,11 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     // 8.051 vs 8.050 ms, same process and arrays; <= 1.3 % for 2-4 fields).  One chain per slot (three) reaches 4.3e-6 --
     // exact sums would give 4.2e-6, the reference's own rounding -- but costs a wavefront of occupancy (75 -> 89 VGPRs for
     // one field): +2.1 % on the bench grid, +10 / +21 % for two / four fields (profiles/r03_slots_ab.json).
-#if defined(RG_EXPERIMENTS) && defined(RG_ROWWISE_SLOTS)   // A/B builds only: 1 = round 2's one chain per lane
-    constexpr int KS = RG_ROWWISE_SLOTS < KPRE ? RG_ROWWISE_SLOTS : KPRE;
-#else
     constexpr int KS = 2;
-#endif
     // Five fields and more: the weight sums keep ONE chain.  They add positive terms only, so their rounding is a few 1e-8
     // of the sum whatever the order; the products -- where mixed signs cancel and the order shows in the result -- keep two.
     // (Eight fields: 165 VGPRs with two chains each, 3 wavefronts per SIMD; 4 wavefronts need <= 128.)
-#if defined(RG_EXPERIMENTS) && defined(RG_ROWWISE_WSLOTS8)
-    constexpr int KSW = NF >= 5 ? (RG_ROWWISE_WSLOTS8 < KS ? RG_ROWWISE_WSLOTS8 : KS) : KS;
-#else
     constexpr int KSW = NF >= 5 ? 1 : KS;
-#endif
     // Byte-mask kernels keep the sums of field PAIRS in 64-bit register pairs (bp / bw: what v_pk_mul / v_pk_add / v_pk_fma
     // take, and what the per-pair asm fences can name without splitting the pairs); the others keep scalars the compiler pairs.
     constexpr int NP2 = (NF + 1) / 2;
@@ -966,29 +861,16 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
               vv[0] = x.x; vv[1] = x.y; vv[2] = x.z; vv[3] = x.w;
               m[0] = NF == 3 ? rg::f32_bits(x.w) : maskw[e];
             } else {
-              if constexpr (DIAG & 1024) {      // timing-only: no window reads
-                const float fe = __builtin_bit_cast(float, 0x3F800000u | (unsigned)e);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) vv[q] = fe;
-                m[0] = m[1] = 0x38383838u;
-              } else {
               const f32x4 x = reinterpret_cast<const f32x4*>(window)[2 * e], y = reinterpret_cast<const f32x4*>(window)[2 * e + 1];
               vv[0] = x.x; vv[1] = x.y; vv[2] = x.z; vv[3] = x.w; vv[4] = y.x; vv[5] = y.y; vv[6] = y.z; vv[7] = y.w;
               const uint2 mm = reinterpret_cast<const uint2*>(maskw)[e];
               m[0] = mm.x; m[1] = mm.y;
-              }
             }
+            // one conversion per field PAIR: v_cvt_pk_f32_fp8 (OCP e4m3: 0x38 = 1.0, 0x00 = +0)
             using g2_t = decltype(__builtin_amdgcn_cvt_pk_f32_fp8(0, false));
-            f32x2 g2[4];
-            if constexpr (kMaskFp8) {      // one conversion per field PAIR: v_cvt_pk_f32_fp8 (OCP e4m3: 0x38 = 1.0, 0x00 = +0)
-              const g2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)m[0], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)m[0], true);
-              const g2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)m[1], false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)m[1], true);
-              g2[0] = (f32x2){a[0], a[1]}; g2[1] = (f32x2){b[0], b[1]}; g2[2] = (f32x2){c[0], c[1]}; g2[3] = (f32x2){d[0], d[1]};
-            } else {
-#pragma unroll
-              for (int j = 0; j < 4; ++j)
-                g2[j] = (f32x2){(float)((m[j >> 1] >> (16 * (j & 1))) & 0xFFu), (float)((m[j >> 1] >> (16 * (j & 1) + 8)) & 0xFFu)};
-            }
+            const g2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)m[0], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)m[0], true);
+            const g2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)m[1], false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)m[1], true);
+            const f32x2 g2[4] = {(f32x2){a[0], a[1]}, (f32x2){b[0], b[1]}, (f32x2){c[0], c[1]}, (f32x2){d[0], d[1]}};
             const f32x2 w2 = (f32x2){w[i], w[i]};
 #pragma unroll
             for (int j = 0; j < NP2; ++j) {
@@ -998,21 +880,14 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
             }
             if constexpr (NF >= kFenceMinNF) fence_sums(k % KS, k % KSW);   // one pair at a time: these sums are complete
             continue;                                                       // before the next pair's window reads are issued
-          } else if constexpr (kNarrow) {
-            v[0] = window[e * 3]; v[1] = window[e * 3 + 1]; v[2] = window[e * 3 + 2];
           } else if constexpr (kPremask) {
             const f32x2 term = (f32x2){w[i], w[i]} * reinterpret_cast<const f32x2*>(window)[e];
             ap[k % KS][0] += term.x;
             aw[k % KSW][0] += term.y;
             continue;
-          } else if constexpr (STRIDE == 1) {
-            v[0] = window[e];
-          } else if constexpr (STRIDE == 2) {
+          } else {                                  // two fields
             const f32x2 x = reinterpret_cast<const f32x2*>(window)[e];
             v[0] = x.x; v[1] = x.y;
-          } else {
-            const f32x4 x = reinterpret_cast<const f32x4*>(window)[e];
-            v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
           }
         } else {
           const unsigned g0 = (unsigned)cdict[p];
@@ -1028,14 +903,9 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
           // ONE select per field and pair: the effective weight is w or +0, and v_mul_legacy_f32 makes 0 * sentinel = +0
           // where an IEEE multiply would make NaN (for a non-zero weight the two multiplies are the same operation, so
           // unmasked NaN / Inf data propagates exactly as before: same bits as good ? w * v : 0)
-#if defined(RG_EXPERIMENTS) && defined(RG_ROWWISE_TWO_SELECTS)   // A/B builds only: round 2's form of the same arithmetic
-          addp(k % KS, f, good ? w[i] * v[f] : 0.0f);
-          addw(k % KSW, f, good ? w[i] : 0.0f);
-#else
           const float wf = good ? w[i] : 0.0f;
           addp(k % KS, f, rg_fmul_legacy(wf, v[f]));
           addw(k % KSW, f, wf);
-#endif
         }
         // the per-pair path of an over-wide chunk (rare): five fields and more take its pairs one at a time -- three 32-byte
         // gathers in flight per record would set the whole kernel's register count (167 instead of <= 128 for eight fields)
@@ -1122,8 +992,6 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
           if (j < (NP >> stages)) {                                 // wave-uniform
             if constexpr (kStage) {
               if (owner && f0 + j * lp < NF) stage[r.myrow * 8 + f0 + j * lp] = w[j] > 0.0f ? p[j] / w[j] : fill;
-            } else if constexpr (DIAG & 2) {      // timing-only: no output store
-              if (owner && f0 + j * lp < NF && p[j] == 123.456f) dst[j * step_f] = w[j];
             } else {
               if (owner && f0 + j * lp < NF) dst[j * step_f] = w[j] > 0.0f ? p[j] / w[j] : fill;
             }
@@ -1145,45 +1013,23 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
       }
     };
 
-    // touch the records of round rho (its rows are consecutive, so its records are one byte range; the first 4 KiB of it)
-    auto prefetch_round = [&](int rho) {
-      if (rho >= rounds) return;                                          // wave-uniform
-      const int first = rho * rpr;
-      const int last = (first + rpr < nrows ? first + rpr : nrows) - 1;
-      const unsigned b = (unsigned)__builtin_amdgcn_readlane(rs_o, first), e = (unsigned)__builtin_amdgcn_readlane(re_o, last);
-      const int ob = (int)(b / 3u) * 16, oe = (int)((e + 2u) / 3u) * 16;
-      const int off = ob + lane * 64;
-      asm volatile("" : : "v"(pf_d0));                                   // the previous touch has long returned
-      pf_d0 = rg_buffer_load_u32(rr, off < oe ? off : kOutOfRange, 0, 0);
-    };
     rg_u32x4 regs_a[KPRE], regs_b[KPRE];
     Step sa = setup(0), sb;
     issue(sa, regs_a);
     for (;;) {     // two register stages, alternating: nothing in flight is ever copied
       sb = advance(sa);
       issue(sb, regs_b);
-      if constexpr (kPrefetch > 0) {
-        if (sb.rho != sa.rho) prefetch_round(sb.rho + kPrefetch - 1);    // behind the real loads in the (in-order) queue
-      }
       process(sa, regs_a, sb.rho != sa.rho);
       if (sb.rho >= rounds) break;
       sa = advance(sb);
       issue(sa, regs_a);
-      if constexpr (kPrefetch > 0) {
-        if (sa.rho != sb.rho) prefetch_round(sa.rho + kPrefetch - 1);
-      }
       process(sb, regs_b, sa.rho != sb.rho);
       if (sa.rho >= rounds) break;
     }
   };
   if (span > 0) {
-#if defined(RG_EXPERIMENTS) && defined(RG_ROWWISE_NO_FALLBACK)     // register-count probe only: over-wide chunks are skipped
-    if (windowed) run(std::true_type{});
-#else
     if (windowed) run(std::true_type{}); else run(std::false_type{});
-#endif
   }
-  if constexpr (kPrefetch > 0) asm volatile("" : : "v"(pf_d0), "v"(pf_d1));      // the touches end here
   // PLANES: the selection words of lane == row, read again at every level (from L2: 4 bytes per selection and row) rather than
   // kept in registers through the streaming loop, where they would cost two fields a wavefront per SIMD
   // (32-bit pixel offsets from wave-uniform bases: the loads and stores take the scalar-base form, no 64-bit address per lane)
@@ -1203,13 +1049,7 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
       const f32x4 lo = reinterpret_cast<const f32x4*>(stage)[2 * lane], hi = reinterpret_cast<const f32x4*>(stage)[2 * lane + 1];
       const float vals[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        if constexpr (DIAG & 2) {
-          if (vals[f] == 123.456f) out[(size_t)f * n_vox + r0 + lane] = vals[f];
-        } else {
-          out[(size_t)f * n_vox + r0 + lane] = vals[f];
-        }
-      }
+      for (int f = 0; f < NF; ++f) out[(size_t)f * n_vox + r0 + lane] = vals[f];
     }
   }
   if (lane < nrows && !(kScatter && span > 0)) {     // kScatter: the rounds stored their rows; a segment without pairs has none
@@ -1218,25 +1058,7 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
       f32x2 s = (f32x2)(0.0f);
       if constexpr (kRegs) s = (f32x2){mine_p[f], mine_w[f]};
       else if (span > 0) s = rowacc[lane * NF + f];
-      if constexpr (DIAG & 2) {
-        if (s.x == 123.456f) out[(size_t)f * n_vox + r0 + lane] = s.y;       // practically never
-      } else if constexpr (DIAG & 32) {      // dense, dispatch-ordered store: 1 KiB per workgroup, neighbours adjacent
-        const long idx = ((long)bid * kH + wv) * 64 + lane;
-        if (idx < n_vox) out[idx] = s.y > 0.0f ? (float)((double)s.x / (double)s.y) : fill;
-      } else if constexpr (DIAG & 128) {     // non-temporal store
-        __builtin_nontemporal_store(s.y > 0.0f ? (float)((double)s.x / (double)s.y) : fill, &out[(size_t)f * n_vox + r0 + lane]);
-      } else if constexpr (DIAG & 256) {     // write-through store (sc0 sc1)
-        const float val = s.y > 0.0f ? (float)((double)s.x / (double)s.y) : fill;
-        float* dst = &out[(size_t)f * n_vox + r0 + lane];
-        asm volatile("global_store_dword %0, %1, off sc0 sc1" : : "v"(dst), "v"(val) : "memory");
-      } else if constexpr (DIAG & 512) {     // sc1 only
-        const float val = s.y > 0.0f ? (float)((double)s.x / (double)s.y) : fill;
-        float* dst = &out[(size_t)f * n_vox + r0 + lane];
-        asm volatile("global_store_dword %0, %1, off sc1" : : "v"(dst), "v"(val) : "memory");
-      } else if constexpr (DIAG & 64) {      // grid layout, but only the 128-byte lines this wavefront owns entirely
-        const long a = r0 + lane, lo = (r0 + 31) & ~31L, hi = (r0 + nrows) & ~31L;
-        if (a >= lo && a < hi) out[a] = s.y > 0.0f ? (float)((double)s.x / (double)s.y) : fill;
-      } else if constexpr (COLS) {
+      if constexpr (COLS) {
         const float val = s.y > 0.0f ? (float)((double)s.x / (double)s.y) : fill;
         const int z = col_z0 + cb;
         if (out) out[(size_t)f * n_vox + r0 + lane] = val;
@@ -1308,28 +1130,28 @@ inline bool rowwise_lds_rowsums(int nf, int window_cap) {
   return nf == 4 && ((long)(window_cap + 1) * 4 * rowwise_entry_words<4>() + (long)kH * 64 * 4 * 8 + 512) * 5 <= kLdsPerCu;
 }
 
-template <typename IndT, int NF, int DIAG = 0>
+template <typename IndT, int NF>
 int launch_rowwise(int window_cap, const void* indptr, const int64_t* dict_ptr, const int32_t* dict, const ChunkGrid& cg,
                    long n_vox, const float* packed, long n_gates, float fill, float* out, hipStream_t s,
-                   const PackedStream& ps, int lanes_hint, int chunks_per_block = 0) {
+                   const PackedStream& ps, int lanes_hint) {
   constexpr int STRIDE = stride_for(NF);
   constexpr int WS = rowwise_entry_words<NF>();                                   // 4-byte words per window entry
-  const bool lds_sums = DIAG == 0 && rowwise_lds_rowsums(NF, window_cap);
+  const bool lds_sums = rowwise_lds_rowsums(NF, window_cap);
   const long kStatic = NF >= 5 ? (long)kH * 64 * 8 * 4 + 16                                     // the staged values of 5-8 fields
                                : (RowwiseConfig<NF>::regs && !lds_sums) ? 16 : (long)kH * 64 * NF * 8;   // the row-sum array, if any
   // one entry beyond window_cap: the sentinel; a smaller window only sends more chunks down the per-pair path
   const long room = (65536 - kStatic - 256) / (4 * WS) - 1;
   if (window_cap > room) window_cap = (int)room;
   const long n_chunks = chunk_count(cg);
-  if (chunks_per_block <= 0) chunks_per_block = kRowwiseChunksPerBlock;      // an explicit request (tile = 2200 + n) is honoured
-  const dim3 grid((unsigned)((n_chunks + chunks_per_block - 1) / chunks_per_block)), block(64 * kH);
+  constexpr int cpb = kRowwiseChunksPerBlock;
+  const dim3 grid((unsigned)((n_chunks + cpb - 1) / cpb)), block(64 * kH);
   const size_t lds = ((size_t)(window_cap + 1) * WS * sizeof(float) + 15) / 16 * 16;
 #define RG_ROWWISE_LAUNCH(REGS_)                                                                                              \
-  hipLaunchKernelGGL((csr_compact_rowwise_kernel<IndT, NF, STRIDE, DIAG, false, REGS_>), grid, block, lds, s,                   \
+  hipLaunchKernelGGL((csr_compact_rowwise_kernel<IndT, NF, STRIDE, 0, REGS_>), grid, block, lds, s,                        \
                      static_cast<const IndT*>(indptr), dict_ptr, dict, cg, packed, (unsigned)(n_gates - 1), fill, window_cap, \
-                     n_vox, out, ps.rec, ps.rec_ptr, ps.w_base, lanes_hint, ps.order, (unsigned)n_chunks, chunks_per_block,   \
+                     n_vox, out, ps.rec, ps.rec_ptr, ps.w_base, lanes_hint, ps.order, (unsigned)n_chunks, cpb,                \
                      RowwiseColumns())
-  if constexpr (NF == 4 && DIAG == 0) {
+  if constexpr (NF == 4) {
     if (lds_sums) RG_ROWWISE_LAUNCH(0); else RG_ROWWISE_LAUNCH(-1);
   } else {
     RG_ROWWISE_LAUNCH(-1);
@@ -1352,7 +1174,7 @@ static int launch_rowwise_columns_t(int window_cap, const void* indptr, const in
   constexpr long kStatic = RowwiseConfig<NF>::regs ? 16 : (long)kH * 64 * NF * 8;
   const long room = (65536 - kStatic - 256) / (4 * WS) - 1;
   if (window_cap > room) window_cap = (int)room;
-  hipLaunchKernelGGL((csr_compact_rowwise_kernel<IndT, NF, STRIDE, 0, PLANES ? 2 : 1, kRegsCols>), dim3(cols.n_cols * (unsigned)cols.pieces),
+  hipLaunchKernelGGL((csr_compact_rowwise_kernel<IndT, NF, STRIDE, PLANES ? 2 : 1, kRegsCols>), dim3(cols.n_cols * (unsigned)cols.pieces),
                      dim3(64 * kH), ((size_t)(window_cap + 1) * WS * sizeof(float) + 15) / 16 * 16, s,
                      static_cast<const IndT*>(indptr), dict_ptr, dict, cg, packed, (unsigned)(n_gates - 1), fill, window_cap, n_vox,
                      out, static_cast<const rg_u32x4*>(rec), rec_ptr, w_base, lanes_hint, rec_order,
@@ -1416,42 +1238,7 @@ int launch_rowwise_nf(int nf, int window_cap, const void* indptr, const int64_t*
                       const ChunkGrid& cg, long n_vox, const float* packed, long n_gates, float fill, float* out,
                       hipStream_t s, const PackedStream& ps, int lanes_hint) {
 #define RG_ROW(NF_) \
-  launch_rowwise<IndT, NF_>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, lanes_hint, cpb)
-  int cpb = 0;
-#ifdef RG_EXPERIMENTS
-  if (lanes_hint >= 200 && lanes_hint <= 264) {                // tile = 2200 + n: n consecutive chunks per workgroup
-    cpb = lanes_hint - 200;
-    lanes_hint = 0;
-  }
-  if (nf == 8 && lanes_hint >= 100 && lanes_hint < 200) {      // eight fields, timing-only: 1 = no gather, 2 = no store, 16 = no
-    switch (lanes_hint - 100) {                                //   record loads, 40 = no window reads, 42 = 40 + 2, 19 = 16 + 2 + 1
-      case 1: return launch_rowwise<IndT, 8, 1>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, 1);
-      case 2: return launch_rowwise<IndT, 8, 2>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, 1);
-      case 16: return launch_rowwise<IndT, 8, 16>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, 1);
-      case 19: return launch_rowwise<IndT, 8, 19>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, 1);
-      case 40: return launch_rowwise<IndT, 8, 1024>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, 1);
-      case 42: return launch_rowwise<IndT, 8, 1026>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, 1);
-      case 43: return launch_rowwise<IndT, 8, 1027>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, 1);
-      case 59: return launch_rowwise<IndT, 8, 1043>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, 1);
-      default: break;
-    }
-  }
-  if (nf == 1 && lanes_hint >= 100 && lanes_hint < 200) {      // timing-only diagnostics (tile = 2100 + DIAG bits)
-    const int cpb1 = 1;          // the diagnostics run one chunk per workgroup
-#define RG_DIAG(D_) \
-  case D_: return launch_rowwise<IndT, 1, D_>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, cpb1)
-    switch (lanes_hint - 100) {
-      RG_DIAG(1); RG_DIAG(2); RG_DIAG(3); RG_DIAG(4); RG_DIAG(8); RG_DIAG(16); RG_DIAG(17); RG_DIAG(19); RG_DIAG(32);
-      RG_DIAG(64);
-      case 70: return launch_rowwise<IndT, 1, 128>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, cpb1);
-      case 71: return launch_rowwise<IndT, 1, 256>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, cpb1);
-      case 72: return launch_rowwise<IndT, 1, 512>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, cpb1);
-      case 73: return launch_rowwise<IndT, 1, 2048>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, 0, cpb1);
-      default: break;
-    }
-#undef RG_DIAG
-  }
-#endif
+  launch_rowwise<IndT, NF_>(window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates, fill, out, s, ps, lanes_hint)
   switch (nf) {
     case 1: return RG_ROW(1);
     case 2: return RG_ROW(2);
@@ -1468,7 +1255,7 @@ int launch_rowwise_nf(int nf, int window_cap, const void* indptr, const int64_t*
 }  // namespace
 
 // 1-4 fields over the packed stream.  tile = 0: the row-wise kernel (agrees with rg_csr_apply_f32 to float32 rounding);
-// tile = 384 (one field: also 576 / 768): the tile kernel over the same records (agrees with it bit for bit);
+// tile = 384: the tile kernel over the same records (agrees with it bit for bit);
 // tile = 2000 + h: row-wise with a diagnostic lane split (h = 1..64: that many lanes per row; h = 70 + t: aim for t
 // records per lane and row) -- a different split is a different order of the float32 adds.
 extern "C" int rg_csr_compact_apply_packed_f32(const void* indptr, int32_t indptr_is_i64, const void* records,
@@ -1480,17 +1267,11 @@ extern "C" int rg_csr_compact_apply_packed_f32(const void* indptr, int32_t indpt
                                                int32_t window_cap, int32_t tile, rg_stream_t stream) {
   const bool rowwise = tile == 0 || tile >= 2000;
   const int lanes_hint = tile >= 2000 ? tile - 2000 : 0;
-#ifdef RG_EXPERIMENTS   // 2100 + DIAG bits (timing-only, wrong results) and 2200 + chunks per workgroup: experiment builds only
-  const bool experiment = (lanes_hint >= 100 && lanes_hint < 200) || (lanes_hint >= 201 && lanes_hint <= 264);
-#else
-  const bool experiment = false;
-#endif
-  RG_REQUIRE(tile == 0 || tile == 384 || ((tile == 576 || tile == 768) && n_fields == 1) ||
+  RG_REQUIRE(tile == 0 || tile == 384 ||
                  (tile >= 2000 && ((lanes_hint >= 1 && lanes_hint <= 64 && (lanes_hint & (lanes_hint - 1)) == 0) ||
-                                   (lanes_hint > 70 && lanes_hint <= 99) || experiment)),
+                                   (lanes_hint > 70 && lanes_hint <= 99))),
              RG_EINVAL,
-             "rg_csr_compact_apply_packed_f32: tile must be 0 (row-wise kernel), 384 (tile kernel; one field: also 576 / "
-             "768) or 2000 + lane split");
+             "rg_csr_compact_apply_packed_f32: tile must be 0 (row-wise kernel), 384 (tile kernel) or 2000 + lane split");
   RG_REQUIRE(rec_order == RG_REC_ORDER_SEGMENT || rec_order == RG_REC_ORDER_DISPATCH, RG_EINVAL,
              "rg_csr_compact_apply_packed_f32: rec_order=%d is neither RG_REC_ORDER_SEGMENT nor RG_REC_ORDER_DISPATCH", rec_order);
   RG_REQUIRE(n_fields >= 1 && n_fields <= (rowwise ? 8 : 4), RG_EUNSUPPORTED,
@@ -1527,14 +1308,9 @@ extern "C" int rg_csr_compact_apply_packed_f32(const void* indptr, int32_t indpt
                                                       fill_value, out, s, ps, lanes_hint)
                          : launch_rowwise_nf<int32_t>(n_fields, window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates,
                                                       fill_value, out, s, ps, lanes_hint);
-#define RG_K1P(IND_, NF_)                                                                                              \
-  launch_nf<IND_, NF_, 384, 0, 0, true>(window_cap, indptr, nullptr, nullptr, dict_ptr, dict, cg, n_vox, packed, n_gates, \
-                                        fill_value, out, s, ps)
-#define RG_K1PT(IND_, TILE_)                                                                                            \
-  launch_nf<IND_, 1, TILE_, 0, 0, true>(window_cap, indptr, nullptr, nullptr, dict_ptr, dict, cg, n_vox, packed, n_gates, \
-                                        fill_value, out, s, ps)
-  if (tile == 576) return indptr_is_i64 ? RG_K1PT(int64_t, 576) : RG_K1PT(int32_t, 576);
-  if (tile == 768) return indptr_is_i64 ? RG_K1PT(int64_t, 768) : RG_K1PT(int32_t, 768);
+#define RG_K1P(IND_, NF_)                                                                                             \
+  launch_nf<IND_, NF_, 384, true>(window_cap, indptr, nullptr, nullptr, dict_ptr, dict, cg, n_vox, packed, n_gates, \
+                                  fill_value, out, s, ps)
   if (indptr_is_i64) {
     switch (n_fields) {
       case 1: return RG_K1P(int64_t, 1);
@@ -1550,7 +1326,6 @@ extern "C" int rg_csr_compact_apply_packed_f32(const void* indptr, int32_t indpt
     default: return RG_K1P(int32_t, 4);
   }
 #undef RG_K1P
-#undef RG_K1PT
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -75,23 +75,23 @@ __device__ __forceinline__ float weight_from_f32(float d2f, float r2f, float inv
 // Count and fill classify hits with the same code, so the second pass writes exactly what the first one counted; a
 // voxel's hits arrive in (cell row, sorted position) order, the row order the CSR has always had.
 constexpr int kGridMode = 0, kCountMode = 1, kFillMode = 2;
-#if !defined(RG_EXPERIMENTS) || !defined(RG_K2_BX)
-#undef RG_K2_BX
-#define RG_K2_BX 4            // block shape BX x (16 / BX) voxels; experiment builds: -DRG_K2_BX=8 / 16
-#endif
 
-// BX x BY = 16 voxels per block (BY rows of BX consecutive voxels); a wavefront walks 4 blocks side by side in x.
-template <int MODE, int W, int NF, int STRIDE, int BX>
+// Block shape: BX x BY = 16 voxels per block (BY rows of BX consecutive voxels); a wavefront walks 4 blocks side by side in
+// x.  With one gate list for all levels 8 x 2 measured best (16.0 ms on the bench grid against 16.5 for 4 x 4 and 19.4 for
+// 16 x 1); with the per-level lists, whose candidate stage is a third as long, the more compact 4 x 4 block (fewer survivors
+// per block) wins: 11.1 against 11.6 ms.
+constexpr int BX = 4, BY = 16 / BX, PX = 4 * BX;    // PX x BY: the patch of one wavefront, voxels of one level
+
+template <int MODE, int W, int NF, int STRIDE>
 __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, const float* __restrict__ packed, float fill,
                                                                float* __restrict__ out, int* __restrict__ counts,
                                                                const long long* __restrict__ indptr,
                                                                int* __restrict__ gidx, float* __restrict__ wts) {
-  constexpr int kVB = 16;             // voxels per block
-  constexpr int BY = kVB / BX;
-  constexpr int PX = 4 * BX;          // patch of one wavefront: PX x BY voxels of one level
+  constexpr int kVB = BX * BY;        // voxels per block
   constexpr int kSlots = 64 / kVB;    // queued records tested per dense step
   static_assert(kSlots == 4, "the builder's slot masks assume 4 records per dense step");
-  constexpr int kLgBX = BX == 16 ? 4 : BX == 8 ? 3 : 2;
+  constexpr int kLgBX = 2;
+  static_assert(1 << kLgBX == BX, "voxel (bxl, byl) of the block from the lane's voxel number");
   constexpr bool GRID = MODE == kGridMode;
   // Value ring (grid mode, 1-2 field slots): the packed field slots of every queued gate are fetched ONCE, when the
   // gate is queued (a queued gate hits up to 16 voxels over several dense steps; gathering per hit also puts a memory
@@ -174,10 +174,6 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
     const unsigned long long lower_slots = vox_lanes & ((1ull << (16 * slot)) - 1ull);
 
     auto dense = [&](int n) {  // test n queued records against the block's 16 voxels, 4 records per step
-#if defined(RG_EXPERIMENTS) && defined(RG_K2_ABL) && RG_K2_ABL == 1     // timing-only (tools/exp_k2_breakdown.py): the dense stage
-      head += n;                                                        // does nothing -- what is left is the candidate side
-      return;
-#endif
       // value-ring variant: the next step's record and field slots are read from LDS before this step's arithmetic,
       // so the LDS latency overlaps it; slots past n hold stale but addressable ring entries and are ignored
       rg_gate4 g_nx;
@@ -382,20 +378,15 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
   }
 }
 
-template <int BX>
 inline dim3 k2_grid(const SearchArgs& a) {
-  constexpr int BY = 16 / BX, PX = 4 * BX;
   const long waves = (long)((a.nx + PX - 1) / PX) * ((a.ny + BY - 1) / BY) * a.nz;
   return dim3((unsigned)((waves + 3) / 4));
 }
 
 template <int W, int NF, int STRIDE>
 int launch(const SearchArgs& a, const float* packed, float fill, float* out, hipStream_t s) {
-  // block shape: with one gate list for all levels 8 x 2 measured best (16.0 ms on the bench grid against 16.5 for 4 x 4 and 19.4
-  // for 16 x 1); with the per-level lists, whose candidate stage is a third as long, the more compact 4 x 4 block (fewer survivors
-  // per block) wins: 11.1 against 11.6 ms
-  hipLaunchKernelGGL((roi_block_kernel<kGridMode, W, NF, STRIDE, RG_K2_BX>), k2_grid<RG_K2_BX>(a), dim3(rg::kBlock), 0, s, a, packed, fill,
-                     out, (int*)nullptr, (const long long*)nullptr, (int*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL((roi_block_kernel<kGridMode, W, NF, STRIDE>), k2_grid(a), dim3(rg::kBlock), 0, s, a, packed, fill, out,
+                     (int*)nullptr, (const long long*)nullptr, (int*)nullptr, (float*)nullptr);
   return rg::check_launch("rg_roi_grid_f32");
 }
 
@@ -432,7 +423,7 @@ extern "C" int rg_roi_grid_f32(const rg_gate4* sorted_gates, const int32_t* cell
              stride_for(n_fields), n_fields);
   RG_REQUIRE(rg::aligned16(packed), RG_EALIGN, "rg_roi_grid_f32: packed must be 16-byte aligned");
   RG_REQUIRE((long)nx * ny * nz > 0 &&
-                 (long)((nx + 4 * RG_K2_BX - 1) / (4 * RG_K2_BX)) * ((ny + 16 / RG_K2_BX - 1) / (16 / RG_K2_BX)) * nz < 0xFFFFFFF0L,
+                 (long)((nx + PX - 1) / PX) * ((ny + BY - 1) / BY) * nz < 0xFFFFFFF0L,
              RG_EUNSUPPORTED,
              "rg_roi_grid_f32: grid too large for one launch");
   const SearchArgs a = make_args(sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx, min_radius, beam_factor);
@@ -456,7 +447,7 @@ extern "C" int rg_geom_count_f32(const rg_gate4* sorted_gates, const int32_t* ce
   if (rc != RG_OK) return rc;
   RG_REQUIRE(counts, RG_EINVAL, "rg_geom_count_f32: null counts");
   const SearchArgs a = make_args(sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx, min_radius, beam_factor);
-  hipLaunchKernelGGL((roi_block_kernel<kCountMode, RG_W_NEAREST, 1, 1, RG_K2_BX>), k2_grid<RG_K2_BX>(a), dim3(rg::kBlock), 0,
+  hipLaunchKernelGGL((roi_block_kernel<kCountMode, RG_W_NEAREST, 1, 1>), k2_grid(a), dim3(rg::kBlock), 0,
                      (hipStream_t)stream, a, (const float*)nullptr, 0.0f, (float*)nullptr, counts,
                      (const long long*)nullptr, (int*)nullptr, (float*)nullptr);
   return rg::check_launch("rg_geom_count_f32");
@@ -472,11 +463,11 @@ extern "C" int rg_geom_fill_f32(const rg_gate4* sorted_gates, const int32_t* cel
   RG_REQUIRE(weighting >= RG_W_BARNES2 && weighting <= RG_W_NEAREST, RG_EINVAL, "rg_geom_fill_f32: unknown weighting %d",
              weighting);
   const SearchArgs a = make_args(sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx, min_radius, beam_factor);
-  const dim3 grid = k2_grid<RG_K2_BX>(a), block(rg::kBlock);
+  const dim3 grid = k2_grid(a), block(rg::kBlock);
   hipStream_t s = (hipStream_t)stream;
   const long long* ip = reinterpret_cast<const long long*>(indptr);
 #define RG_FILL(W_)                                                                                                     \
-  hipLaunchKernelGGL((roi_block_kernel<kFillMode, W_, 1, 1, RG_K2_BX>), grid, block, 0, s, a, (const float*)nullptr, 0.0f,     \
+  hipLaunchKernelGGL((roi_block_kernel<kFillMode, W_, 1, 1>), grid, block, 0, s, a, (const float*)nullptr, 0.0f,               \
                      (float*)nullptr, (int*)nullptr, ip, gate_idx, weights)
   switch (weighting) {
     case RG_W_BARNES2: RG_FILL(RG_W_BARNES2); break;

@@ -604,10 +604,10 @@ def test_nonfinite_and_denormal_values_bit_for_bit_across_kernels(rg):
 
 
 def test_product_library_refuses_timing_only_and_experiment_tile_codes(rg):
-    """The shipped library computes right answers or refuses: the timing-only variants of the row-wise kernel (tile = 2100 +
-    bits: no store, no record loads, ...), several chunks per workgroup (2201 .. 2264), the ablations of the tile kernel
-    (901 .. 909, block-rotation overrides) and K1's tuning variants exist only in -DRG_EXPERIMENTS builds
-    (tools/build_experiments.py)."""
+    """The shipped library computes right answers or refuses: the codes of the removed timing-only variants of the row-wise
+    kernel (tile = 2100 + bits: no store, no record loads, ...), of several chunks per workgroup (2201 .. 2264), of the
+    single-field tuning variants of the packed tile kernel (576, 768), of the ablations of the tile kernel (901 .. 909,
+    block-rotation overrides) and of K1's tuning variants are RG_EINVAL."""
     import torch
     from radar_processor_amd import _native
     lib = rg.load_library()
@@ -617,7 +617,7 @@ def test_product_library_refuses_timing_only_and_experiment_tile_codes(rg):
     i64 = torch.zeros(8, dtype=torch.int64, device=dev)
     rec = torch.zeros((4, 4), dtype=torch.int32, device=dev)
     P = _native.ptr
-    for tile in (2100, 2102, 2116, 2199, 2201, 2204, 2264, 2265, 1999, 385):
+    for tile in (2100, 2102, 2116, 2199, 2201, 2204, 2264, 2265, 1999, 385, 576, 768):
         st = lib.rg_csr_compact_apply_packed_f32(P(ip), 0, P(rec), P(i64), _native.RG_REC_ORDER_DISPATCH, 120 << 23, P(i64),
                                                  P(ip), 64, 0, 64, 1, P(buf), 1, 1, 64, 0.0, P(buf), 256, tile, 0)
         assert st == _native.RG_EINVAL, (tile, st)

@@ -299,14 +299,14 @@ class TestNativeLibrary:
         assert lib.rg_geom_count_f32(1 << 12, 1 << 12, cells, 1 << 12, 1 << 12, 1 << 12, 3, 4, 4, 250.0, 0.01746, 1 << 12,
                                      None) == _native.RG_EINVAL and b"levels 3 .. 5" in lib.rg_last_error()
 
-    def test_product_library_refuses_experiment_codes(self):
+    def test_product_library_refuses_experiment_codes_and_has_no_knob_parameters(self):
         """Timing-only kernels (results wrong by construction) and tuning variants are not in the shipped library: their
-        tile / variant codes are RG_EINVAL (validation only, nothing is launched), and no DIAG instantiation of the row-wise
-        kernel is linked in (VERDICT r3 #6)."""
+        tile / variant codes are RG_EINVAL (validation only, nothing is launched), and the kernels have no template
+        parameters left that selected them (VERDICT r3 #6)."""
         import subprocess
         lib = rg.load_library(require_device=False)
         p = 1 << 12                                   # never dereferenced: every call fails validation first
-        for tile in (2100, 2102, 2116, 2199, 2201, 2264, 2265, 1999, 385):
+        for tile in (2100, 2102, 2116, 2199, 2201, 2264, 2265, 1999, 385, 576, 768):
             st = lib.rg_csr_compact_apply_packed_f32(p, 0, p, p, _native.RG_REC_ORDER_DISPATCH, 120 << 23, p, p, 64, 0, 64, 1,
                                                      p, 1, 1, 64, 0.0, p, 256, tile, None)
             assert st == _native.RG_EINVAL, (tile, st)
@@ -321,11 +321,14 @@ class TestNativeLibrary:
         assert nm_exe, "binutils nm is part of the image"
         nm = subprocess.run([nm_exe, "-C", "--defined-only", _native.LIB_PATH], capture_output=True, text=True)
         if nm.returncode == 0:       # host-side kernel stubs carry the template arguments
-            rows = [l for l in nm.stdout.splitlines() if "csr_compact_rowwise_kernel<" in l]
-            assert rows, "row-wise kernel not found in the symbol table"
-            for l in rows:           # <IndT, NF, STRIDE, DIAG, COLS, REGS>: DIAG must be 0 everywhere
-                args = l[l.index("csr_compact_rowwise_kernel<") + len("csr_compact_rowwise_kernel<"):].split(">(")[0].split(",")
-                assert len(args) == 6 and args[3].strip() == "0", l
+            # <IndT, NF, STRIDE, COLS, REGS>, <IndT, NF, STRIDE, TILE, PACKED>, <IndT, NF, STRIDE, TILE>
+            for kernel, n_args in (("csr_compact_rowwise_kernel<", 5), ("csr_compact_kernel<", 5),
+                                   ("csr_apply_dyn_kernel<", 4)):
+                rows = [l for l in nm.stdout.splitlines() if kernel in l]
+                assert rows, f"{kernel[:-1]} not found in the symbol table"
+                for l in rows:
+                    args = l[l.index(kernel) + len(kernel):].split(">(")[0].split(",")
+                    assert len(args) == n_args, l
 
     def test_ensure_built_rebuilds_a_stale_library(self, tmp_path, monkeypatch):
         """ensure_built() compiles when the library is missing AND when it was built from other sources or headers than

@@ -27,13 +27,7 @@ def main():
     ap.add_argument("--pieces", default="0,1,2,4")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--layout", default="auto")
-    ap.add_argument("--exp-lib", default="", help="tag[:-DFLAG,...]: run through an experiment build (tools/build_experiments.py)")
     args = ap.parse_args()
-    if args.exp_lib:
-        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-        import build_experiments
-        tag, _, flags = args.exp_lib.partition(":")
-        build_experiments.use(tag, [f for f in flags.split(",") if f])
     import torch
     import radar_processor_amd as rg
     from radar_processor_amd import grid_products as gp, synthetic
