@@ -251,6 +251,45 @@ int rg_roi_grid_f32(const rg_gate4* sorted_gates, const int32_t* cell_start, con
                     rg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Several radars on one grid (mosaic): K2 over up to RG_MAX_RADARS search structures in one launch, the joint masked
+ * weighted mean
+ *     out[f][v] = sum_r sum_{live j} w_j * v_j / sum_r sum_{live j} w_j   (fill_value where the sum is not > 0)
+ * where radar r's neighbours and weights of voxel v are those of radar_grid/compute.py:46-91 evaluated in that radar's
+ * frame (voxel coordinates relative to its antenna), and the mean is radar_grid/interpolate.py:69-104 over the union of
+ * every radar's neighbours.  The reference has no joint mean: it grids one radar per geometry.  Per radar, the
+ * arithmetic is rg_roi_grid_f32's; hits of all radars add into the same float32 accumulators, radar by radar in table
+ * order, and a radar whose window misses a voxel block is skipped.  One entry built from a search structure with a
+ * full-grid window and gate_offset 0 returns exactly the bits of rg_roi_grid_f32 on that structure.
+ *
+ * Entry r describes radar r:
+ *   sorted_gates, cell_start, cells   its cell-sorted gates (rg_geom_bin_gates_f32 / _levels_f32); a gate's index is the
+ *                                     radar's OWN gate number;
+ *   xc, yc, zc                        the float32 coordinates relative to this radar of the window's columns (xc[nx_win]),
+ *                                     rows (yc[ny_win]) and of every grid level (zc[nz]) -- slices of the radar's full
+ *                                     tables, so that they round as those do;
+ *   ix0, iy0, nx_win, ny_win          the window: voxels ix0 .. ix0 + nx_win - 1, iy0 .. iy0 + ny_win - 1 of the shared
+ *                                     grid (all levels); nx_win or ny_win == 0: the radar reaches no voxel (its pointers
+ *                                     are not read);
+ *   gate_offset, n_gates              radar r's gate g is packed slot gate_offset + g of `packed` (the rg_pack_fields_f32
+ *                                     layout over the concatenated gates); gate_offset + n_gates <= n_gates_total.
+ * The table is read on the host and passed by value in the kernel arguments.  RG_W_CLOSEST is not supported.
+ * ------------------------------------------------------------------------------------------------- */
+#define RG_MAX_RADARS 16
+typedef struct rg_mosaic_radar {
+  const rg_gate4* sorted_gates;
+  const int32_t* cell_start;
+  rg_cellgrid cells;
+  const float *xc, *yc, *zc;
+  int32_t ix0, iy0, nx_win, ny_win;
+  int64_t gate_offset, n_gates;
+} rg_mosaic_radar;
+
+int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_t n_radars, int32_t nz, int32_t ny, int32_t nx,
+                           double min_radius, double beam_factor, int32_t weighting, const float* packed,
+                           int32_t n_fields, int32_t stride, int64_t n_gates_total, float fill_value, float* out,
+                           rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * (f)3  processor-style collapse of the cached 3-D grid to the 2-D product plane:
  * radar_processor/processor.py:480-551 (collapse_grid_to_2d) and radar_processor/utils.py:336-387
  * (collapse_field_3d_to_2d).  'cappi' (nearest level, :530-533) and 'colmax' (:534-535) are

@@ -22,6 +22,8 @@ from .grid_products import (EARTH_RADIUS, EFFECTIVE_RADIUS_FACTOR, column_argmax
                             get_elevation_from_z_level)
 from .gridding import PlaneProducts, apply_geometry, apply_geometry_multi, grid_fields_device, grid_products_device
 from .roi_grid import roi_grid_fields_device
+from .mosaic import (MosaicSearch, apply_mosaic, apply_mosaic_multi, compute_mosaic_geometry, mosaic_fields_device,
+                     mosaic_limits, reach_window)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -45,6 +47,8 @@ __all__ = [
     "collapse_field_3d_to_2d", "collapse_grid_to_2d", "apply_filter_masks",
     # build-specific additions
     "save_device_layout", "load_device_layout", "column_argmax", "grid_fields_device", "grid_products_device", "PlaneProducts", "roi_grid_fields_device", "build_grid3d_package", "device_gate_mask", "RoiSearch", "DeviceCSR",
+    "mosaic_limits", "reach_window", "compute_mosaic_geometry", "apply_mosaic", "apply_mosaic_multi", "MosaicSearch",
+    "mosaic_fields_device",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

@@ -82,11 +82,37 @@ constexpr int kGridMode = 0, kCountMode = 1, kFillMode = 2;
 // per block) wins: 11.1 against 11.6 ms.
 constexpr int BX = 4, BY = 16 / BX, PX = 4 * BX;    // PX x BY: the patch of one wavefront, voxels of one level
 
-template <int MODE, int W, int NF, int STRIDE>
-__global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, const float* __restrict__ packed, float fill,
+// Several radars on one grid (rg_roi_grid_mosaic_f32): one search structure per radar, passed by value in the kernel
+// arguments.  xc / yc are the radar's coordinate tables of its window (voxels ix0 .. ix0 + nxw - 1 of the shared grid),
+// zc its table of all levels; packed points at the radar's gate 0 inside the shared packed fields.
+struct MosaicRadar {
+  const rg_gate4* sorted;
+  const int* cell_start;
+  Cells c;
+  const float* xc;
+  const float* yc;
+  const float* zc;
+  const float* packed;
+  int ix0, iy0, nxw, nyw;     // nxw == 0 or nyw == 0: the radar reaches no voxel
+};
+struct MosaicArgs {
+  MosaicRadar r[RG_MAX_RADARS];
+  int n_radars;
+  int nz, ny, nx;
+  long n_vox;
+  double min_radius, beam_factor;
+};
+
+// MOSAIC (grid mode only): a voxel block visits every radar whose window meets it, in table order, runs the search of that
+// radar over its lists and coordinates and adds its hits into the block's one set of accumulators; the radar's queue is
+// drained before the next radar starts, so a radar's candidates never move another radar's slot assignment.
+template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false>
+__global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_t<MOSAIC, MosaicArgs, SearchArgs> a,
+                                                               const float* __restrict__ packed, float fill,
                                                                float* __restrict__ out, int* __restrict__ counts,
                                                                const long long* __restrict__ indptr,
                                                                int* __restrict__ gidx, float* __restrict__ wts) {
+  static_assert(!MOSAIC || MODE == kGridMode, "the mosaic grids; it builds no CSR");
   constexpr int kVB = BX * BY;        // voxels per block
   constexpr int kSlots = 64 / kVB;    // queued records tested per dense step
   static_assert(kSlots == 4, "the builder's slot masks assume 4 records per dense step");
@@ -119,41 +145,30 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
   const unsigned py = rem / wpx;
   const int iy0 = (int)py * BY, ix0 = (int)(rem - py * wpx) * PX;
   const int nvy = a.ny - iy0 < BY ? a.ny - iy0 : BY;
-  const double z = (double)a.zc[iz];                             // common to the whole wave
-  const int lvl_off = a.c.levels > 1 ? (a.c.level0 + iz) * (a.c.ncx * a.c.ncy) : 0;   // per-level gate lists: this level's cells
-  const float zf = (float)z;                                     // grid coordinates ARE float32 values: exact
   const int vl = lane & (kVB - 1);                               // voxel of the block this lane owns ...
   const int bxl = vl & (BX - 1), byl = vl >> kLgBX;              // ... at (bxl, byl) inside the block
   const int slot = lane >> 4;                                    // which of the 4 records of a dense step
-  const float ya = a.yc[iy0], yb = a.yc[iy0 + nvy - 1];
-  const float ylo = fminf(ya, yb), yhi = fmaxf(ya, yb);
+  // the search structure of the radar being visited (the only one without MOSAIC: set once per wave)
+  const rg_gate4* sorted;
+  const int* cell_start;
+  Cells c;
+  const float *xc, *yc;
+  const float* pk;
+  double z;                                                      // common to the whole wave
+  float zf, ylo, yhi;
+  int lvl_off;
+  if constexpr (!MOSAIC) {
+    sorted = a.sorted; cell_start = a.cell_start; c = a.c; xc = a.xc; yc = a.yc; pk = packed;
+    z = (double)a.zc[iz];
+    lvl_off = c.levels > 1 ? (c.level0 + iz) * (c.ncx * c.ncy) : 0;   // per-level gate lists: this level's cells
+    zf = (float)z;                                               // grid coordinates ARE float32 values: exact
+    const float ya = yc[iy0], yb = yc[iy0 + nvy - 1];
+    ylo = fminf(ya, yb); yhi = fmaxf(ya, yb);
+  }
 
   for (int b0 = 0; b0 < PX && ix0 + b0 < a.nx; b0 += BX) {
     const int nvx = a.nx - ix0 - b0 < BX ? a.nx - ix0 - b0 : BX;  // wave-uniform
     const bool vlive = bxl < nvx && byl < nvy;
-    // ---- this lane's voxel: the reference's float64 ROI (compute.py:46-47,57) and its float32 bounds --------
-    const double x = (double)a.xc[ix0 + b0 + (vlive ? bxl : 0)];
-    const double y = (double)a.yc[iy0 + (vlive ? byl : 0)];
-    const double dist = sqrt(x * x + y * y + z * z);
-    const double r = fmax(a.min_radius, dist * a.beam_factor);
-    const double r2 = r * r;
-    const float xf = (float)x, yf = (float)y, r2f = (float)r2;
-    // float32 d2 carries < 4e-7 relative error: outside [r2_lo, r2_hi] the float32 comparison is already exact
-    const float r2_hi = vlive ? (float)(r2 * (1.0 + 2e-6)) * (1.0f + 2.4e-7f) : -1.0f;
-    const float r2_lo = vlive ? (float)(r2 * (1.0 - 2e-6)) * (1.0f - 2.4e-7f) : -1.0f;  // dead lanes never hit
-    const float inv_r2q = (float)(-1.4426950408889634 * 4.0 / r2);      // see weight_from_f32
-    // ---- block-wide (wave-uniform) quantities ------------------------------------------------------------
-    double rmax = vlive ? r : 0.0;
-#pragma unroll
-    for (int m = 1; m < kVB; m <<= 1) rmax = fmax(rmax, __shfl_xor(rmax, m, 64));
-    rmax = readlane_f64(rmax, 0);
-    const float xa = a.xc[ix0 + b0], xb = a.xc[ix0 + b0 + nvx - 1];
-    const float xlo = fminf(xa, xb), xhi = fmaxf(xa, xb);
-    const float r2max_hi = (float)(rmax * rmax * (1.0 + 2e-6)) * (1.0f + 2.4e-7f);
-    const int cx0 = __builtin_amdgcn_readfirstlane(cell_clamped((double)xlo - rmax, a.c.x0, a.c.inv_cx, a.c.ncx));
-    const int cx1 = __builtin_amdgcn_readfirstlane(cell_clamped((double)xhi + rmax, a.c.x0, a.c.inv_cx, a.c.ncx));
-    const int cy0 = __builtin_amdgcn_readfirstlane(cell_clamped((double)ylo - rmax, a.c.y0, a.c.inv_cy, a.c.ncy));
-    const int cy1 = __builtin_amdgcn_readfirstlane(cell_clamped((double)yhi + rmax, a.c.y0, a.c.inv_cy, a.c.ncy));
 
     // weighted modes: acc_p = sum w*v, acc_w = sum w.  Closest-gate mode: acc_p = value of the closest gate so far,
     // acc_w = its float32 d2 (+inf = none), best_idx = its gate index (ties go to the lower index).
@@ -164,6 +179,7 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
     for (int f = 0; f < NF; ++f) { acc_p[f] = 0.0f; acc_w[f] = CLOSEST ? __builtin_inff() : 0.0f; best_idx[f] = 0x7FFFFFFF; }
     int head = 0, tail = 0;  // ring positions (wave-uniform, monotone)
     int ready = 0;           // records [head, ready) are complete (grid mode: their values have been parked)
+
     // builder modes: hits of this lane's voxel so far (identical in the voxel's 4 slot lanes) and its row base
     int cursor = 0;
     long long row_base = 0;
@@ -172,6 +188,57 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
     }
     const unsigned long long vox_lanes = 0x0001000100010001ull << vl;            // the 4 slot lanes of voxel vl
     const unsigned long long lower_slots = vox_lanes & ((1ull << (16 * slot)) - 1ull);
+
+    int n_visits = 1;
+    if constexpr (MOSAIC) n_visits = a.n_radars;
+    for (int visit = 0; visit < n_visits; ++visit) {
+    // x range [xv0, xv1] and y range [yv0, yv1] of the block's voxels the radar reaches, at wx0 / wy0 of its tables
+    int xv0 = ix0 + b0, xv1 = ix0 + b0 + nvx - 1, yv0 = iy0, wx0 = 0, wy0 = 0;
+    bool live = vlive;
+    if constexpr (MOSAIC) {
+      const MosaicRadar& R = a.r[visit];
+      const int yv1 = min(iy0 + nvy - 1, R.iy0 + R.nyw - 1);
+      xv0 = max(xv0, R.ix0); xv1 = min(xv1, R.ix0 + R.nxw - 1); yv0 = max(yv0, R.iy0);
+      if (xv0 > xv1 || yv0 > yv1) continue;                      // the window misses the block (wave-uniform)
+      wx0 = R.ix0; wy0 = R.iy0;
+      const int ixv = ix0 + b0 + bxl, iyv = iy0 + byl;
+      live = vlive && ixv >= xv0 && ixv <= xv1 && iyv >= yv0 && iyv <= yv1;   // lanes outside the window: dead for this radar
+      sorted = R.sorted; cell_start = R.cell_start; c = R.c; xc = R.xc; yc = R.yc; pk = R.packed;
+      z = (double)R.zc[iz];
+      lvl_off = c.levels > 1 ? (c.level0 + iz) * (c.ncx * c.ncy) : 0;
+      zf = (float)z;
+      const float ya = yc[yv0 - wy0], yb = yc[yv1 - wy0];
+      ylo = fminf(ya, yb); yhi = fmaxf(ya, yb);
+    }
+    // ---- this lane's voxel: the reference's float64 ROI (compute.py:46-47,57) and its float32 bounds --------
+    double x, y;
+    if constexpr (MOSAIC) {
+      x = (double)xc[(live ? ix0 + b0 + bxl : xv0) - wx0];
+      y = (double)yc[(live ? iy0 + byl : yv0) - wy0];
+    } else {
+      x = (double)xc[ix0 + b0 + (vlive ? bxl : 0)];
+      y = (double)yc[iy0 + (vlive ? byl : 0)];
+    }
+    const double dist = sqrt(x * x + y * y + z * z);
+    const double r = fmax(a.min_radius, dist * a.beam_factor);
+    const double r2 = r * r;
+    const float xf = (float)x, yf = (float)y, r2f = (float)r2;
+    // float32 d2 carries < 4e-7 relative error: outside [r2_lo, r2_hi] the float32 comparison is already exact
+    const float r2_hi = live ? (float)(r2 * (1.0 + 2e-6)) * (1.0f + 2.4e-7f) : -1.0f;
+    const float r2_lo = live ? (float)(r2 * (1.0 - 2e-6)) * (1.0f - 2.4e-7f) : -1.0f;  // dead lanes never hit
+    const float inv_r2q = (float)(-1.4426950408889634 * 4.0 / r2);      // see weight_from_f32
+    // ---- block-wide (wave-uniform) quantities ------------------------------------------------------------
+    double rmax = live ? r : 0.0;
+#pragma unroll
+    for (int m = 1; m < kVB; m <<= 1) rmax = fmax(rmax, __shfl_xor(rmax, m, 64));
+    rmax = readlane_f64(rmax, 0);
+    const float xa = xc[xv0 - wx0], xb = xc[xv1 - wx0];
+    const float xlo = fminf(xa, xb), xhi = fmaxf(xa, xb);
+    const float r2max_hi = (float)(rmax * rmax * (1.0 + 2e-6)) * (1.0f + 2.4e-7f);
+    const int cx0 = __builtin_amdgcn_readfirstlane(cell_clamped((double)xlo - rmax, c.x0, c.inv_cx, c.ncx));
+    const int cx1 = __builtin_amdgcn_readfirstlane(cell_clamped((double)xhi + rmax, c.x0, c.inv_cx, c.ncx));
+    const int cy0 = __builtin_amdgcn_readfirstlane(cell_clamped((double)ylo - rmax, c.y0, c.inv_cy, c.ncy));
+    const int cy1 = __builtin_amdgcn_readfirstlane(cell_clamped((double)yhi + rmax, c.y0, c.inv_cy, c.ncy));
 
     auto dense = [&](int n) {  // test n queued records against the block's 16 voxels, 4 records per step
       // value-ring variant: the next step's record and field slots are read from LDS before this step's arithmetic,
@@ -241,7 +308,7 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
             } else {
               w = weight_from_f32<W>(d2f, r2f, inv_r2q);
             }
-            if constexpr (!VRING) load_packed<STRIDE>(packed, (unsigned)g.index, val);   // one gather per hit
+            if constexpr (!VRING) load_packed<STRIDE>(pk, (unsigned)g.index, val);   // one gather per hit
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
               const bool ok = rg::f32_bits(val[f]) != RG_EXCLUDED_BITS;
@@ -285,9 +352,9 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
       // bounds of up to 64 cell rows with one vector load each (lane <-> cell row)
       int rs_l = 0, re_l = 0;
       if (rb + lane < nrows) {
-        const int base = lvl_off + (cy0 + rb + lane) * a.c.ncx;
-        rs_l = a.cell_start[base + cx0];
-        re_l = a.cell_start[base + cx1 + 1];
+        const int base = lvl_off + (cy0 + rb + lane) * c.ncx;
+        rs_l = cell_start[base + cx0];
+        re_l = cell_start[base + cx1 + 1];
       }
       const int nr = nrows - rb < 64 ? nrows - rb : 64;
       int row = -1, jb = 0, je = 0;
@@ -304,12 +371,12 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
       rg_gate4 gn;
       gn.x = gn.y = gn.z = 0.0f; gn.index = 0;
       bool vn = false;
-      if (have) { vn = jb + lane < je; if (vn) gn = a.sorted[jb + lane]; }
+      if (have) { vn = jb + lane < je; if (vn) gn = sorted[jb + lane]; }
       while (have) {
         const rg_gate4 g = gn;
         const bool valid = vn;
         have = advance();
-        if (have) { vn = jb + lane < je; if (vn) gn = a.sorted[jb + lane]; }  // prefetch the next step
+        if (have) { vn = jb + lane < je; if (vn) gn = sorted[jb + lane]; }  // prefetch the next step
         if constexpr (VRING) flush_pending();   // the values requested one step ago have had that step to arrive
         // lower bound of the distance to the nearest voxel of the block vs the block's largest (inflated) radius
         const float dz = g.z - zf;
@@ -324,7 +391,7 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
           if constexpr (VRING) {  // request the gate's field slots now, park them in the ring one step later
             pend = true;
             pend_pos = pos & (kRing - 1);
-            load_packed<STRIDE>(packed, (unsigned)g.index, pend_val);
+            load_packed<STRIDE>(pk, (unsigned)g.index, pend_val);
           }
         }
         tail += __popcll(m);
@@ -345,6 +412,7 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(SearchArgs a, con
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }   // visit: the radar's queue is empty
 
     if constexpr (MODE == kCountMode) {
       if (slot == 0 && vlive) counts[((size_t)iz * a.ny + (iy0 + byl)) * a.nx + (ix0 + b0 + bxl)] = cursor;
@@ -406,6 +474,29 @@ int dispatch(int nf, const SearchArgs& a, const float* packed, float fill, float
 
 inline int stride_for(int nf) { return nf == 1 ? 1 : nf == 2 ? 2 : nf <= 4 ? 4 : 8; }
 
+template <int W, int NF, int STRIDE>
+int launch_mosaic(const MosaicArgs& a, float fill, float* out, hipStream_t s) {
+  const long waves = (long)((a.nx + PX - 1) / PX) * ((a.ny + BY - 1) / BY) * a.nz;
+  hipLaunchKernelGGL((roi_block_kernel<kGridMode, W, NF, STRIDE, true>), dim3((unsigned)((waves + 3) / 4)),
+                     dim3(rg::kBlock), 0, s, a, (const float*)nullptr, fill, out, (int*)nullptr, (const long long*)nullptr,
+                     (int*)nullptr, (float*)nullptr);
+  return rg::check_launch("rg_roi_grid_mosaic_f32");
+}
+
+template <int W>
+int dispatch_mosaic(int nf, const MosaicArgs& a, float fill, float* out, hipStream_t s) {
+  switch (nf) {
+    case 1: return launch_mosaic<W, 1, 1>(a, fill, out, s);
+    case 2: return launch_mosaic<W, 2, 2>(a, fill, out, s);
+    case 3: return launch_mosaic<W, 3, 4>(a, fill, out, s);
+    case 4: return launch_mosaic<W, 4, 4>(a, fill, out, s);
+    case 5: return launch_mosaic<W, 5, 8>(a, fill, out, s);
+    case 6: return launch_mosaic<W, 6, 8>(a, fill, out, s);
+    case 7: return launch_mosaic<W, 7, 8>(a, fill, out, s);
+    default: return launch_mosaic<W, 8, 8>(a, fill, out, s);
+  }
+}
+
 }  // namespace
 
 extern "C" int rg_roi_grid_f32(const rg_gate4* sorted_gates, const int32_t* cell_start, const rg_cellgrid* cells_host,
@@ -433,6 +524,64 @@ extern "C" int rg_roi_grid_f32(const rg_gate4* sorted_gates, const int32_t* cell
     case RG_W_CRESSMAN: return dispatch<RG_W_CRESSMAN>(n_fields, a, packed, fill_value, out, s);
     case RG_W_CLOSEST: return dispatch<RG_W_CLOSEST>(n_fields, a, packed, fill_value, out, s);
     default: return dispatch<RG_W_NEAREST>(n_fields, a, packed, fill_value, out, s);
+  }
+}
+
+// Several radars on one grid: per radar, radar_grid/compute.py:46-91 in that radar's frame and radar_grid/interpolate.py:69-104
+// over the union of all radars' neighbours (a joint mean the reference does not have: it grids one radar per geometry).
+extern "C" int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_t n_radars, int32_t nz, int32_t ny,
+                                      int32_t nx, double min_radius, double beam_factor, int32_t weighting,
+                                      const float* packed, int32_t n_fields, int32_t stride, int64_t n_gates_total,
+                                      float fill_value, float* out, rg_stream_t stream) {
+  RG_REQUIRE(radars_host, RG_EINVAL, "rg_roi_grid_mosaic_f32: null radar table");
+  RG_REQUIRE(n_radars >= 1, RG_EINVAL, "rg_roi_grid_mosaic_f32: n_radars=%d", n_radars);
+  RG_REQUIRE(n_radars <= RG_MAX_RADARS, RG_EUNSUPPORTED, "rg_roi_grid_mosaic_f32: n_radars=%d exceeds %d", n_radars,
+             RG_MAX_RADARS);
+  RG_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1, RG_EINVAL, "rg_roi_grid_mosaic_f32: bad grid shape (%d,%d,%d)", nz, ny, nx);
+  RG_REQUIRE(packed && out, RG_EINVAL, "rg_roi_grid_mosaic_f32: null pointer");
+  RG_REQUIRE(weighting != RG_W_CLOSEST, RG_EUNSUPPORTED, "rg_roi_grid_mosaic_f32: the closest-gate mode is single-radar");
+  RG_REQUIRE(weighting >= RG_W_BARNES2 && weighting <= RG_W_NEAREST, RG_EINVAL,
+             "rg_roi_grid_mosaic_f32: unknown weighting %d", weighting);
+  RG_REQUIRE(n_fields >= 1 && n_fields <= RG_MAX_FIELDS, RG_EUNSUPPORTED,
+             "rg_roi_grid_mosaic_f32: n_fields=%d not in 1..%d", n_fields, RG_MAX_FIELDS);
+  RG_REQUIRE(stride == stride_for(n_fields), RG_EINVAL, "rg_roi_grid_mosaic_f32: stride=%d, expected %d for %d fields",
+             stride, stride_for(n_fields), n_fields);
+  RG_REQUIRE(rg::aligned16(packed), RG_EALIGN, "rg_roi_grid_mosaic_f32: packed must be 16-byte aligned");
+  // the gather takes a 32-bit slot number (rg::load_packed)
+  RG_REQUIRE(n_gates_total >= 0 && n_gates_total <= 0x7FFFFFFFL, RG_EUNSUPPORTED,
+             "rg_roi_grid_mosaic_f32: n_gates_total=%lld not in 0 .. 2^31 - 1", (long long)n_gates_total);
+  RG_REQUIRE((long)((nx + PX - 1) / PX) * ((ny + BY - 1) / BY) * nz < 0xFFFFFFF0L, RG_EUNSUPPORTED,
+             "rg_roi_grid_mosaic_f32: grid too large for one launch");
+  MosaicArgs a = {};
+  a.n_radars = n_radars;
+  a.nz = nz; a.ny = ny; a.nx = nx;
+  a.n_vox = (long)nz * ny * nx;
+  a.min_radius = min_radius; a.beam_factor = beam_factor;
+  for (int r = 0; r < n_radars; ++r) {
+    const rg_mosaic_radar& e = radars_host[r];
+    RG_REQUIRE(e.nx_win >= 0 && e.ny_win >= 0 && e.ix0 >= 0 && e.iy0 >= 0 && (long)e.ix0 + e.nx_win <= nx &&
+                   (long)e.iy0 + e.ny_win <= ny,
+               RG_EINVAL, "rg_roi_grid_mosaic_f32: radar %d: window x %d+%d, y %d+%d outside the %dx%d grid", r, e.ix0,
+               e.nx_win, e.iy0, e.ny_win, nx, ny);
+    // the kernel gathers packed[gate_offset + index] through a raw pointer: the offsets are what keep it in bounds
+    RG_REQUIRE(e.gate_offset >= 0 && e.n_gates >= 0 && e.gate_offset + e.n_gates <= n_gates_total, RG_EINVAL,
+               "rg_roi_grid_mosaic_f32: radar %d: gates %lld + %lld exceed n_gates_total=%lld", r,
+               (long long)e.gate_offset, (long long)e.n_gates, (long long)n_gates_total);
+    MosaicRadar& m = a.r[r];
+    if (e.nx_win == 0 || e.ny_win == 0) continue;           // reaches nothing: never visited, pointers not read
+    const int rc = check_search_args("rg_roi_grid_mosaic_f32", e.sorted_gates, e.cell_start, &e.cells, e.xc, e.yc, e.zc,
+                                     nz, e.ny_win, e.nx_win);
+    if (rc != RG_OK) return rc;
+    m.sorted = e.sorted_gates; m.cell_start = e.cell_start; m.c = to_cells(&e.cells);
+    m.xc = e.xc; m.yc = e.yc; m.zc = e.zc;
+    m.packed = packed + e.gate_offset * stride;
+    m.ix0 = e.ix0; m.iy0 = e.iy0; m.nxw = e.nx_win; m.nyw = e.ny_win;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  switch (weighting) {
+    case RG_W_BARNES2: return dispatch_mosaic<RG_W_BARNES2>(n_fields, a, fill_value, out, s);
+    case RG_W_CRESSMAN: return dispatch_mosaic<RG_W_CRESSMAN>(n_fields, a, fill_value, out, s);
+    default: return dispatch_mosaic<RG_W_NEAREST>(n_fields, a, fill_value, out, s);
   }
 }
 

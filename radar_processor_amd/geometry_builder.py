@@ -45,20 +45,34 @@ class RoiSearch:
 
     def __init__(self, gate_x, gate_y, gate_z, grid_shape, grid_limits, radar_altitude=0.0, min_radius=250.0,
                  beam_factor=0.01746, toa=17000.0, device=None, cell_size: Optional[float] = None,
-                 per_level: Optional[bool] = None):
+                 per_level: Optional[bool] = None, window: Optional[Tuple[int, int, int, int]] = None):
         """``per_level``: keep one cell-sorted gate list PER GRID LEVEL, each holding only the gates that can reach that level
         (``rg_geom_bin_gates_levels_f32``: |z_gate - z_level| within the largest radius of influence any neighbouring voxel of
         the gate can have) -- a voxel block then streams a third of the candidates.  Default: on where the bound holds
-        (0 <= beam_factor < 0.5) and the grid has more than one level; the neighbour sets are the same either way."""
+        (0 <= beam_factor < 0.5) and the grid has more than one level; the neighbour sets are the same either way.
+
+        ``window=(iy0, iy1, ix0, ix1)``: search only the columns ``iy0:iy1, ix0:ix1`` of the grid (all levels).  The coordinate
+        tables are SLICES of the whole grid's float32 linspace (a linspace of narrower limits rounds differently), the cell grid
+        is the whole grid's lattice (its origin and cell size) cropped to the cells the window's voxels can reach, and
+        ``grid_shape`` becomes the window's ``(nz, iy1 - iy0, ix1 - ix0)``: every kernel sees the window as its grid.  Every
+        gate keeps the cell it has in the whole grid's search, so a window voxel's CSR row holds the same pairs in the same order
+        as without the window.  ``full_shape`` keeps the grid's shape.  ``None``: the whole grid."""
         torch = _native.torch_mod()
         lib = _native.load_library()
         self.dev = _native.canonical_device(device)
-        self.grid_shape = tuple(int(s) for s in grid_shape)
+        self.grid_shape = self.full_shape = tuple(int(s) for s in grid_shape)
         self.grid_limits = grid_limits
         self.min_radius = float(min_radius)
         self.beam_factor = float(beam_factor)
         self.toa = toa
         nz, ny, nx = self.grid_shape
+        if window is not None:
+            iy0, iy1, ix0, ix1 = (int(v) for v in window)
+            if not (0 <= iy0 < iy1 <= ny and 0 <= ix0 < ix1 <= nx):
+                raise ValueError(f"window {tuple(window)} is empty or outside the {ny} x {nx} columns of the grid")
+            self.window = (iy0, iy1, ix0, ix1)
+        else:
+            self.window = (0, ny, 0, nx)
 
         gx = _as_device_f32(gate_x, self.dev)
         gy = _as_device_f32(gate_y, self.dev)
@@ -71,7 +85,6 @@ class RoiSearch:
         zc = np.linspace(grid_limits[0][0], grid_limits[0][1], nz, dtype="float32")
         yc = np.linspace(grid_limits[1][0], grid_limits[1][1], ny, dtype="float32")
         xc = np.linspace(grid_limits[2][0], grid_limits[2][1], nx, dtype="float32")
-        self.zc, self.yc, self.xc = (torch.from_numpy(c).to(self.dev) for c in (zc, yc, xc))
 
         # largest ROI over the grid (reached at a corner), padded so dropped gates provably cannot be neighbours
         far = math.sqrt(max(abs(float(xc.min())), abs(float(xc.max()))) ** 2
@@ -93,6 +106,12 @@ class RoiSearch:
         self.cell_size = cell_size
         ncx = max(1, int(math.ceil((x_hi - x_lo) / cell_size)))
         ncy = max(1, int(math.ceil((y_hi - y_lo) / cell_size)))
+        if window is not None:
+            yc, xc = yc[self.window[0]:self.window[1]], xc[self.window[2]:self.window[3]]
+            self.grid_shape = (nz, len(yc), len(xc))
+            ny, nx = len(yc), len(xc)
+            x_lo, y_lo, ncx, ncy = self._crop_cells(gx, gy, xc, yc, zc, x_lo, y_lo, ncx, ncy, cell_size)
+        self.zc, self.yc, self.xc = (torch.from_numpy(c).to(self.dev) for c in (zc, yc, xc))
         self.per_level = bool(want_levels and ncx * ncy * nz < 2 ** 31 - 1)
         self.cells = _native.CellGrid(x0=x_lo, y0=y_lo, inv_cx=1.0 / cell_size, inv_cy=1.0 / cell_size,
                                       z_lo=float(zc.min()) - r_max, z_hi=float(zc.max()) + r_max, ncx=ncx, ncy=ncy,
@@ -138,6 +157,33 @@ class RoiSearch:
                 _native.stream_ptr()), "rg_geom_bin_gates_f32")
             self.n_binned = int(self.cell_start[-1].item())
         del ws
+
+    def _crop_cells(self, gx, gy, xc, yc, zc, x_lo, y_lo, ncx, ncy, cell_size):
+        """The whole grid's cell lattice cropped to the cells a window voxel can reach: ``(x0, y0, ncx, ncy)``.  The crop's
+        origin is a lattice point; the binning kernel then puts every gate of the crop into the cell it has in the whole lattice
+        provided ``floor((g - x0) * inv)`` rounds as ``floor((g - x_lo) * inv) - k0`` -- checked here for every gate, in the
+        kernel's float64 arithmetic.  Where it does not hold (a gate on a cell boundary), the whole lattice is kept."""
+        far = math.sqrt(max(abs(float(xc.min())), abs(float(xc.max()))) ** 2
+                        + max(abs(float(yc.min())), abs(float(yc.max()))) ** 2
+                        + max(abs(float(zc.min())), abs(float(zc.max()))) ** 2)
+        reach = max(self.min_radius, far * abs(self.beam_factor)) * (1.0 + 1e-6) + 1.0   # as r_max, over the window
+        inv = 1.0 / cell_size
+
+        def crop(g, lo, n, c_lo, c_hi):
+            k0 = min(max(int(math.floor((c_lo - reach - lo) * inv)), 0), n - 1)
+            k1 = min(max(int(math.floor((c_hi + reach - lo) * inv)), 0), n - 1)
+            origin = lo + k0 * cell_size
+            g = g.detach().cpu().numpy().astype(np.float64)
+            whole = np.floor((g - lo) * inv)
+            inside = (whole >= k0) & (whole <= k1)
+            same = bool(np.array_equal(np.floor((g[inside] - origin) * inv), whole[inside] - k0))
+            return (origin, k1 - k0 + 1) if same else (lo, n)
+
+        x0, ncx_w = crop(gx, x_lo, ncx, float(xc.min()), float(xc.max()))
+        y0, ncy_w = crop(gy, y_lo, ncy, float(yc.min()), float(yc.max()))
+        if (x0 == x_lo and ncx_w != ncx) or (y0 == y_lo and ncy_w != ncy):
+            logger.info("window: a gate lies on a cell boundary of the cropped lattice; keeping the whole lattice")
+        return x0, y0, ncx_w, ncy_w
 
     def cells_from(self, level0: int):
         """The cell grid for a call that covers the levels from ``level0`` on (passing ``zc + level0``): per-level gate lists

@@ -597,11 +597,7 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
     lo, hi = gp._level_window(nz, *products.window, geometry)
     if products.columns and lo > hi:
         raise ValueError(f"empty level window [{lo}, {hi}]")
-    plans = {alt: gp.cappi_plan(geometry.grid_limits[0], nz, alt, products.interpolation) for alt in products.cappi}
-    for alt, plan in plans.items():
-        if plan[0] == "outside":
-            z_min, z_max = geometry.grid_limits[0]
-            gp.logger.warning(f"Altitude {alt}m is outside grid range [{z_min}, {z_max}]m")
+    plans = cappi_plans(products, geometry, nz)
     needed = sorted({k for plan in plans.values() if plan[0] != "outside" for k in ((plan[1], plan[1] + 1) if plan[0] == "blend"
                                                                                     else (plan[1],))})
     keep_lo, n_keep = (needed[0], needed[-1] - needed[0] + 1) if needed else (0, 0)
@@ -639,45 +635,77 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
             else:
                 grids = torch.empty((nf, nz, ny, nx), dtype=torch.float32, device=dev)
                 gridder.apply(grids.view(nf, -1), fill_value)
-                cmax = carg = None
-                level = (lambda k, z: grids[k, z])
             for k in range(nf):
+                if not run_fused:
+                    results.append(products_of_grid(products, grids[k], geometry, lo, hi, plans))
+                    continue
                 rec = {}
                 if products.colmax:
-                    if run_fused:
-                        rec["colmax"] = cmax[k]
-                        if products.argmax:
-                            rec["argmax"] = carg[k]
-                    else:
-                        got = gp._column("max", grids[k], lo, hi, None, None, None, want_arg=products.argmax)
-                        rec["colmax"], rec["argmax"] = got if products.argmax else (got, None)
-                        if not products.argmax:
-                            del rec["argmax"]
-                if run_fused:
-                    for key in ("colmin", "colmean"):
-                        if key in fused_planes:
-                            rec[key] = fused_planes[key][k]
-                else:
-                    reduce_planes(products, grids[k], geometry, lo, hi, rec)
-                    ppi_recs = rec.pop("ppi", None)
+                    rec["colmax"] = cmax[k]
+                    if products.argmax:
+                        rec["argmax"] = carg[k]
+                for key in ("colmin", "colmean"):
+                    if key in fused_planes:
+                        rec[key] = fused_planes[key][k]
                 if products.cappi:
-                    rec["cappi"] = {}
-                    for alt, plan in plans.items():
-                        if plan[0] == "outside":
-                            rec["cappi"][alt] = torch.full((ny, nx), float("nan"), dtype=torch.float32, device=dev)
-                        elif plan[0] == "level":
-                            rec["cappi"][alt] = level(k, plan[1])
-                        else:
-                            out = torch.empty((ny, nx), dtype=torch.float32, device=dev)
-                            lo_plane = level(k, plan[1])      # levels k and k + 1 are adjacent planes of one buffer
-                            _native.check(gridder.lib.rg_cappi_lerp_f32(_native.ptr(lo_plane), ny * nx, 0,
-                                                                        float(np.float32(plan[2])), float(np.float32(plan[3])),
-                                                                        _native.ptr(out), _native.stream_ptr()), "rg_cappi_lerp_f32")
-                            rec["cappi"][alt] = out
+                    rec["cappi"] = _cappi_planes(plans, lambda z: level(k, z), ny, nx, dev)
                 if products.ppi:
-                    rec["ppi"] = fused_planes["ppi"][k] if run_fused else ppi_recs
+                    rec["ppi"] = fused_planes["ppi"][k]
                 results.append(rec)
     return results
+
+
+def cappi_plans(products: PlaneProducts, geometry, nz: int) -> dict:
+    """``{altitude: cappi_plan}`` of a products request, warning about altitudes outside the grid as
+    ``constant_altitude_ppi`` does.  ``geometry``: anything with the grid's ``grid_limits``."""
+    from . import grid_products as gp
+    plans = {alt: gp.cappi_plan(geometry.grid_limits[0], nz, alt, products.interpolation) for alt in products.cappi}
+    for alt, plan in plans.items():
+        if plan[0] == "outside":
+            z_min, z_max = geometry.grid_limits[0]
+            gp.logger.warning(f"Altitude {alt}m is outside grid range [{z_min}, {z_max}]m")
+    return plans
+
+
+def _cappi_planes(plans: dict, level, ny: int, nx: int, dev) -> dict:
+    """The CAPPI planes of ``plans``; ``level(z)`` returns grid level ``z`` as a ``[ny, nx]`` plane (levels ``z`` and
+    ``z + 1`` adjacent in one buffer)."""
+    torch = _native.torch_mod()
+    lib = _native.load_library()
+    out = {}
+    for alt, plan in plans.items():
+        if plan[0] == "outside":
+            out[alt] = torch.full((ny, nx), float("nan"), dtype=torch.float32, device=dev)
+        elif plan[0] == "level":
+            out[alt] = level(plan[1])
+        else:
+            plane = torch.empty((ny, nx), dtype=torch.float32, device=dev)
+            _native.check(lib.rg_cappi_lerp_f32(_native.ptr(level(plan[1])), ny * nx, 0, float(np.float32(plan[2])),
+                                                float(np.float32(plan[3])), _native.ptr(plane), _native.stream_ptr()),
+                          "rg_cappi_lerp_f32")
+            out[alt] = plane
+    return out
+
+
+def products_of_grid(products: PlaneProducts, grid, geometry, lo: int, hi: int, plans: dict) -> dict:
+    """The planes ``grid_products_device`` returns for one field, from its stored grid ``[nz, ny, nx]`` (device) through the
+    separate kernels: ``column_argmax`` / ``column_max`` over levels ``lo .. hi``, ``reduce_planes``, the CAPPIs of ``plans``
+    (``cappi_plans``).  ``geometry``: anything with the grid's ``grid_shape`` / ``grid_limits``."""
+    from . import grid_products as gp
+    _, ny, nx = (int(s) for s in grid.shape)
+    rec = {}
+    if products.colmax:
+        got = gp._column("max", grid, lo, hi, None, None, None, want_arg=products.argmax)
+        rec["colmax"], rec["argmax"] = got if products.argmax else (got, None)
+        if not products.argmax:
+            del rec["argmax"]
+    reduce_planes(products, grid, geometry, lo, hi, rec)
+    ppi_recs = rec.pop("ppi", None)
+    if products.cappi:
+        rec["cappi"] = _cappi_planes(plans, lambda z: grid[z], ny, nx, grid.device)
+    if products.ppi:
+        rec["ppi"] = ppi_recs
+    return rec
 
 
 def _fused_planes_pass(gridder: CsrGridder, products: PlaneProducts, geometry: GridGeometry, fill_value, planes, keep_lo,

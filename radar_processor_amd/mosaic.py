@@ -1,0 +1,499 @@
+"""Several radars on one shared grid (mosaic).
+
+Each radar gives float32 gate coordinates relative to its antenna (what ``get_gate_coordinates`` returns) and its
+``origin = (oz, oy, ox)``: the antenna position in the grid frame, in metres, in the axis order of ``grid_limits``.  Gates
+are translated into the grid frame, not rotated or re-projected.
+
+Radar r's contribution to voxel v is row v of ``compute_grid_geometry(gx_r, gy_r, gz_r, grid_shape,
+mosaic_limits(grid_limits, o_r), ..., radar_altitude=0.0, toa=toa - oz_r)`` -- the reference's neighbour set and weights
+(``radar_grid/compute.py:46-91``) in that radar's frame.  The mosaic value of a voxel is the masked weighted mean
+(``radar_grid/interpolate.py:69-104``) over the union of every radar's neighbours::
+
+    sum_r sum_{live j} w_j * v_j / sum_r sum_{live j} w_j          (fill_value where the weight sum is not > 0)
+
+Radar r's gate g is gate ``gate_offsets[r] + g`` of the mosaic (radars concatenated in the order given), and row v of a
+mosaic geometry is radar 0's row v, then radar 1's, and so on.  With one radar at origin (0, 0, 0) the mosaic IS
+``compute_grid_geometry``.
+
+Two routes:
+
+* :func:`compute_mosaic_geometry` builds one reference-format CSR over the concatenated gates (the builder's count and
+  fill kernels, each radar over its reach window) and :func:`apply_mosaic` / :func:`mosaic_fields_device` grid through it
+  like any geometry -- for repeated volumes;
+* :class:`MosaicSearch` keeps one search structure per radar and :func:`mosaic_fields_device` grids straight from the gates
+  (``rg_roi_grid_mosaic_f32``) -- no CSR, any subset of the radars per call.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _native
+from .geometry_builder import WEIGHTINGS, RoiSearch
+from .grid_geometry import DeviceCSR, GridGeometry
+
+_INT32_MAX = 2 ** 31 - 1
+_GATHER_BYTES = 2 ** 32        # buffer-resource range of the packed-field gather in rg_csr_apply_f32
+
+
+def mosaic_limits(grid_limits, origin) -> Tuple[Tuple[float, float], ...]:
+    """The shared grid's limits in the frame of a radar at ``origin = (oz, oy, ox)`` (Python floats)."""
+    return tuple((float(lo) - float(o), float(hi) - float(o)) for (lo, hi), o in zip(grid_limits, origin))
+
+
+def _stride_for(n_fields: int) -> int:
+    return 1 if n_fields == 1 else 2 if n_fields == 2 else 4 if n_fields <= 4 else 8
+
+
+def _length(a) -> int:
+    """Element count of a NumPy array, torch tensor or sequence -- without touching a device."""
+    if hasattr(a, "numel"):
+        return int(a.numel())
+    if hasattr(a, "size") and not callable(a.size):
+        return int(a.size)
+    return len(a)
+
+
+def _host(a):
+    """A tensor (any device) -> NumPy; anything else as it is."""
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else a
+
+
+def _check_radars(radars, max_radars: Optional[int] = None):
+    """``[(gate_x, gate_y, gate_z, origin), ...]`` -> (gate counts, origins float64 [R, 3]); raises ValueError."""
+    radars = list(radars)
+    if not radars:
+        raise ValueError("a mosaic needs at least one radar")
+    if max_radars is not None and len(radars) > max_radars:
+        raise ValueError(f"{len(radars)} radars: one CSR-free mosaic launch takes at most {max_radars} "
+                         "(RG_MAX_RADARS); build a mosaic geometry instead")
+    counts, origins = [], []
+    for r, radar in enumerate(radars):
+        if len(radar) != 4:
+            raise ValueError(f"radar {r}: expected (gate_x, gate_y, gate_z, origin)")
+        gx, gy, gz, origin = radar
+        o = np.asarray(origin, dtype=np.float64)
+        if o.shape != (3,) or not np.all(np.isfinite(o)):
+            raise ValueError(f"radar {r}: origin must be three finite numbers (oz, oy, ox), got {origin!r}")
+        n = _length(gx)
+        if not (_length(gy) == _length(gz) == n):
+            raise ValueError(f"radar {r}: gate_x, gate_y and gate_z differ in length")
+        counts.append(n)
+        origins.append(o)
+    if sum(counts) > _INT32_MAX:
+        raise ValueError(f"{sum(counts)} gates in all: the mosaic numbers gates with int32 (at most 2^31 - 1)")
+    return counts, np.stack(origins)
+
+
+def _offsets(counts: Sequence[int]) -> np.ndarray:
+    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]).astype(np.int64)
+
+
+def reach_window(gate_x, gate_y, gate_z, grid_shape, grid_limits, origin, min_radius: float = 250.0,
+                 beam_factor: float = 0.01746, toa: float = 17000.0) -> Tuple[int, int, int, int]:
+    """The columns ``(iy0, iy1, ix0, ix1)`` (half-open) of the shared grid a radar can reach.
+
+    A valid gate (``gz <= toa - oz``) is a neighbour only of voxels within ``R_g = max(min_radius, bf * |g| / (1 - bf))`` of
+    it (the bound ``rg_geom_bin_levels_count`` uses: ``r_v = max(min_radius, |v| * bf)`` and ``|v| <= |g| + r_v``).  The
+    window holds the voxels whose coordinates -- the radar's own float32 tables of the shifted limits -- fall inside the
+    xy box of ``gate +- R_g``, widened by one voxel on each side and clipped to the grid.  ``iy0 == iy1``: the radar reaches
+    nothing.  ``beam_factor`` outside ``[0, 1)``: the whole grid.  Host code, float64; gate coordinates may be NumPy arrays or
+    tensors on any device (they are copied to the host)."""
+    nz, ny, nx = (int(s) for s in grid_shape)
+    if not (0.0 <= float(beam_factor) < 1.0):
+        return (0, ny, 0, nx)
+    lim = mosaic_limits(grid_limits, origin)
+    gx = np.asarray(_host(gate_x), dtype=np.float32).ravel().astype(np.float64)
+    gy = np.asarray(_host(gate_y), dtype=np.float32).ravel().astype(np.float64)
+    gz32 = np.asarray(_host(gate_z), dtype=np.float32).ravel()
+    valid = (gz32 <= np.float32(float(toa) - float(origin[0]))) & np.isfinite(gx) & np.isfinite(gy)
+    if not valid.any():
+        return (0, 0, 0, 0)
+    gx, gy, gz = gx[valid], gy[valid], gz32[valid].astype(np.float64)
+    bf = float(beam_factor)
+    reach = np.maximum(float(min_radius), bf * np.sqrt(gx * gx + gy * gy + gz * gz) / (1.0 - bf))
+    reach = reach * (1.0 + 1e-9) + 1e-6         # the bound is exact arithmetic; the float64 test rounds
+    yc = np.linspace(lim[1][0], lim[1][1], ny, dtype="float32").astype(np.float64)
+    xc = np.linspace(lim[2][0], lim[2][1], nx, dtype="float32").astype(np.float64)
+
+    def span(c, lo, hi):
+        idx = np.nonzero((c >= lo) & (c <= hi))[0]
+        if idx.size == 0:
+            return 0, 0
+        return max(int(idx.min()) - 1, 0), min(int(idx.max()) + 2, len(c))
+
+    iy0, iy1 = span(yc, float(np.min(gy - reach)), float(np.max(gy + reach)))
+    ix0, ix1 = span(xc, float(np.min(gx - reach)), float(np.max(gx + reach)))
+    if iy0 == iy1 or ix0 == ix1:
+        return (0, 0, 0, 0)
+    return (iy0, iy1, ix0, ix1)
+
+
+def _window_empty(w) -> bool:
+    return w[0] >= w[1] or w[2] >= w[3]
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# geometry route
+# ------------------------------------------------------------------------------------------------------------------------
+def compute_mosaic_geometry(radars, grid_shape, grid_limits, temp_dir: str, min_radius: float = 250.0,
+                            beam_factor: float = 0.01746, weighting: str = "barnes2", toa: float = 17000.0,
+                            n_workers: Optional[int] = None) -> GridGeometry:
+    """One reference-format geometry of several radars on one grid: row v is radar 0's row v of
+    ``compute_grid_geometry(..., mosaic_limits(grid_limits, o_r), radar_altitude=0.0, toa=toa - oz_r)``, then radar 1's, ...,
+    with radar r's gate g numbered ``gate_offsets[r] + g``.
+
+    ``radars``: a sequence of ``(gate_x, gate_y, gate_z, origin)``.  The result carries the shared ``grid_limits`` and
+    ``toa`` and, besides the reference's arrays, ``.gate_offsets`` (int64 ``[R + 1]``) and ``.origins`` (float64 ``[R, 3]``).
+    ``save_geometry`` writes the usual nine keys: a reloaded mosaic is a plain geometry over the concatenated gates (the
+    two mosaic attributes are not kept).  Geometries of 50 M pairs and more get the compact / packed device copy on their
+    first gridding pass like any other (``gridding._use_compact``); only the CSR layout is built here.  ``temp_dir`` and
+    ``n_workers`` as in ``compute_grid_geometry``."""
+    if not os.path.isdir(temp_dir):
+        raise ValueError(f"temp_dir does not exist: {temp_dir}")
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"Unknown weighting function: {weighting}")
+    radars = list(radars)
+    counts, origins = _check_radars(radars)
+    torch = _native.torch_mod()
+    lib = _native.load_library()
+    dev = _native.device()
+    nz, ny, nx = (int(s) for s in grid_shape)
+    n_vox = nz * ny * nx
+    offsets = _offsets(counts)
+    # per radar: its search over its reach window (None: reaches nothing)
+    parts = []
+    for r, (gx, gy, gz, origin) in enumerate(radars):
+        w = reach_window(gx, gy, gz, (nz, ny, nx), grid_limits, origins[r], min_radius, beam_factor, toa)
+        if _window_empty(w):
+            parts.append(None)
+            continue
+        search = RoiSearch(gx, gy, gz, (nz, ny, nx), mosaic_limits(grid_limits, origins[r]), radar_altitude=0.0,
+                           min_radius=min_radius, beam_factor=beam_factor, toa=float(toa) - float(origins[r][0]),
+                           device=dev, window=w)
+        parts.append(search)
+    with torch.cuda.device(dev):
+        stream = _native.stream_ptr()
+        total = torch.zeros(n_vox + 1, dtype=torch.int32, device=dev)
+        grid_counts = total[:n_vox].view(nz, ny, nx)
+        win_counts = []
+        for search in parts:
+            if search is None:
+                win_counts.append(None)
+                continue
+            _, wy, wx = search.grid_shape
+            cnt = torch.zeros(nz * wy * wx, dtype=torch.int32, device=dev)
+            _native.check(lib.rg_geom_count_f32(
+                _native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(search.xc),
+                _native.ptr(search.yc), _native.ptr(search.zc), nz, wy, wx, search.min_radius, search.beam_factor,
+                _native.ptr(cnt), stream), "rg_geom_count_f32")
+            iy0, iy1, ix0, ix1 = search.window
+            grid_counts[:, iy0:iy1, ix0:ix1] += cnt.view(nz, wy, wx)
+            win_counts.append(cnt)
+        indptr = torch.empty(n_vox + 1, dtype=torch.int64, device=dev)
+        ws_bytes = int(lib.rg_scan_workspace_bytes(n_vox))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _native.check(lib.rg_scan_counts_i64(_native.ptr(total), n_vox, _native.ptr(indptr), _native.ptr(ws), ws_bytes,
+                                             stream), "rg_scan_counts_i64")
+        del ws, total
+        n_pairs = int(indptr[-1].item())
+        gate_idx = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)[:n_pairs]
+        weights = torch.empty(max(n_pairs, 1), dtype=torch.float32, device=dev)[:n_pairs]
+        # running cursor: indptr plus the counts of the radars already filled.  The fill kernel reads only cursor[v] as the
+        # row base and writes at absolute positions, so every radar fills its segment of each row of its window.
+        cursor = indptr[:n_vox].view(nz, ny, nx).clone()
+        for r, search in enumerate(parts):
+            if search is None or n_pairs == 0:
+                continue
+            _, wy, wx = search.grid_shape
+            iy0, iy1, ix0, ix1 = search.window
+            cur_w = cursor[:, iy0:iy1, ix0:ix1].contiguous()
+            # the radar's gate numbers carry its offset: shift the index column of this build's copy of its sorted gates
+            search.sorted_gates.view(torch.int32).view(-1, 4)[:, 3] += int(offsets[r])
+            _native.check(lib.rg_geom_fill_f32(
+                _native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(search.xc),
+                _native.ptr(search.yc), _native.ptr(search.zc), nz, wy, wx, search.min_radius, search.beam_factor,
+                _native.WEIGHTINGS[weighting], _native.ptr(cur_w), _native.ptr(gate_idx), _native.ptr(weights), stream),
+                "rg_geom_fill_f32")
+            cursor[:, iy0:iy1, ix0:ix1] += win_counts[r].view(nz, wy, wx)
+        del cursor, parts
+        if n_pairs <= _INT32_MAX:
+            indptr = indptr.to(torch.int32)
+        max_gate = int(gate_idx.max().item()) if n_pairs else -1
+    geom = GridGeometry.from_device((nz, ny, nx), grid_limits, DeviceCSR(indptr, gate_idx, weights, max_gate), toa)
+    geom.gate_offsets = offsets
+    geom.origins = origins
+    return geom
+
+
+def _mosaic_layout(geometry) -> np.ndarray:
+    offsets = getattr(geometry, "gate_offsets", None)
+    if offsets is None:
+        raise ValueError("not a mosaic: the geometry has no gate_offsets (built by compute_mosaic_geometry)")
+    return np.asarray(offsets, dtype=np.int64)
+
+
+def _host_concat(offsets, fields, filters, what: str):
+    """Per-radar masked fields (+ per-radar GateFilter lists) -> concatenated float32 values and uint8 exclusion mask."""
+    from .gridding import _coerce_filters, _host_field
+    n_radars = len(offsets) - 1
+    if len(fields) != n_radars:
+        raise ValueError(f"{what}: expected one field per radar ({n_radars}), got {len(fields)}")
+    if filters is None:
+        filters = [None] * n_radars
+    if len(filters) != n_radars:
+        raise ValueError(f"{what}: expected one filter list per radar ({n_radars}), got {len(filters)}")
+    values, masks = [], []
+    for r in range(n_radars):
+        n = int(offsets[r + 1] - offsets[r])
+        if _length(np.ma.getdata(fields[r])) != n:
+            raise ValueError(f"{what}: radar {r} has {n} gates, its field {_length(np.ma.getdata(fields[r]))}")
+        v, m = _host_field(fields[r], _coerce_filters(filters[r]))
+        values.append(v)
+        masks.append(m)
+    return np.concatenate(values), np.concatenate(masks)
+
+
+def apply_mosaic(geometry: GridGeometry, fields: Sequence, additional_filters: Optional[Sequence] = None,
+                 fill_value: float = np.nan) -> np.ndarray:
+    """Grid one field of every radar through a mosaic geometry: ``fields[r]`` is radar r's (masked) field in the reference
+    format, ``additional_filters[r]`` a list of ``GateFilter`` of radar r.  Returns a float32 grid of
+    ``geometry.grid_shape``."""
+    offsets = _mosaic_layout(geometry)
+    values, mask = _host_concat(offsets, list(fields), additional_filters, "apply_mosaic")
+    _check_gather(int(offsets[-1]), 1)
+    from .gridding import _to_host, grid_fields_device
+    torch = _native.torch_mod()
+    dev = _native.device()
+    f_t = torch.from_numpy(values).to(dev)
+    m_t = torch.from_numpy(mask).to(dev) if mask.any() else None
+    grid = grid_fields_device(geometry, [f_t], [m_t], fill_value=fill_value)
+    return _to_host(grid[0]).reshape(geometry.grid_shape)
+
+
+def apply_mosaic_multi(geometry: GridGeometry, fields: Dict[str, Sequence],
+                       additional_filters: Optional[Dict[str, Sequence]] = None,
+                       fill_value: float = np.nan) -> Dict[str, np.ndarray]:
+    """Several fields of every radar in one pass: ``fields[name][r]`` radar r's field, ``additional_filters[name][r]`` its
+    filter list (a missing name: no filters)."""
+    offsets = _mosaic_layout(geometry)
+    if additional_filters is None:
+        additional_filters = {}
+    names = list(fields.keys())
+    if not names:
+        return {}
+    host = [_host_concat(offsets, list(fields[n]), additional_filters.get(n), f"apply_mosaic_multi[{n}]") for n in names]
+    _check_gather(int(offsets[-1]), len(names))
+    from .gridding import _to_host, grid_fields_device
+    torch = _native.torch_mod()
+    dev = _native.device()
+    f_ts = [torch.from_numpy(v).to(dev) for v, _ in host]
+    m_ts = [torch.from_numpy(m).to(dev) if m.any() else None for _, m in host]
+    grid = _to_host(grid_fields_device(geometry, f_ts, m_ts, fill_value=fill_value))
+    return {name: grid[i].reshape(geometry.grid_shape) for i, name in enumerate(names)}
+
+
+def _check_gather(n_gates_total: int, n_fields: int) -> None:
+    """The geometry route gathers packed fields through a 32-bit buffer resource (rg_csr_apply_f32)."""
+    stride = _stride_for(min(n_fields, _native.RG_MAX_FIELDS))
+    if n_gates_total * stride * 4 >= _GATHER_BYTES:
+        raise ValueError(f"{n_gates_total} gates x {stride} packed slots x 4 bytes reach 4 GiB: too many gates for one "
+                         "pass of the geometry route (use a MosaicSearch, or fewer fields per call)")
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# CSR-free route
+# ------------------------------------------------------------------------------------------------------------------------
+class MosaicSearch:
+    """One :class:`RoiSearch` per radar, each restricted to that radar's reach window (:func:`reach_window`), for
+    ``rg_roi_grid_mosaic_f32``.  Radar r's search is ``None`` when it reaches no voxel.  Attributes: ``grid_shape``,
+    ``grid_limits``, ``origins`` (float64 ``[R, 3]``), ``n_gates`` (per radar), ``windows``, ``searches``."""
+
+    def __init__(self, radars, grid_shape, grid_limits, min_radius: float = 250.0, beam_factor: float = 0.01746,
+                 toa: float = 17000.0, device=None):
+        radars = list(radars)
+        counts, origins = _check_radars(radars, max_radars=_native.RG_MAX_RADARS)
+        self.grid_shape = tuple(int(s) for s in grid_shape)
+        if len(self.grid_shape) != 3 or min(self.grid_shape) < 1:
+            raise ValueError(f"bad grid shape {grid_shape}")
+        self.grid_limits = grid_limits
+        self.min_radius = float(min_radius)
+        self.beam_factor = float(beam_factor)
+        self.toa = toa
+        self.origins = origins
+        self.n_gates = [int(c) for c in counts]
+        self.dev = _native.canonical_device(device)
+        self.windows, self.searches = [], []
+        for r, (gx, gy, gz, _) in enumerate(radars):
+            w = reach_window(gx, gy, gz, self.grid_shape, grid_limits, origins[r], min_radius, beam_factor, toa)
+            self.windows.append(w)
+            self.searches.append(None if _window_empty(w) else RoiSearch(
+                gx, gy, gz, self.grid_shape, mosaic_limits(grid_limits, origins[r]), radar_altitude=0.0,
+                min_radius=min_radius, beam_factor=beam_factor, toa=float(toa) - float(origins[r][0]), device=self.dev,
+                window=w))
+
+    @property
+    def n_radars(self) -> int:
+        return len(self.searches)
+
+    def table(self, radars: Sequence[int], offsets: Sequence[int]):
+        """The ``rg_mosaic_radar`` table of the selected radars, radar ``radars[k]`` at packed offset ``offsets[k]``."""
+        table = (_native.MosaicRadar * len(radars))()
+        for k, r in enumerate(radars):
+            e = table[k]
+            e.gate_offset, e.n_gates = int(offsets[k]), self.n_gates[r]
+            s = self.searches[r]
+            if s is None:
+                continue                                          # nx_win = ny_win = 0: never visited
+            iy0, iy1, ix0, ix1 = s.window
+            e.sorted_gates, e.cell_start, e.cells = _native.ptr(s.sorted_gates), _native.ptr(s.cell_start), s.cells
+            e.xc, e.yc, e.zc = _native.ptr(s.xc), _native.ptr(s.yc), _native.ptr(s.zc)
+            e.ix0, e.iy0, e.nx_win, e.ny_win = ix0, iy0, ix1 - ix0, iy1 - iy0
+        return table
+
+
+def _check_device_inputs(fields, masks, shared_masks, counts, n_fields, torch, dev):
+    for r, n in enumerate(counts):
+        for f, t in enumerate(fields[r]):
+            if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError(f"radar {r} field {f}: expected a contiguous cuda float32 tensor on {dev}")
+        for f, m in enumerate(list(masks[r]) + [shared_masks[r]]):
+            if m is not None and not (m.is_cuda and m.device == dev and m.dtype == torch.uint8 and m.is_contiguous()):
+                raise ValueError(f"radar {r} mask {f}: expected a contiguous cuda uint8 tensor on {dev}")
+
+
+def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Sequence] = None,
+                         shared_masks: Optional[Sequence] = None, weighting: str = "barnes2", fill_value: float = np.nan,
+                         products=None, radars: Optional[Sequence[int]] = None):
+    """Grid device-resident fields of several radars onto the shared grid.
+
+    ``target``: a mosaic ``GridGeometry`` (:func:`compute_mosaic_geometry`) or a :class:`MosaicSearch`.
+    ``fields[k][f]``: cuda float32 tensor of field f of the k-th radar of the call; ``masks[k][f]`` optional uint8 tensors
+    (``1`` = excluded), ``shared_masks[k]`` one optional uint8 QC mask of that radar.  ``radars``: which radars of a
+    ``MosaicSearch`` the call holds, in that order (default: all) -- any subset; for a geometry it must be all of them, in
+    order (its gate numbering is fixed).  ``weighting`` applies to the search route only (a geometry carries its weights).
+
+    Returns ``[F, nz, ny, nx]`` float32, or with a ``PlaneProducts`` what ``grid_products_device`` returns: the geometry
+    route goes through ``grid_products_device`` itself (``fused=True`` planes come out of its epilogue), the search route
+    grids, then reduces with the separate kernels.  Every argument is validated before the device is touched."""
+    is_geometry = isinstance(target, GridGeometry)
+    if not is_geometry and not isinstance(target, MosaicSearch):
+        raise TypeError("target must be a mosaic GridGeometry or a MosaicSearch")
+    if is_geometry:
+        offsets = _mosaic_layout(target)
+        n_all = len(offsets) - 1
+        all_counts = [int(offsets[r + 1] - offsets[r]) for r in range(n_all)]
+        if radars is not None and list(radars) != list(range(n_all)):
+            raise ValueError("a mosaic geometry grids all of its radars, in order (its gate numbering is fixed)")
+        sel = list(range(n_all))
+    else:
+        if weighting not in WEIGHTINGS:
+            raise ValueError(f"Unknown weighting function: {weighting} (the mosaic has no closest-gate mode)")
+        n_all = target.n_radars
+        all_counts = target.n_gates
+        sel = list(range(n_all)) if radars is None else [int(r) for r in radars]
+        if not sel or len(set(sel)) != len(sel) or not all(0 <= r < n_all for r in sel):
+            raise ValueError(f"radars must be distinct indices of the {n_all} radars, got {radars!r}")
+    counts = [all_counts[r] for r in sel]
+    fields = [list(f) for f in fields]
+    if len(fields) != len(sel):
+        raise ValueError(f"expected the fields of {len(sel)} radars, got {len(fields)}")
+    n_fields = len(fields[0]) if fields else 0
+    if n_fields == 0:
+        raise ValueError("no fields to grid")
+    masks = [[None] * n_fields for _ in sel] if masks is None else [list(m) for m in masks]
+    shared_masks = [None] * len(sel) if shared_masks is None else list(shared_masks)
+    if len(masks) != len(sel) or len(shared_masks) != len(sel):
+        raise ValueError(f"masks and shared_masks need one entry per radar ({len(sel)})")
+    for k, n in enumerate(counts):
+        if len(fields[k]) != n_fields:
+            raise ValueError(f"radar {sel[k]}: {len(fields[k])} fields, radar {sel[0]} has {n_fields}")
+        if len(masks[k]) != n_fields:
+            raise ValueError(f"radar {sel[k]}: masks must have one entry (tensor or None) per field")
+        for f, t in enumerate(fields[k]):
+            if _length(t) != n:
+                raise ValueError(f"radar {sel[k]} field {f}: {_length(t)} values for {n} gates")
+        for f, m in enumerate(list(masks[k]) + [shared_masks[k]]):
+            if m is not None and _length(m) != n:
+                raise ValueError(f"radar {sel[k]} mask {f}: {_length(m)} values for {n} gates")
+    n_total = sum(counts)
+    if n_total > _INT32_MAX:
+        raise ValueError(f"{n_total} gates in all: the mosaic numbers gates with int32 (at most 2^31 - 1)")
+    if is_geometry:
+        _check_gather(n_total, n_fields)
+
+    torch = _native.torch_mod()
+    dev = fields[0][0].device
+    if dev.type != "cuda":
+        raise _native.NativeUnavailable("mosaic_fields_device needs device-resident (cuda) tensors")
+    if not is_geometry and dev != target.dev:
+        raise ValueError(f"the fields are on {dev}, the MosaicSearch on {target.dev}")
+    _check_device_inputs(fields, masks, shared_masks, counts, n_fields, torch, dev)
+
+    with torch.cuda.device(dev):
+        def cat_masks(pick):
+            got = [pick(k) for k in range(len(sel))]
+            if all(m is None for m in got):
+                return None
+            return torch.cat([m if m is not None else torch.zeros(counts[k], dtype=torch.uint8, device=dev)
+                              for k, m in enumerate(got)])
+        cat_fields = [torch.cat([fields[k][f] for k in range(len(sel))]) for f in range(n_fields)]
+        cat_field_masks = [cat_masks(lambda k, f=f: masks[k][f]) for f in range(n_fields)]
+        cat_shared = cat_masks(lambda k: shared_masks[k])
+        if is_geometry:
+            from .gridding import grid_fields_device, grid_products_device
+            if products is not None:
+                return grid_products_device(target, cat_fields, cat_field_masks, cat_shared, products=products,
+                                            fill_value=fill_value)
+            return grid_fields_device(target, cat_fields, cat_field_masks, cat_shared, fill_value=fill_value)
+        grids = _search_grid(target, sel, counts, cat_fields, cat_field_masks, cat_shared, weighting, fill_value, dev)
+    if products is not None:
+        return _products_of_grids(products, grids, target)
+    return grids
+
+
+def _search_grid(search: MosaicSearch, sel, counts, fields, masks, shared_mask, weighting, fill_value, dev):
+    torch = _native.torch_mod()
+    lib = _native.load_library()
+    nz, ny, nx = search.grid_shape
+    n_vox = nz * ny * nx
+    n_fields = len(fields)
+    n_total = sum(counts)
+    offsets = _offsets(counts)[:-1]
+    table = search.table(sel, offsets)
+    out = torch.empty((n_fields, nz, ny, nx), dtype=torch.float32, device=dev)
+    fill = float(np.float32(fill_value))
+    stream = _native.stream_ptr()
+    for f0 in range(0, n_fields, _native.RG_MAX_FIELDS):
+        group = list(range(f0, min(n_fields, f0 + _native.RG_MAX_FIELDS)))
+        nf = len(group)
+        stride = _stride_for(nf)
+        packed = torch.empty(max(n_total, 1) * stride, dtype=torch.float32, device=dev)
+        fptrs = (ctypes.c_void_p * nf)(*[_native.ptr(fields[i]) for i in group])
+        mptrs = (ctypes.c_void_p * nf)(*[_native.ptr(masks[i]) for i in group])
+        _native.check(lib.rg_pack_fields_f32(nf, fptrs, mptrs, _native.ptr(shared_mask), n_total, stride,
+                                             _native.ptr(packed), stream), "rg_pack_fields_f32")
+        out_view = out.view(n_fields, n_vox)[f0:f0 + nf]
+        _native.check(lib.rg_roi_grid_mosaic_f32(
+            table, len(sel), nz, ny, nx, search.min_radius, search.beam_factor, _native.WEIGHTINGS[weighting],
+            _native.ptr(packed), nf, stride, n_total, fill, _native.ptr(out_view), stream), "rg_roi_grid_mosaic_f32")
+    return out
+
+
+def _products_of_grids(products, grids, spec) -> List[dict]:
+    """The planes ``grid_products_device`` returns, from stored grids ``[F, nz, ny, nx]`` through the separate kernels
+    (``gridding.products_of_grid``; ``spec``: anything with the shared ``grid_shape`` / ``grid_limits``)."""
+    from . import grid_products as gp
+    from .gridding import cappi_plans, products_of_grid
+    torch = _native.torch_mod()
+    nz = int(spec.grid_shape[0])
+    lo, hi = gp._level_window(nz, *products.window, spec)
+    if products.columns and lo > hi:
+        raise ValueError(f"empty level window [{lo}, {hi}]")
+    plans = cappi_plans(products, spec, nz)
+    with torch.cuda.device(grids.device):
+        return [products_of_grid(products, grids[k], spec, lo, hi, plans) for k in range(grids.shape[0])]
