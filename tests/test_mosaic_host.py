@@ -9,8 +9,10 @@ import re
 import numpy as np
 import pytest
 
+import mosaic_scenes
 import radar_processor_amd as rg
 from conftest import GOLDEN, REPO, assert_same_to_rounding, load_golden
+from mosaic_scenes import concat_rows  # noqa: F401  (shared with tests/test_gpu_mosaic.py)
 from oracle import radar_grid_oracle as oracle
 from radar_processor_amd import _native, synthetic
 
@@ -46,23 +48,6 @@ def fixture_masks(meta, vols, name):
             extra = [oracle.gate_mask("below", np.ma.getdata(vol.fields[meta["qc"][0]]), meta["qc"][1])]
         out.append(oracle.merge_masks(vol.fields[name], extra))
     return out
-
-
-def concat_rows(csrs, offsets):
-    """Row v: radar 0's row v, then radar 1's, ... with gate numbers shifted by the radar's offset."""
-    counts = [np.diff(np.asarray(ip, dtype=np.int64)) for ip, _, _ in csrs]
-    indptr = np.concatenate([[0], np.cumsum(np.sum(counts, axis=0))]).astype(np.int64)
-    idx = np.empty(int(indptr[-1]), dtype=np.int32)
-    w = np.empty(int(indptr[-1]), dtype=csrs[0][2].dtype)
-    base = indptr[:-1].copy()
-    for r, (ip, gi, wt) in enumerate(csrs):
-        ip = np.asarray(ip, dtype=np.int64)
-        rows = np.repeat(np.arange(len(ip) - 1), counts[r])
-        dest = base[rows] + (np.arange(len(gi)) - ip[rows])
-        idx[dest] = np.asarray(gi, dtype=np.int64) + offsets[r]
-        w[dest] = wt
-        base += counts[r]
-    return indptr, idx, w
 
 
 def oracle_mosaic(vols, origins, shape, limits, weighting, toa, exact_weights=False, min_radius=250.0,
@@ -346,6 +331,91 @@ def test_mosaic_entry_point_argument_validation():
     # ... an entry that reaches nothing does not: its pointers are never read
     assert _mosaic([_entry(nx_win=0, sorted_gates=0, cell_start=0, xc=0), bad]) == _native.RG_EINVAL
     assert b"exceed n_gates_total" in lib.rg_last_error()
+
+
+def test_validation_of_the_last_slot_of_a_full_table():
+    """A 16-entry table (RG_MAX_RADARS) whose slot 15 alone is refused -- its window outside the grid, or its gates past
+    n_gates_total: the call fails before any launch and names radar 15 (the checks run over every slot, the last one
+    included)."""
+    lib = rg.load_library(require_device=False)
+    assert _native.RG_MAX_RADARS == 16
+    good = [_entry(gate_offset=k % 3, n_gates=7) for k in range(15)]
+    for last, what in ((_entry(ix0=1), b"outside the"), (_entry(iy0=3, ny_win=2), b"outside the"),
+                       (_entry(gate_offset=5, n_gates=6), b"exceed n_gates_total"),
+                       (_entry(nx_win=0, gate_offset=9, n_gates=2, sorted_gates=0, xc=0), b"exceed n_gates_total")):
+        assert _mosaic(good + [last]) == _native.RG_EINVAL
+        msg = lib.rg_last_error()
+        assert b"radar 15:" in msg and what in msg, msg
+
+
+# ---- 6. many radars: the seeded scenes of tests/mosaic_scenes.py --------------------------------------------------------
+@pytest.mark.parametrize("name", ["scene16", "scene20"])
+def test_many_radar_scene_properties(name):
+    """The scenes exercise what they are built for (mosaic_scenes.check_properties): 16 / 20 radars, a voxel reached by
+    >= 8 of them, >= 100 oracle pairs from every live radar, window left edges on >= 8 residues mod 16 and all 4 mod 4,
+    every grid face touched, inert radars at slots 0 and 7 and a live one at slot 15, a radar reaching levels below its
+    antenna and one whose gates cross its toa - oz cut."""
+    scene = getattr(mosaic_scenes, name)()
+    assert scene.n_radars == {"scene16": 16, "scene20": 20}[name]
+    assert scene.shape[1] % 4 and scene.shape[2] % 16                  # ragged against the 16 x 4 patch
+    got = mosaic_scenes.check_properties(scene)
+    print(name, got)
+
+
+@pytest.mark.parametrize("name", ["scene16", "scene20"])
+def test_reach_window_is_conservative_on_the_scenes(name):
+    """No voxel with an oracle neighbour of radar r lies outside radar r's reach window; an empty window means no pairs."""
+    scene = getattr(mosaic_scenes, name)()
+    for r in range(scene.n_radars):
+        w = scene.window(r)
+        ip = scene.csr(r)[0]
+        if w == (0, 0, 0, 0):
+            assert ip[-1] == 0, r
+            continue
+        outside, inside = _rows_outside(ip, scene.shape, w)
+        assert outside == 0, (r, w, outside)
+
+
+def _extra_placements():
+    """Seeded placements around the scene grid: just outside each face (x, y, below the bottom), antennas above the grid
+    top and above toa, for beam factors 0.01746, 0 and 0.05 and minimum radii 250 and 1500."""
+    rng = np.random.default_rng(77)
+    (z0, z1), (y0, y1), (x0, x1) = mosaic_scenes.LIMITS
+    out = []
+    for k in range(10):
+        d = float(rng.uniform(2e3, 12e3))
+        oy, ox = float(rng.uniform(y0, y1)), float(rng.uniform(x0, x1))
+        oz = float(rng.uniform(0.0, 3000.0))
+        origin = [(oz, oy, x0 - d), (oz, oy, x1 + d), (oz, y0 - d, ox), (oz, y1 + d, ox), (z0 - d / 4, oy, ox),
+                  (z1 + d / 10, oy, ox), (mosaic_scenes.TOA + d / 10, oy, ox), (oz, y1 + d, x0 - d), (oz, oy, ox),
+                  (oz, y0 - d, x1 + d)][k]
+        bf = (0.01746, 0.0, 0.05)[k % 3]
+        mr = (250.0, 1500.0)[k % 2]
+        spec = mosaic_scenes.RadarSpec(seed=300 + k, max_range_m=float(rng.uniform(18e3, 28e3)), origin=origin)
+        out.append((spec, bf, mr))
+    return out
+
+
+def test_reach_window_is_conservative_for_extra_placements():
+    shape, limits, toa = mosaic_scenes.SHAPE, mosaic_scenes.LIMITS, mosaic_scenes.TOA
+    n_empty = n_cut = 0
+    for spec, bf, mr in _extra_placements():
+        v = mosaic_scenes.volume(spec)
+        w = rg.reach_window(v.gate_x, v.gate_y, v.gate_z, shape, limits, spec.origin, mr, bf, toa)
+        ip, _, _ = oracle.build_geometry(v.gate_x, v.gate_y, v.gate_z, shape, rg.mosaic_limits(limits, spec.origin),
+                                         min_radius=mr, beam_factor=bf, weighting="nearest", toa=toa - spec.origin[0])
+        if w == (0, 0, 0, 0):
+            assert ip[-1] == 0, (spec, bf, mr)
+            n_empty += 1
+            continue
+        outside, inside = _rows_outside(ip, shape, w)
+        assert outside == 0, (spec, bf, mr, w, outside)
+        n_cut += inside > 0 and (w[1] - w[0] < shape[1] or w[3] - w[2] < shape[2])
+        # a beam factor outside [0, 1): the whole grid
+        for bad in (1.0, -0.01, 2.5):
+            assert rg.reach_window(v.gate_x, v.gate_y, v.gate_z, shape, limits, spec.origin, mr, bad, toa) == \
+                (0, shape[1], 0, shape[2])
+    assert n_empty >= 2 and n_cut >= 5, (n_empty, n_cut)
 
 
 def test_fixtures_are_small_and_complete():
