@@ -290,6 +290,30 @@ int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_t n_radars,
                            rg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Vertical cross-section along any path: K2's arithmetic at n_points sample columns (xs[i], ys[i]) -- float32 metres in
+ * the radar frame, device pointers; not necessarily equally spaced, sorted or distinct -- times the nz levels of zc.
+ * Sample (k, i) is what radar_grid/compute.py:46-91 + radar_grid/interpolate.py:69-104 would put into a voxel lying exactly
+ * at (xs[i], ys[i], zc[k]); out is float32 [n_fields][nz][n_points], row k * n_points + i the row order of a grid of shape
+ * (nz, 1, n_points).  The search structure is the one of the lattice entry points; every point must lie inside the xy
+ * rectangle it was built for (the caller checks: the points are device memory).  A point with a non-finite coordinate
+ * has no neighbours.  Weights of rg_roi_section_f32 as rg_roi_grid_f32's (same budgets); rg_section_count_f32 /
+ * rg_section_fill_f32 are the builder passes (row lengths; gate index and float64-exact weight rounded to float32, as
+ * rg_geom_fill_f32 writes them; rg_scan_counts_i64 in between).  RG_W_CLOSEST is not supported (RG_EUNSUPPORTED).
+ * ------------------------------------------------------------------------------------------------- */
+int rg_roi_section_f32(const rg_gate4* sorted_gates, const int32_t* cell_start, const rg_cellgrid* cells_host,
+                       const float* xs, const float* ys, const float* zc, int32_t nz, int32_t n_points,
+                       double min_radius, double beam_factor, int32_t weighting,
+                       const float* packed, int32_t n_fields, int32_t stride, float fill_value, float* out,
+                       rg_stream_t stream);
+int rg_section_count_f32(const rg_gate4* sorted_gates, const int32_t* cell_start, const rg_cellgrid* cells_host,
+                         const float* xs, const float* ys, const float* zc, int32_t nz, int32_t n_points,
+                         double min_radius, double beam_factor, int32_t* counts, rg_stream_t stream);
+int rg_section_fill_f32(const rg_gate4* sorted_gates, const int32_t* cell_start, const rg_cellgrid* cells_host,
+                        const float* xs, const float* ys, const float* zc, int32_t nz, int32_t n_points,
+                        double min_radius, double beam_factor, int32_t weighting, const int64_t* indptr,
+                        int32_t* gate_idx, float* weights, rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * (f)3  processor-style collapse of the cached 3-D grid to the 2-D product plane:
  * radar_processor/processor.py:480-551 (collapse_grid_to_2d) and radar_processor/utils.py:336-387
  * (collapse_field_3d_to_2d).  'cappi' (nearest level, :530-533) and 'colmax' (:534-535) are

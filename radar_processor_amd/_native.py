@@ -143,6 +143,13 @@ SIGNATURES = {
                                   c_float, c_void_p, c_void_p]),
     "rg_roi_grid_mosaic_f32": (c_int32, [POINTER(MosaicRadar), c_int32, c_int32, c_int32, c_int32, c_double, c_double,
                                          c_int32, c_void_p, c_int32, c_int32, c_int64, c_float, c_void_p, c_void_p]),
+    "rg_roi_section_f32": (c_int32, [c_void_p, c_void_p, POINTER(CellGrid), c_void_p, c_void_p, c_void_p, c_int32,
+                                     c_int32, c_double, c_double, c_int32, c_void_p, c_int32, c_int32, c_float, c_void_p,
+                                     c_void_p]),
+    "rg_section_count_f32": (c_int32, [c_void_p, c_void_p, POINTER(CellGrid), c_void_p, c_void_p, c_void_p, c_int32,
+                                       c_int32, c_double, c_double, c_void_p, c_void_p]),
+    "rg_section_fill_f32": (c_int32, [c_void_p, c_void_p, POINTER(CellGrid), c_void_p, c_void_p, c_void_p, c_int32,
+                                      c_int32, c_double, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rg_collapse_ppi_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double,
                                       c_double, c_void_p, c_void_p, c_void_p]),
     "rg_plane_filter_f32": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(PlaneTest), c_int32, c_void_p, c_void_p,

@@ -28,6 +28,7 @@ SOURCES = [
     ("rg_products.hip", []),
     ("rg_geometry.hip", []),
     ("rg_roi_grid.hip", []),
+    ("rg_roi_section.hip", []),
     ("rg_raster.hip", []),
 ]
 

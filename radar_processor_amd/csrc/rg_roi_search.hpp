@@ -42,6 +42,21 @@ struct SearchArgs {
   double min_radius, beam_factor;
 };
 
+// A vertical section (rg_roi_section.hip): n_points sample columns at arbitrary (xs[i], ys[i]) times the nz levels of zc.
+// The search structure is the lattice's own: its cell lists and bounds do not depend on where the samples lie, as long as
+// they lie inside the rectangle the structure was built for.
+struct SectionArgs {
+  const rg_gate4* sorted;
+  const int* cell_start;
+  Cells c;
+  const float* xs;
+  const float* ys;
+  const float* zc;
+  int nz, n_points;
+  long n_samples;      // nz * n_points
+  double min_radius, beam_factor;
+};
+
 template <int W>
 __device__ __forceinline__ float roi_weight(double d2, double r2) {
   if constexpr (W == RG_W_BARNES2) {

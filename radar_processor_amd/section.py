@@ -1,0 +1,225 @@
+"""A vertical cross-section along any path, gridded straight from the gates (csrc/rg_roi_section.hip).
+
+The reference's ``radar_grid`` can cut a finished 3-D grid along one grid row or column (``plot_vertical_cross_section``,
+``mpl_visualization.py:343-435``: ``grid[:, y_index, :]``).  Here a *section* is ``n_points`` sample columns
+``(xs[i], ys[i])`` -- anywhere inside the grid's rectangle, at any spacing -- times the ``nz`` levels of a
+:class:`RoiSearch`, and the value at level ``k``, point ``i`` is what the reference would put into a voxel lying exactly
+there (``radar_grid/compute.py:46-91`` with ``radar_grid/interpolate.py:69-104``): the weighted mean of the gates within
+that point's radius of influence, not a resampling of the lattice.
+
+Two routes, as for the lattice: :func:`section_fields_device` grids without a CSR (one pass, nothing kept);
+:func:`compute_section_geometry` keeps the section's CSR as an ordinary :class:`GridGeometry` of shape
+``(nz, 1, n_points)`` for repeated volumes.  :func:`section_path` samples a polyline; :func:`vertical_section` is the
+NumPy-in / NumPy-out convenience.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _native
+from .geometry_builder import _INT32_MAX, WEIGHTINGS, RoiSearch
+from .grid_geometry import DeviceCSR, GridGeometry
+from .gridding import _coerce_filters, _host_field, _stride_for, _to_host
+
+
+def section_path(vertices, spacing: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Sample the polyline through ``vertices`` (``[(x, y), ...]``, metres) every ``spacing`` metres of path length:
+    ``s_j = j * spacing`` for ``j = 0 .. floor(L / spacing)``, ``L`` the polyline's length.  The position is interpolated
+    linearly inside its segment in float64 and rounded to float32.  Returns ``(xs float32, ys float32, s float64)``; the
+    last vertex is a sample only where ``L`` is a multiple of ``spacing``."""
+    v = np.asarray(vertices, dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 2 or v.shape[0] < 2:
+        raise ValueError("vertices must be at least two (x, y) pairs")
+    spacing = float(spacing)
+    if not np.all(np.isfinite(v)) or not math.isfinite(spacing):
+        raise ValueError("vertices and spacing must be finite")
+    if not spacing > 0.0:
+        raise ValueError(f"spacing must be positive, not {spacing}")
+    seg = np.hypot(np.diff(v[:, 0]), np.diff(v[:, 1]))
+    if np.any(seg == 0.0):
+        raise ValueError(f"segment {int(np.argmin(seg))} of the path has zero length")
+    cum = np.concatenate([[0.0], np.cumsum(seg)])
+    s = np.arange(int(math.floor(cum[-1] / spacing)) + 1, dtype=np.float64) * spacing
+    k = np.clip(np.searchsorted(cum, s, side="right") - 1, 0, len(seg) - 1)      # the segment a sample lies in
+    t = (s - cum[k]) / seg[k]
+    xs = v[k, 0] + t * (v[k + 1, 0] - v[k, 0])
+    ys = v[k, 1] + t * (v[k + 1, 1] - v[k, 1])
+    return xs.astype(np.float32), ys.astype(np.float32), s
+
+
+def section_rectangle(search) -> Tuple[float, float, float, float]:
+    """``(x_min, x_max, y_min, y_max)`` of the sample points a search structure serves: the xy rectangle of its
+    ``grid_limits`` -- the ends of its float32 coordinate tables -- and for a windowed search the window's coordinate
+    range.  The cell lattice and the padding by the largest radius of influence are proven only there.  Host arithmetic:
+    the tables are NumPy's float32 ``linspace`` (``compute.py:185-186``), recomputed here rather than read back."""
+    _, ny, nx = search.full_shape
+    iy0, iy1, ix0, ix1 = search.window
+    yc = np.linspace(search.grid_limits[1][0], search.grid_limits[1][1], ny, dtype="float32")[iy0:iy1]
+    xc = np.linspace(search.grid_limits[2][0], search.grid_limits[2][1], nx, dtype="float32")[ix0:ix1]
+    return float(xc.min()), float(xc.max()), float(yc.min()), float(yc.max())
+
+
+def _check_points(search, xs, ys, weighting: str):
+    """The points as contiguous float32 host arrays, refused (``ValueError``) before anything touches the device."""
+    if weighting == "closest":
+        raise ValueError("weighting 'closest' is a single-radar lattice mode; a section takes barnes2, cressman or nearest")
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"Unknown weighting function: {weighting}")
+    if type(xs).__module__.startswith("torch"):
+        xs = xs.detach().cpu().numpy()
+    if type(ys).__module__.startswith("torch"):
+        ys = ys.detach().cpu().numpy()
+    xs = np.ascontiguousarray(xs, dtype=np.float32)
+    ys = np.ascontiguousarray(ys, dtype=np.float32)
+    if xs.ndim != 1 or ys.ndim != 1 or xs.shape != ys.shape:
+        raise ValueError(f"xs and ys must be one-dimensional and of equal length, not {xs.shape} and {ys.shape}")
+    if xs.size == 0:
+        raise ValueError("a section needs at least one point (n_points == 0)")
+    if not (np.all(np.isfinite(xs)) and np.all(np.isfinite(ys))):
+        raise ValueError("xs and ys must be finite (NaN or infinite coordinate)")
+    x0, x1, y0, y1 = section_rectangle(search)
+    bad = (xs < x0) | (xs > x1) | (ys < y0) | (ys > y1)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"point {i} = ({xs[i]}, {ys[i]}) lies outside the rectangle x [{x0}, {x1}], y [{y0}, {y1}] the "
+                         f"search was built for ({int(bad.sum())} of {xs.size} points do)")
+    return xs, ys
+
+
+def _cumulative_distance(xs: np.ndarray, ys: np.ndarray) -> float:
+    x, y = xs.astype(np.float64), ys.astype(np.float64)
+    return float(np.hypot(np.diff(x), np.diff(y)).sum())
+
+
+def section_fields_device(search: RoiSearch, xs, ys, fields: Sequence, masks: Optional[Sequence] = None, shared_mask=None,
+                          weighting: str = "barnes2", fill_value: float = np.nan, out=None):
+    """Grid device-resident fields at the columns ``(xs[i], ys[i])`` straight from the gates, without a CSR.  ``xs`` /
+    ``ys``: float32 metres in the radar frame (the frame of the gate coordinates), inside the search's rectangle
+    (:func:`section_rectangle`); they need not be equally spaced, sorted or distinct -- only the speed depends on
+    consecutive points being close.  ``fields`` / ``masks`` / ``shared_mask`` / ``fill_value`` / ``out`` as
+    :func:`roi_grid_fields_device`.  Returns ``[F, nz, n_points]`` float32."""
+    xs, ys = _check_points(search, xs, ys, weighting)
+    n_fields = len(fields)
+    if n_fields == 0:
+        raise ValueError("no fields to grid")
+    torch = _native.torch_mod()
+    dev = search.dev
+    n_gates = search.n_gates
+    for i, f in enumerate(fields):
+        if not (f.is_cuda and f.device == dev and f.dtype == torch.float32 and f.is_contiguous()
+                and f.numel() == n_gates):
+            raise ValueError(f"field {i}: expected a contiguous float32 tensor of {n_gates} gates on {dev}")
+    if masks is None:
+        masks = [None] * n_fields
+    if len(masks) != n_fields:
+        raise ValueError("masks must have one entry (tensor or None) per field")
+    for i, m in enumerate(list(masks) + [shared_mask]):
+        if m is not None and not (m.is_cuda and m.device == dev and m.dtype == torch.uint8 and m.is_contiguous()
+                                  and m.numel() == n_gates):
+            raise ValueError(f"mask {i}: expected a contiguous uint8 tensor of {n_gates} gates on {dev}")
+    nz, n_points = search.grid_shape[0], int(xs.size)
+    n_samples = nz * n_points
+    if out is not None and not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous()
+                                and out.numel() == n_fields * n_samples):
+        # the kernel writes n_fields * nz * n_points floats through a raw pointer: anything else is an out-of-bounds write
+        raise ValueError(f"out must be a contiguous float32 tensor of shape [F, nz, n_points] on {dev}")
+    lib = _native.load_library()
+    if out is None:
+        out = torch.empty((n_fields, nz, n_points), dtype=torch.float32, device=dev)
+    fill = float(np.float32(fill_value))
+    with torch.cuda.device(dev):
+        stream = _native.stream_ptr()
+        xs_t, ys_t = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
+        for f0 in range(0, n_fields, _native.RG_MAX_FIELDS):
+            group = list(range(f0, min(n_fields, f0 + _native.RG_MAX_FIELDS)))
+            nf = len(group)
+            stride = _stride_for(nf)
+            packed = torch.empty(max(n_gates, 1) * stride, dtype=torch.float32, device=dev)
+            fptrs = (ctypes.c_void_p * nf)(*[_native.ptr(fields[i]) for i in group])
+            mptrs = (ctypes.c_void_p * nf)(*[_native.ptr(masks[i]) for i in group])
+            _native.check(lib.rg_pack_fields_f32(nf, fptrs, mptrs, _native.ptr(shared_mask), n_gates, stride,
+                                                 _native.ptr(packed), stream), "rg_pack_fields_f32")
+            out_view = out.view(n_fields, n_samples)[f0:f0 + nf]
+            _native.check(lib.rg_roi_section_f32(
+                _native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(xs_t),
+                _native.ptr(ys_t), _native.ptr(search.zc), nz, n_points, search.min_radius, search.beam_factor,
+                _native.WEIGHTINGS[weighting], _native.ptr(packed), nf, stride, fill, _native.ptr(out_view), stream),
+                "rg_roi_section_f32")
+    return out.view(n_fields, nz, n_points)
+
+
+def compute_section_geometry(search: RoiSearch, xs, ys, weighting: str = "barnes2") -> GridGeometry:
+    """The section's CSR as an ordinary geometry: ``grid_shape (nz, 1, n_points)``, row ``k * n_points + i`` holding the
+    gates within the radius of influence of ``(xs[i], ys[i], z_k)`` and their weights (float64-exact, rounded to float32,
+    as ``compute_grid_geometry`` writes them).  It goes through ``apply_geometry`` / ``apply_geometry_multi`` /
+    ``grid_fields_device`` / ``save_geometry`` like any geometry -- the route for repeated volumes.  ``grid_limits`` are
+    ``(z_limits, (0.0, 0.0), (0.0, s_last))`` with ``s_last`` the cumulative point-to-point distance; the points
+    themselves are kept as ``.section_x`` / ``.section_y`` (``save_geometry`` writes the reference's nine keys only)."""
+    xs, ys = _check_points(search, xs, ys, weighting)
+    torch = _native.torch_mod()
+    lib = _native.load_library()
+    dev = search.dev
+    nz, n_points = search.grid_shape[0], int(xs.size)
+    n_rows = nz * n_points
+    with torch.cuda.device(dev):
+        stream = _native.stream_ptr()
+        xs_t, ys_t = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
+        head = (_native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(xs_t),
+                _native.ptr(ys_t), _native.ptr(search.zc), nz, n_points, search.min_radius, search.beam_factor)
+        counts = torch.zeros(n_rows + 1, dtype=torch.int32, device=dev)
+        _native.check(lib.rg_section_count_f32(*head, _native.ptr(counts), stream), "rg_section_count_f32")
+        indptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        ws_bytes = int(lib.rg_scan_workspace_bytes(n_rows))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _native.check(lib.rg_scan_counts_i64(_native.ptr(counts), n_rows, _native.ptr(indptr), _native.ptr(ws), ws_bytes,
+                                             stream), "rg_scan_counts_i64")
+        n_pairs = int(indptr[-1].item())
+        del counts, ws
+        gate_idx = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)[:n_pairs]
+        weights = torch.empty(max(n_pairs, 1), dtype=torch.float32, device=dev)[:n_pairs]
+        if n_pairs:
+            _native.check(lib.rg_section_fill_f32(*head, _native.WEIGHTINGS[weighting], _native.ptr(indptr),
+                                                  _native.ptr(gate_idx), _native.ptr(weights), stream),
+                          "rg_section_fill_f32")
+        if n_pairs <= _INT32_MAX:
+            indptr = indptr.to(torch.int32)       # the reference's dtype (compute.py:232) whenever it fits
+        max_gate = int(gate_idx.max().item()) if n_pairs else -1
+    z_limits = tuple(float(v) for v in search.grid_limits[0])
+    geom = GridGeometry.from_device((nz, 1, n_points), (z_limits, (0.0, 0.0), (0.0, _cumulative_distance(xs, ys))),
+                                    DeviceCSR(indptr, gate_idx, weights, max_gate), search.toa)
+    geom.section_x, geom.section_y = xs, ys
+    return geom
+
+
+def vertical_section(gate_x, gate_y, gate_z, field_data, vertices, spacing, z_limits, nz, additional_filters=None,
+                     radar_altitude=0.0, min_radius=250.0, beam_factor=0.01746, weighting="barnes2", toa=17000.0,
+                     fill_value=np.nan):
+    """One masked field on the vertical section along the polyline ``vertices`` sampled every ``spacing`` metres
+    (:func:`section_path`), ``nz`` levels over ``z_limits``; the gridding arguments as ``compute_grid_geometry`` and
+    ``apply_geometry``.  Returns ``(section float32 [nz, n_points], s float64 [n_points])``.
+
+    The search structure is built for the bounding box of the float32 sample points themselves, so every sample lies
+    inside its rectangle by construction (a path along an axis gives a rectangle of zero width, which is legal)."""
+    xs, ys, s = section_path(vertices, spacing)
+    nz = int(nz)
+    if nz < 1:
+        raise ValueError(f"nz must be at least 1, not {nz}")
+    if weighting == "closest":
+        raise ValueError("weighting 'closest' is a single-radar lattice mode; a section takes barnes2, cressman or nearest")
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"Unknown weighting function: {weighting}")
+    values, mask = _host_field(field_data, _coerce_filters(additional_filters))
+    limits = (tuple(float(v) for v in z_limits), (float(ys.min()), float(ys.max())), (float(xs.min()), float(xs.max())))
+    search = RoiSearch(gate_x, gate_y, gate_z, (nz, 2, 2), limits, radar_altitude=radar_altitude, min_radius=min_radius,
+                       beam_factor=beam_factor, toa=toa)
+    if values.size != search.n_gates:
+        raise ValueError(f"field_data has {values.size} values for {search.n_gates} gates")
+    torch = _native.torch_mod()
+    f_t = torch.from_numpy(values).to(search.dev)
+    m_t = torch.from_numpy(mask).to(search.dev) if mask.any() else None
+    out = section_fields_device(search, xs, ys, [f_t], [m_t], weighting=weighting, fill_value=fill_value)
+    return _to_host(out[0]), s
