@@ -26,6 +26,10 @@ inline int check_launch(const char* what) {
 constexpr int kWave = 64;        // CDNA4 wavefront
 constexpr int kBlock = 256;      // 4 waves per workgroup
 
+// float32 slots per gate of the packed fields (rg_pack_fields_f32) for a pass of nf fields: the gather is one 4-, 8- or
+// 16-byte load, or two of 16
+constexpr int stride_for(int nf) { return nf == 1 ? 1 : nf == 2 ? 2 : nf <= 4 ? 4 : 8; }
+
 __device__ __forceinline__ uint32_t f32_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
 __device__ __forceinline__ float bits_f32(uint32_t v) { return __builtin_bit_cast(float, v); }
 

@@ -119,8 +119,7 @@ __device__ __forceinline__ Segment chunk_segment(const ChunkGrid& g, unsigned ch
   return s;
 }
 
-
-constexpr int stride_for(int nf) { return nf == 1 ? 1 : nf == 2 ? 2 : nf <= 4 ? 4 : 8; }
+using rg::stride_for;
 
 bool make_chunk_grid(int64_t n_rows, int64_t line_len, int64_t lines_per_plane, ChunkGrid* cg) {
   if (line_len <= 0) line_len = n_rows > 0 ? n_rows : 1;

@@ -273,7 +273,7 @@ int dispatch(int nf, int variant, const void* indptr, const int32_t* gidx, const
 #undef RG_KD
 }
 
-inline int stride_for(int nf) { return nf == 1 ? 1 : nf == 2 ? 2 : nf <= 4 ? 4 : 8; }
+using rg::stride_for;
 
 }  // namespace
 

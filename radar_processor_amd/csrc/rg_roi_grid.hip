@@ -18,20 +18,16 @@
 //     candidates regardless of the block size; survivors are compacted with ballot + mbcnt into a per-wave LDS ring;
 //   * dense stage (lanes = 16 voxels x 4 queued records per step): lane k owns voxel k of the block -- its
 //     constants live in its registers, its sums never leave it -- and tests 4 records per step (LDS broadcast
-//     reads).  float32 d2 decides membership whenever it is clear of the rim by 2e-6; inside that band the lane
-//     falls back to the reference's exact float64 `d2 < r2` (compute.py:69-74), so the neighbour set equals the
-//     CSR builder's.  Barnes and uniform weights in float32 (Barnes |rel err| < 2e-6 against compute.py's float64
-//     weight, uniform exact); the Cressman numerator r2 - d2 from the float64 d2 (from the float32 d2 it cancels at
-//     the rim: a hit there could weigh 0 or less), its denominator in float32 (|rel err| < 5e-7).  These budgets are
-//     the delta of the per-voxel error bound (oracle.mean_error_bound) every grid of this kernel is tested against, and
-//     are observed directly by tests/test_gpu_mean_bounds.py's two-gate probes (worst measured: Barnes 5.1e-7,
-//     Cressman 1.6e-7, uniform 0).  The packed field slots of a gate are fetched once,
+//     reads).  The membership rule (float32 d2 where it is clear of the rim, the reference's float64 `d2 < r2` inside the
+//     band, so the neighbour set equals the CSR builder's), the weights and their error budgets, and what the builder
+//     modes do with a hit are rg_roi_search.hpp's (in_roi, grid_weight, emit_hit, accumulate), shared with the section
+//     kernel and explained there.  The packed field slots of a gate are fetched once,
 //     when the gate is queued, and parked in a second LDS ring one candidate step later; the dense stage reads
 //     records and values from LDS one step ahead of its arithmetic;
 //   * per block two wavefront shuffles fold the 4 record slots; 16 lanes store 16 consecutive voxels per field.
 //
 // Compiled with -ffp-contract=off like every TU (the exact test must not be fused); the float32 tests use explicit
-// fmaf, their error is covered by the 2e-6 band.
+// fmaf, their error is covered by the rim band (rg_roi_search.hpp).
 #include "rg_common.hpp"
 #include "rg_roi_search.hpp"
 
@@ -45,36 +41,7 @@ constexpr int kRingBuild = 128, kRingGrid = 256;
 
 using rg::load_packed;
 
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)b, lane);
-  const unsigned hi = __builtin_amdgcn_readlane((unsigned)(b >> 32), lane);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
-
-// float32 weight from the float32 d2 (compute.py:82-87): Barnes (>= e^-4 inside the ROI) and uniform; relative error
-// < 2e-6 (d2f and inv_r2q carry a few u each; 2^x turns the exponent's absolute error, up to 5.8 * 6u, into a relative
-// one of ln 2 times that).  Not Cressman, whose numerator r2 - d2 cancels near the rim (grid mode takes it from the float64 d2).
-// inv_r2q: Barnes -- MINUS log2(e) * 4 / r2, so that exp(-d2 / (r2 / 4)) is one multiply and one v_exp_f32 (= 2^x)
-template <int W>
-__device__ __forceinline__ float weight_from_f32(float d2f, float r2f, float inv_r2q) {
-  if constexpr (W == RG_W_BARNES2) {
-    return __builtin_amdgcn_exp2f(d2f * inv_r2q) + 1e-5f;
-  } else if constexpr (W == RG_W_CRESSMAN) {
-    return (r2f - d2f) / (r2f + d2f);
-  } else {
-    return 1.0f;
-  }
-}
-
-// What the dense stage does with a (record, voxel) hit:
-//   kGridMode   accumulate the masked weighted mean (rg_roi_grid_f32)
-//   kCountMode  count it                            (rg_geom_count_f32: row lengths of the CSR)
-//   kFillMode   append (gate index, float64-exact weight) to the voxel's CSR row (rg_geom_fill_f32)
-// Count and fill classify hits with the same code, so the second pass writes exactly what the first one counted; a
-// voxel's hits arrive in (cell row, sorted position) order, the row order the CSR has always had.
-constexpr int kGridMode = 0, kCountMode = 1, kFillMode = 2;
+// The modes of the dense stage (kGridMode / kCountMode / kFillMode) are rg_roi_search.hpp's.
 
 // Block shape: BX x BY = 16 voxels per block (BY rows of BX consecutive voxels); a wavefront walks 4 blocks side by side in
 // x.  With one gate list for all levels 8 x 2 measured best (16.0 ms on the bench grid against 16.5 for 4 x 4 and 19.4 for
@@ -106,6 +73,19 @@ struct MosaicArgs {
 // MOSAIC (grid mode only): a voxel block visits every radar whose window meets it, in table order, runs the search of that
 // radar over its lists and coordinates and adds its hits into the block's one set of accumulators; the radar's queue is
 // drained before the next radar starts, so a radar's candidates never move another radar's slot assignment.
+template <int NF, int STRIDE>
+__device__ __forceinline__ void keep_closest(float d2f, int index, const float (&val)[STRIDE], float (&acc_p)[NF],
+                                             float (&acc_w)[NF], int (&best_idx)[NF]) {
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    const bool ok = rg::f32_bits(val[f]) != RG_EXCLUDED_BITS;
+    const bool better = ok && (d2f < acc_w[f] || (d2f == acc_w[f] && index < best_idx[f]));
+    acc_p[f] = better ? val[f] : acc_p[f];
+    acc_w[f] = better ? d2f : acc_w[f];
+    best_idx[f] = better ? index : best_idx[f];
+  }
+}
+
 template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false>
 __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_t<MOSAIC, MosaicArgs, SearchArgs> a,
                                                                const float* __restrict__ packed, float fill,
@@ -155,13 +135,12 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
   const float *xc, *yc;
   const float* pk;
   double z;                                                      // common to the whole wave
-  float zf, ylo, yhi;
+  float ylo, yhi;
   int lvl_off;
   if constexpr (!MOSAIC) {
     sorted = a.sorted; cell_start = a.cell_start; c = a.c; xc = a.xc; yc = a.yc; pk = packed;
     z = (double)a.zc[iz];
     lvl_off = c.levels > 1 ? (c.level0 + iz) * (c.ncx * c.ncy) : 0;   // per-level gate lists: this level's cells
-    zf = (float)z;                                               // grid coordinates ARE float32 values: exact
     const float ya = yc[iy0], yb = yc[iy0 + nvy - 1];
     ylo = fminf(ya, yb); yhi = fmaxf(ya, yb);
   }
@@ -206,7 +185,6 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
       sorted = R.sorted; cell_start = R.cell_start; c = R.c; xc = R.xc; yc = R.yc; pk = R.packed;
       z = (double)R.zc[iz];
       lvl_off = c.levels > 1 ? (c.level0 + iz) * (c.ncx * c.ncy) : 0;
-      zf = (float)z;
       const float ya = yc[yv0 - wy0], yb = yc[yv1 - wy0];
       ylo = fminf(ya, yb); yhi = fmaxf(ya, yb);
     }
@@ -219,26 +197,13 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
       x = (double)xc[ix0 + b0 + (vlive ? bxl : 0)];
       y = (double)yc[iy0 + (vlive ? byl : 0)];
     }
-    const double dist = sqrt(x * x + y * y + z * z);
-    const double r = fmax(a.min_radius, dist * a.beam_factor);
-    const double r2 = r * r;
-    const float xf = (float)x, yf = (float)y, r2f = (float)r2;
-    // float32 d2 carries < 4e-7 relative error: outside [r2_lo, r2_hi] the float32 comparison is already exact
-    const float r2_hi = live ? (float)(r2 * (1.0 + 2e-6)) * (1.0f + 2.4e-7f) : -1.0f;
-    const float r2_lo = live ? (float)(r2 * (1.0 - 2e-6)) * (1.0f - 2.4e-7f) : -1.0f;  // dead lanes never hit
-    const float inv_r2q = (float)(-1.4426950408889634 * 4.0 / r2);      // see weight_from_f32
+    const Sample s = make_sample(x, y, z, live, a.min_radius, a.beam_factor);
     // ---- block-wide (wave-uniform) quantities ------------------------------------------------------------
-    double rmax = live ? r : 0.0;
-#pragma unroll
-    for (int m = 1; m < kVB; m <<= 1) rmax = fmax(rmax, __shfl_xor(rmax, m, 64));
-    rmax = readlane_f64(rmax, 0);
+    const double rmax = block_max_radius<kVB>(s, live);
     const float xa = xc[xv0 - wx0], xb = xc[xv1 - wx0];
     const float xlo = fminf(xa, xb), xhi = fmaxf(xa, xb);
-    const float r2max_hi = (float)(rmax * rmax * (1.0 + 2e-6)) * (1.0f + 2.4e-7f);
-    const int cx0 = __builtin_amdgcn_readfirstlane(cell_clamped((double)xlo - rmax, c.x0, c.inv_cx, c.ncx));
-    const int cx1 = __builtin_amdgcn_readfirstlane(cell_clamped((double)xhi + rmax, c.x0, c.inv_cx, c.ncx));
-    const int cy0 = __builtin_amdgcn_readfirstlane(cell_clamped((double)ylo - rmax, c.y0, c.inv_cy, c.ncy));
-    const int cy1 = __builtin_amdgcn_readfirstlane(cell_clamped((double)yhi + rmax, c.y0, c.inv_cy, c.ncy));
+    const float r2max_hi = band_hi(rmax * rmax);
+    const CellBox box = cell_box(xlo, xhi, ylo, yhi, rmax, c);
 
     auto dense = [&](int n) {  // test n queued records against the block's 16 voxels, 4 records per step
       // value-ring variant: the next step's record and field slots are read from LDS before this step's arithmetic,
@@ -267,61 +232,19 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
             if constexpr (VPACK) val_nx[0] = __builtin_bit_cast(float, g_nx.index);
             else load_packed<STRIDE>(ringv, (unsigned)((head + e + kSlots) & (kRing - 1)), val_nx);
           }
-          const float dx = g.x - xf, dy = g.y - yf, dz = g.z - zf;
-          d2f = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-          in = e < n && d2f <= r2_lo;
-          if (e < n && !in && d2f <= r2_hi) {  // within 2e-6 of the rim: the reference's float64 arithmetic decides
-            const double ex = (double)g.x - x, ey = (double)g.y - y, ez = (double)g.z - z;  // compute.py:69-71
-            in = ex * ex + ey * ey + ez * ez < r2;                                          // compute.py:72,74
-          }
+          in = in_roi(g, s, e < n, d2f);
         } else if (e < n) {
           g = ring[(head + e) & (kRing - 1)];
-          const float dx = g.x - xf, dy = g.y - yf, dz = g.z - zf;
-          d2f = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-          in = d2f <= r2_lo;
-          if (!in && d2f <= r2_hi) {  // within 2e-6 of the rim: the reference's float64 arithmetic decides
-            const double ex = (double)g.x - x, ey = (double)g.y - y, ez = (double)g.z - z;  // compute.py:69-71
-            in = ex * ex + ey * ey + ez * ez < r2;                                          // compute.py:72,74
-          }
+          in = in_roi(g, s, true, d2f);
         }
         if constexpr (MODE != kGridMode) {
-          const unsigned long long hits = __ballot(in);   // executed by every lane of the wave
-          if constexpr (MODE == kFillMode) {
-            if (in) {
-              const double ex = (double)g.x - x, ey = (double)g.y - y, ez = (double)g.z - z;
-              const double d2 = ex * ex + ey * ey + ez * ez;                                // compute.py:72
-              const long long pos = row_base + cursor + __popcll(hits & lower_slots);
-              gidx[pos] = g.index;
-              wts[pos] = roi_weight<W>(d2, r2);                                             // compute.py:82-87
-            }
-          }
-          cursor += __popcll(hits & vox_lanes);
-        } else {
-          if (in) {
-            float w;
-            if constexpr (W == RG_W_CRESSMAN) {
-              // (r2 - d2) / (r2 + d2), compute.py:85: the numerator cancels at the rim -- from the float32 d2 it can be 0 or
-              // negative for a gate the float64 test admitted.  Numerator from the reference's float64 d2 (unfused, as the
-              // test: r2 - d2 > 0 for every hit), rounded once; denominator in float32 (no cancellation): |rel err| < 5e-7
-              const double ex = (double)g.x - x, ey = (double)g.y - y, ez = (double)g.z - z;
-              w = (float)(r2 - (ex * ex + ey * ey + ez * ez)) / (r2f + d2f);                // compute.py:72,85
-            } else {
-              w = weight_from_f32<W>(d2f, r2f, inv_r2q);
-            }
-            if constexpr (!VRING) load_packed<STRIDE>(pk, (unsigned)g.index, val);   // one gather per hit
-#pragma unroll
-            for (int f = 0; f < NF; ++f) {
-              const bool ok = rg::f32_bits(val[f]) != RG_EXCLUDED_BITS;
-              if constexpr (CLOSEST) {
-                const bool better = ok && (d2f < acc_w[f] || (d2f == acc_w[f] && g.index < best_idx[f]));
-                acc_p[f] = better ? val[f] : acc_p[f];
-                acc_w[f] = better ? d2f : acc_w[f];
-                best_idx[f] = better ? g.index : best_idx[f];
-              } else {
-                acc_p[f] += ok ? w * val[f] : 0.0f;  // float32 product, as interpolate.py:82
-                acc_w[f] += ok ? w : 0.0f;
-              }
-            }
+          emit_hit<MODE, W>(in, g, s, vox_lanes, lower_slots, row_base, cursor, gidx, wts);
+        } else if (in) {
+          if constexpr (!VRING) load_packed<STRIDE>(pk, (unsigned)g.index, val);   // one gather per hit
+          if constexpr (CLOSEST) {
+            keep_closest<NF>(d2f, g.index, val, acc_p, acc_w, best_idx);
+          } else {
+            accumulate<NF>(grid_weight<W>(g, s, d2f), val, acc_p, acc_w);
           }
         }
       }
@@ -347,14 +270,15 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
       ready = tail;
     };
 
-    const int nrows = cy1 - cy0 + 1;
+    const int nrows = box.cy1 - box.cy0 + 1;
     for (int rb = 0; rb < nrows; rb += 64) {
-      // bounds of up to 64 cell rows with one vector load each (lane <-> cell row)
+      // bounds of up to 64 cell rows with one vector load each (lane <-> cell row): the text of rg_roi_search.hpp's
+      // CellRows, kept as locals and a lambda because the struct costs this kernel occupancy (see the note there)
       int rs_l = 0, re_l = 0;
       if (rb + lane < nrows) {
-        const int base = lvl_off + (cy0 + rb + lane) * c.ncx;
-        rs_l = cell_start[base + cx0];
-        re_l = cell_start[base + cx1 + 1];
+        const int base = lvl_off + (box.cy0 + rb + lane) * c.ncx;
+        rs_l = cell_start[base + box.cx0];
+        re_l = cell_start[base + box.cx1 + 1];
       }
       const int nr = nrows - rb < 64 ? nrows - rb : 64;
       int row = -1, jb = 0, je = 0;
@@ -379,14 +303,14 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
         if (have) { vn = jb + lane < je; if (vn) gn = sorted[jb + lane]; }  // prefetch the next step
         if constexpr (VRING) flush_pending();   // the values requested one step ago have had that step to arrive
         // lower bound of the distance to the nearest voxel of the block vs the block's largest (inflated) radius
-        const float dz = g.z - zf;
+        const float dz = g.z - s.zf;
         const float dxb = fmaxf(fmaxf(xlo - g.x, g.x - xhi), 0.0f);
         const float dyb = fmaxf(fmaxf(ylo - g.y, g.y - yhi), 0.0f);
         const float d2min = __builtin_fmaf(dxb, dxb, __builtin_fmaf(dyb, dyb, dz * dz));
         const bool pre = valid && d2min <= r2max_hi;
         const unsigned long long m = __ballot(pre);
         if (pre) {
-          const int pos = tail + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+          const int pos = ring_position(m, tail);
           ring[pos & (kRing - 1)] = g;
           if constexpr (VRING) {  // request the gate's field slots now, park them in the ring one step later
             pend = true;
@@ -397,21 +321,15 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
         tail += __popcll(m);
         if constexpr (!VRING) ready = tail;
         if (ready - head >= 64) {   // only records whose values are in the ring (without a value ring: ready == tail)
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          wave_sync();
           dense(64);
         }
       }
     }
     if constexpr (VRING) flush_pending();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     dense(tail - head);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     }   // visit: the radar's queue is empty
 
     if constexpr (MODE == kCountMode) {
@@ -446,55 +364,23 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
   }
 }
 
-inline dim3 k2_grid(const SearchArgs& a) {
-  const long waves = (long)((a.nx + PX - 1) / PX) * ((a.ny + BY - 1) / BY) * a.nz;
-  return dim3((unsigned)((waves + 3) / 4));
+// Wavefronts of a launch over an nz x ny x nx lattice: one per PX x BY patch of a level.  The kernel decodes its wave
+// number in 32 bits: every gridding entry point refuses a lattice whose count does not fit.
+inline long lattice_waves(int nz, int ny, int nx) { return (long)((nx + PX - 1) / PX) * ((ny + BY - 1) / BY) * nz; }
+
+inline int check_lattice_launch(const char* fn, int nz, int ny, int nx) {
+  RG_REQUIRE((long)nx * ny * nz > 0 && lattice_waves(nz, ny, nx) < 0xFFFFFFF0L, RG_EUNSUPPORTED,
+             "%s: grid too large for one launch", fn);
+  return RG_OK;
 }
 
-template <int W, int NF, int STRIDE>
-int launch(const SearchArgs& a, const float* packed, float fill, float* out, hipStream_t s) {
-  hipLaunchKernelGGL((roi_block_kernel<kGridMode, W, NF, STRIDE>), k2_grid(a), dim3(rg::kBlock), 0, s, a, packed, fill, out,
-                     (int*)nullptr, (const long long*)nullptr, (int*)nullptr, (float*)nullptr);
-  return rg::check_launch("rg_roi_grid_f32");
-}
-
-template <int W>
-int dispatch(int nf, const SearchArgs& a, const float* packed, float fill, float* out, hipStream_t s) {
-  switch (nf) {
-    case 1: return launch<W, 1, 1>(a, packed, fill, out, s);
-    case 2: return launch<W, 2, 2>(a, packed, fill, out, s);
-    case 3: return launch<W, 3, 4>(a, packed, fill, out, s);
-    case 4: return launch<W, 4, 4>(a, packed, fill, out, s);
-    case 5: return launch<W, 5, 8>(a, packed, fill, out, s);
-    case 6: return launch<W, 6, 8>(a, packed, fill, out, s);
-    case 7: return launch<W, 7, 8>(a, packed, fill, out, s);
-    default: return launch<W, 8, 8>(a, packed, fill, out, s);
-  }
-}
-
-inline int stride_for(int nf) { return nf == 1 ? 1 : nf == 2 ? 2 : nf <= 4 ? 4 : 8; }
-
-template <int W, int NF, int STRIDE>
-int launch_mosaic(const MosaicArgs& a, float fill, float* out, hipStream_t s) {
-  const long waves = (long)((a.nx + PX - 1) / PX) * ((a.ny + BY - 1) / BY) * a.nz;
-  hipLaunchKernelGGL((roi_block_kernel<kGridMode, W, NF, STRIDE, true>), dim3((unsigned)((waves + 3) / 4)),
-                     dim3(rg::kBlock), 0, s, a, (const float*)nullptr, fill, out, (int*)nullptr, (const long long*)nullptr,
-                     (int*)nullptr, (float*)nullptr);
-  return rg::check_launch("rg_roi_grid_mosaic_f32");
-}
-
-template <int W>
-int dispatch_mosaic(int nf, const MosaicArgs& a, float fill, float* out, hipStream_t s) {
-  switch (nf) {
-    case 1: return launch_mosaic<W, 1, 1>(a, fill, out, s);
-    case 2: return launch_mosaic<W, 2, 2>(a, fill, out, s);
-    case 3: return launch_mosaic<W, 3, 4>(a, fill, out, s);
-    case 4: return launch_mosaic<W, 4, 4>(a, fill, out, s);
-    case 5: return launch_mosaic<W, 5, 8>(a, fill, out, s);
-    case 6: return launch_mosaic<W, 6, 8>(a, fill, out, s);
-    case 7: return launch_mosaic<W, 7, 8>(a, fill, out, s);
-    default: return launch_mosaic<W, 8, 8>(a, fill, out, s);
-  }
+template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false, class Args>
+int launch(const char* fn, const Args& a, const float* packed, float fill, float* out, int* counts, const long long* indptr,
+           int* gidx, float* wts, hipStream_t s) {
+  hipLaunchKernelGGL((roi_block_kernel<MODE, W, NF, STRIDE, MOSAIC>),
+                     dim3((unsigned)((lattice_waves(a.nz, a.ny, a.nx) + 3) / 4)), dim3(rg::kBlock), 0, s, a, packed, fill,
+                     out, counts, indptr, gidx, wts);
+  return rg::check_launch(fn);
 }
 
 }  // namespace
@@ -503,28 +389,20 @@ extern "C" int rg_roi_grid_f32(const rg_gate4* sorted_gates, const int32_t* cell
                                const float* xc, const float* yc, const float* zc, int32_t nz, int32_t ny, int32_t nx,
                                double min_radius, double beam_factor, int32_t weighting, const float* packed,
                                int32_t n_fields, int32_t stride, float fill_value, float* out, rg_stream_t stream) {
-  const int rc = check_search_args("rg_roi_grid_f32", sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx);
+  const char* fn = "rg_roi_grid_f32";
+  int rc = check_search_args(fn, sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx);
   if (rc != RG_OK) return rc;
-  RG_REQUIRE(packed && out, RG_EINVAL, "rg_roi_grid_f32: null pointer");
-  RG_REQUIRE(weighting >= RG_W_BARNES2 && weighting <= RG_W_CLOSEST, RG_EINVAL, "rg_roi_grid_f32: unknown weighting %d",
-             weighting);
-  RG_REQUIRE(n_fields >= 1 && n_fields <= RG_MAX_FIELDS, RG_EUNSUPPORTED, "rg_roi_grid_f32: n_fields=%d not in 1..%d",
-             n_fields, RG_MAX_FIELDS);
-  RG_REQUIRE(stride == stride_for(n_fields), RG_EINVAL, "rg_roi_grid_f32: stride=%d, expected %d for %d fields", stride,
-             stride_for(n_fields), n_fields);
-  RG_REQUIRE(rg::aligned16(packed), RG_EALIGN, "rg_roi_grid_f32: packed must be 16-byte aligned");
-  RG_REQUIRE((long)nx * ny * nz > 0 &&
-                 (long)((nx + PX - 1) / PX) * ((ny + BY - 1) / BY) * nz < 0xFFFFFFF0L,
-             RG_EUNSUPPORTED,
-             "rg_roi_grid_f32: grid too large for one launch");
+  rc = check_grid_args(fn, packed, out, weighting, RG_W_CLOSEST, nullptr, n_fields, stride);
+  if (rc != RG_OK) return rc;
+  rc = check_lattice_launch(fn, nz, ny, nx);
+  if (rc != RG_OK) return rc;
   const SearchArgs a = make_args(sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx, min_radius, beam_factor);
-  hipStream_t s = (hipStream_t)stream;
-  switch (weighting) {
-    case RG_W_BARNES2: return dispatch<RG_W_BARNES2>(n_fields, a, packed, fill_value, out, s);
-    case RG_W_CRESSMAN: return dispatch<RG_W_CRESSMAN>(n_fields, a, packed, fill_value, out, s);
-    case RG_W_CLOSEST: return dispatch<RG_W_CLOSEST>(n_fields, a, packed, fill_value, out, s);
-    default: return dispatch<RG_W_NEAREST>(n_fields, a, packed, fill_value, out, s);
-  }
+  return dispatch_weighting<true>(weighting, [&](auto w) {
+    return dispatch_fields(n_fields, [&](auto nf, auto st) {
+      return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value>(
+          fn, a, packed, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    });
+  });
 }
 
 // Several radars on one grid: per radar, radar_grid/compute.py:46-91 in that radar's frame and radar_grid/interpolate.py:69-104
@@ -533,25 +411,18 @@ extern "C" int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_
                                       int32_t nx, double min_radius, double beam_factor, int32_t weighting,
                                       const float* packed, int32_t n_fields, int32_t stride, int64_t n_gates_total,
                                       float fill_value, float* out, rg_stream_t stream) {
-  RG_REQUIRE(radars_host, RG_EINVAL, "rg_roi_grid_mosaic_f32: null radar table");
-  RG_REQUIRE(n_radars >= 1, RG_EINVAL, "rg_roi_grid_mosaic_f32: n_radars=%d", n_radars);
-  RG_REQUIRE(n_radars <= RG_MAX_RADARS, RG_EUNSUPPORTED, "rg_roi_grid_mosaic_f32: n_radars=%d exceeds %d", n_radars,
-             RG_MAX_RADARS);
-  RG_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1, RG_EINVAL, "rg_roi_grid_mosaic_f32: bad grid shape (%d,%d,%d)", nz, ny, nx);
-  RG_REQUIRE(packed && out, RG_EINVAL, "rg_roi_grid_mosaic_f32: null pointer");
-  RG_REQUIRE(weighting != RG_W_CLOSEST, RG_EUNSUPPORTED, "rg_roi_grid_mosaic_f32: the closest-gate mode is single-radar");
-  RG_REQUIRE(weighting >= RG_W_BARNES2 && weighting <= RG_W_NEAREST, RG_EINVAL,
-             "rg_roi_grid_mosaic_f32: unknown weighting %d", weighting);
-  RG_REQUIRE(n_fields >= 1 && n_fields <= RG_MAX_FIELDS, RG_EUNSUPPORTED,
-             "rg_roi_grid_mosaic_f32: n_fields=%d not in 1..%d", n_fields, RG_MAX_FIELDS);
-  RG_REQUIRE(stride == stride_for(n_fields), RG_EINVAL, "rg_roi_grid_mosaic_f32: stride=%d, expected %d for %d fields",
-             stride, stride_for(n_fields), n_fields);
-  RG_REQUIRE(rg::aligned16(packed), RG_EALIGN, "rg_roi_grid_mosaic_f32: packed must be 16-byte aligned");
+  const char* fn = "rg_roi_grid_mosaic_f32";
+  RG_REQUIRE(radars_host, RG_EINVAL, "%s: null radar table", fn);
+  RG_REQUIRE(n_radars >= 1, RG_EINVAL, "%s: n_radars=%d", fn, n_radars);
+  RG_REQUIRE(n_radars <= RG_MAX_RADARS, RG_EUNSUPPORTED, "%s: n_radars=%d exceeds %d", fn, n_radars, RG_MAX_RADARS);
+  RG_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1, RG_EINVAL, "%s: bad grid shape (%d,%d,%d)", fn, nz, ny, nx);
+  int rc = check_grid_args(fn, packed, out, weighting, RG_W_NEAREST, "single-radar", n_fields, stride);
+  if (rc != RG_OK) return rc;
   // the gather takes a 32-bit slot number (rg::load_packed)
   RG_REQUIRE(n_gates_total >= 0 && n_gates_total <= 0x7FFFFFFFL, RG_EUNSUPPORTED,
-             "rg_roi_grid_mosaic_f32: n_gates_total=%lld not in 0 .. 2^31 - 1", (long long)n_gates_total);
-  RG_REQUIRE((long)((nx + PX - 1) / PX) * ((ny + BY - 1) / BY) * nz < 0xFFFFFFF0L, RG_EUNSUPPORTED,
-             "rg_roi_grid_mosaic_f32: grid too large for one launch");
+             "%s: n_gates_total=%lld not in 0 .. 2^31 - 1", fn, (long long)n_gates_total);
+  rc = check_lattice_launch(fn, nz, ny, nx);
+  if (rc != RG_OK) return rc;
   MosaicArgs a = {};
   a.n_radars = n_radars;
   a.nz = nz; a.ny = ny; a.nx = nx;
@@ -561,28 +432,27 @@ extern "C" int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_
     const rg_mosaic_radar& e = radars_host[r];
     RG_REQUIRE(e.nx_win >= 0 && e.ny_win >= 0 && e.ix0 >= 0 && e.iy0 >= 0 && (long)e.ix0 + e.nx_win <= nx &&
                    (long)e.iy0 + e.ny_win <= ny,
-               RG_EINVAL, "rg_roi_grid_mosaic_f32: radar %d: window x %d+%d, y %d+%d outside the %dx%d grid", r, e.ix0,
-               e.nx_win, e.iy0, e.ny_win, nx, ny);
+               RG_EINVAL, "%s: radar %d: window x %d+%d, y %d+%d outside the %dx%d grid", fn, r, e.ix0, e.nx_win, e.iy0,
+               e.ny_win, nx, ny);
     // the kernel gathers packed[gate_offset + index] through a raw pointer: the offsets are what keep it in bounds
     RG_REQUIRE(e.gate_offset >= 0 && e.n_gates >= 0 && e.gate_offset + e.n_gates <= n_gates_total, RG_EINVAL,
-               "rg_roi_grid_mosaic_f32: radar %d: gates %lld + %lld exceed n_gates_total=%lld", r,
-               (long long)e.gate_offset, (long long)e.n_gates, (long long)n_gates_total);
+               "%s: radar %d: gates %lld + %lld exceed n_gates_total=%lld", fn, r, (long long)e.gate_offset,
+               (long long)e.n_gates, (long long)n_gates_total);
     MosaicRadar& m = a.r[r];
     if (e.nx_win == 0 || e.ny_win == 0) continue;           // reaches nothing: never visited, pointers not read
-    const int rc = check_search_args("rg_roi_grid_mosaic_f32", e.sorted_gates, e.cell_start, &e.cells, e.xc, e.yc, e.zc,
-                                     nz, e.ny_win, e.nx_win);
+    rc = check_search_args(fn, e.sorted_gates, e.cell_start, &e.cells, e.xc, e.yc, e.zc, nz, e.ny_win, e.nx_win);
     if (rc != RG_OK) return rc;
     m.sorted = e.sorted_gates; m.cell_start = e.cell_start; m.c = to_cells(&e.cells);
     m.xc = e.xc; m.yc = e.yc; m.zc = e.zc;
     m.packed = packed + e.gate_offset * stride;
     m.ix0 = e.ix0; m.iy0 = e.iy0; m.nxw = e.nx_win; m.nyw = e.ny_win;
   }
-  hipStream_t s = (hipStream_t)stream;
-  switch (weighting) {
-    case RG_W_BARNES2: return dispatch_mosaic<RG_W_BARNES2>(n_fields, a, fill_value, out, s);
-    case RG_W_CRESSMAN: return dispatch_mosaic<RG_W_CRESSMAN>(n_fields, a, fill_value, out, s);
-    default: return dispatch_mosaic<RG_W_NEAREST>(n_fields, a, fill_value, out, s);
-  }
+  return dispatch_weighting(weighting, [&](auto w) {
+    return dispatch_fields(n_fields, [&](auto nf, auto st) {
+      return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value, true>(
+          fn, a, nullptr, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -592,37 +462,29 @@ extern "C" int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_
 extern "C" int rg_geom_count_f32(const rg_gate4* sorted_gates, const int32_t* cell_start, const rg_cellgrid* cells_host,
                                  const float* xc, const float* yc, const float* zc, int32_t nz, int32_t ny, int32_t nx,
                                  double min_radius, double beam_factor, int32_t* counts, rg_stream_t stream) {
-  const int rc = check_search_args("rg_geom_count_f32", sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx);
+  const char* fn = "rg_geom_count_f32";
+  const int rc = check_search_args(fn, sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx);
   if (rc != RG_OK) return rc;
-  RG_REQUIRE(counts, RG_EINVAL, "rg_geom_count_f32: null counts");
+  RG_REQUIRE(counts, RG_EINVAL, "%s: null counts", fn);
   const SearchArgs a = make_args(sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx, min_radius, beam_factor);
-  hipLaunchKernelGGL((roi_block_kernel<kCountMode, RG_W_NEAREST, 1, 1>), k2_grid(a), dim3(rg::kBlock), 0,
-                     (hipStream_t)stream, a, (const float*)nullptr, 0.0f, (float*)nullptr, counts,
-                     (const long long*)nullptr, (int*)nullptr, (float*)nullptr);
-  return rg::check_launch("rg_geom_count_f32");
+  return launch<kCountMode, RG_W_NEAREST, 1, 1>(fn, a, nullptr, 0.0f, nullptr, counts, nullptr, nullptr, nullptr,
+                                                (hipStream_t)stream);
 }
 
 extern "C" int rg_geom_fill_f32(const rg_gate4* sorted_gates, const int32_t* cell_start, const rg_cellgrid* cells_host,
                                 const float* xc, const float* yc, const float* zc, int32_t nz, int32_t ny, int32_t nx,
                                 double min_radius, double beam_factor, int32_t weighting, const int64_t* indptr,
                                 int32_t* gate_idx, float* weights, rg_stream_t stream) {
-  const int rc = check_search_args("rg_geom_fill_f32", sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx);
+  const char* fn = "rg_geom_fill_f32";
+  int rc = check_search_args(fn, sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx);
   if (rc != RG_OK) return rc;
-  RG_REQUIRE(indptr && gate_idx && weights, RG_EINVAL, "rg_geom_fill_f32: null pointer");
-  RG_REQUIRE(weighting >= RG_W_BARNES2 && weighting <= RG_W_NEAREST, RG_EINVAL, "rg_geom_fill_f32: unknown weighting %d",
-             weighting);
+  RG_REQUIRE(indptr && gate_idx && weights, RG_EINVAL, "%s: null pointer", fn);
+  rc = check_weighting(fn, weighting, RG_W_NEAREST, nullptr);
+  if (rc != RG_OK) return rc;
   const SearchArgs a = make_args(sorted_gates, cell_start, cells_host, xc, yc, zc, nz, ny, nx, min_radius, beam_factor);
-  const dim3 grid = k2_grid(a), block(rg::kBlock);
-  hipStream_t s = (hipStream_t)stream;
-  const long long* ip = reinterpret_cast<const long long*>(indptr);
-#define RG_FILL(W_)                                                                                                     \
-  hipLaunchKernelGGL((roi_block_kernel<kFillMode, W_, 1, 1>), grid, block, 0, s, a, (const float*)nullptr, 0.0f,               \
-                     (float*)nullptr, (int*)nullptr, ip, gate_idx, weights)
-  switch (weighting) {
-    case RG_W_BARNES2: RG_FILL(RG_W_BARNES2); break;
-    case RG_W_CRESSMAN: RG_FILL(RG_W_CRESSMAN); break;
-    default: RG_FILL(RG_W_NEAREST); break;
-  }
-#undef RG_FILL
-  return rg::check_launch("rg_geom_fill_f32");
+  return dispatch_weighting(weighting, [&](auto w) {
+    return launch<kFillMode, decltype(w)::value, 1, 1>(fn, a, nullptr, 0.0f, nullptr, nullptr,
+                                                       reinterpret_cast<const long long*>(indptr), gate_idx, weights,
+                                                       (hipStream_t)stream);
+  });
 }

@@ -12,11 +12,11 @@
 //     sub-boxes of kPts / 4 points each -- with 4 points per block, to the nearest POINT -- against the block's largest
 //     radius, inflated by 2e-6.  A path runs at any angle through the cells, so the block's box is mostly far from it; the
 //     sub-boxes follow it;
-//   * dense stage: K2's, 16 queued records per step.  float32 d2 decides membership where it is clear of the rim by 2e-6,
-//     inside that band the reference's float64 `d2 < r2` (compute.py:69-74) decides.  Grid mode weighs in float32 within
-//     K2's budgets (Barnes |rel err| < 2e-6; Cressman numerator from the float64 d2, < 5e-7; uniform exact) and gathers the
-//     packed field slots per hit; count and fill classify hits with the same code, fill writes the float64-exact weight
-//     rounded to float32; a point's hits arrive in (cell row, sorted position) order, the row order the CSR has always had;
+//   * dense stage: K2's, 16 queued records per step, through the same functions of rg_roi_search.hpp (in_roi: float32 d2
+//     where it is clear of the rim band, the reference's float64 `d2 < r2` inside it; grid_weight / accumulate: float32
+//     weights within K2's budgets; emit_hit: count and fill classify hits with the same code, fill writes the float64-exact
+//     weight rounded to float32).  Grid mode gathers the packed field slots per hit; a point's hits arrive in (cell row,
+//     sorted position) order, the row order the CSR has always had;
 //   * the survivor ring holds at most 63 waiting + 64 new records and is drained whenever 64 are waiting, so a row of
 //     thousands of neighbours (a section through the radar) passes through it like any other; row lengths and ring
 //     positions are 32-bit counts of gates, of which the search structure holds fewer than 2^31.
@@ -33,7 +33,7 @@
 // neighbours are not guaranteed -- the Python surface refuses both before a launch.
 //
 // Compiled with -ffp-contract=off like every TU (the exact test must not be fused); the float32 tests use explicit fmaf,
-// their error is covered by the 2e-6 band.
+// their error is covered by the rim band (rg_roi_search.hpp).
 #include "rg_common.hpp"
 #include "rg_roi_search.hpp"
 
@@ -51,30 +51,6 @@ constexpr unsigned long long slot_lanes_of_point0() {   // the lanes that own po
   unsigned long long m = 0;
   for (int s = 0; s < kSlots; ++s) m |= 1ull << (s * kPts);
   return m;
-}
-
-constexpr int kGridMode = 0, kCountMode = 1, kFillMode = 2;
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)b, lane);
-  const unsigned hi = __builtin_amdgcn_readlane((unsigned)(b >> 32), lane);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ float readlane_f32(float v, int lane) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-
-// float32 weight from the float32 d2: Barnes as one multiply and one v_exp_f32 (inv_r2q = -log2(e) * 4 / r2), uniform 1;
-// the error analysis is rg_roi_grid.hip's (|rel err| < 2e-6).  Cressman takes its numerator from the float64 d2, below.
-template <int W>
-__device__ __forceinline__ float weight_from_f32(float d2f, float inv_r2q) {
-  if constexpr (W == RG_W_BARNES2) {
-    return __builtin_amdgcn_exp2f(d2f * inv_r2q) + 1e-5f;
-  } else {
-    return 1.0f;
-  }
 }
 
 template <int MODE, int W, int NF, int STRIDE>
@@ -107,20 +83,9 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, cons
   const bool live = inside && __builtin_isfinite(xf) && __builtin_isfinite(yf);
   const double z = (double)a.zc[iz];                                            // common to the whole wave
   const float zf = (float)z;
-  const double x = live ? (double)xf : 0.0, y = live ? (double)yf : 0.0;
-  const double dist = sqrt(x * x + y * y + z * z);
-  const double r = fmax(a.min_radius, dist * a.beam_factor);
-  const double r2 = r * r;
-  const float r2f = (float)r2;
-  // float32 d2 carries < 4e-7 relative error: outside [r2_lo, r2_hi] the float32 comparison is already exact
-  const float r2_hi = live ? (float)(r2 * (1.0 + 2e-6)) * (1.0f + 2.4e-7f) : -1.0f;
-  const float r2_lo = live ? (float)(r2 * (1.0 - 2e-6)) * (1.0f - 2.4e-7f) : -1.0f;   // dead lanes never hit
-  const float inv_r2q = (float)(-1.4426950408889634 * 4.0 / r2);
+  const Sample s = make_sample(live ? (double)xf : 0.0, live ? (double)yf : 0.0, z, live, a.min_radius, a.beam_factor);
   // ---- block-wide (wave-uniform) quantities: largest radius, the four sub-boxes and the block's box ----------------
-  double rmax = live ? r : 0.0;
-#pragma unroll
-  for (int m = 1; m < kPts; m <<= 1) rmax = fmax(rmax, __shfl_xor(rmax, m, 64));
-  rmax = readlane_f64(rmax, 0);
+  const double rmax = block_max_radius<kPts>(s, live);
   const float inf = __builtin_inff();
   float bxlo = live ? xf : inf, bxhi = live ? xf : -inf, bylo = live ? yf : inf, byhi = live ? yf : -inf;
 #pragma unroll
@@ -139,14 +104,9 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, cons
   const float ylo = fminf(fminf(sylo[0], sylo[1]), fminf(sylo[2], sylo[3]));
   const float yhi = fmaxf(fmaxf(syhi[0], syhi[1]), fmaxf(syhi[2], syhi[3]));
   const bool any_live = xlo <= xhi;                                             // wave-uniform
-  const float r2max_hi = (float)(rmax * rmax * (1.0 + 2e-6)) * (1.0f + 2.4e-7f);
-  int cx0 = 0, cx1 = -1, cy0 = 0, cy1 = -1;
-  if (any_live) {
-    cx0 = __builtin_amdgcn_readfirstlane(cell_clamped((double)xlo - rmax, c.x0, c.inv_cx, c.ncx));
-    cx1 = __builtin_amdgcn_readfirstlane(cell_clamped((double)xhi + rmax, c.x0, c.inv_cx, c.ncx));
-    cy0 = __builtin_amdgcn_readfirstlane(cell_clamped((double)ylo - rmax, c.y0, c.inv_cy, c.ncy));
-    cy1 = __builtin_amdgcn_readfirstlane(cell_clamped((double)yhi + rmax, c.y0, c.inv_cy, c.ncy));
-  }
+  const float r2max_hi = band_hi(rmax * rmax);
+  CellBox box = {0, -1, 0, -1};
+  if (any_live) box = cell_box(xlo, xhi, ylo, yhi, rmax, c);
 
   // acc_p = sum w*v, acc_w = sum w (this lane's point, this lane's record slot)
   float acc_p[NF], acc_w[NF];
@@ -172,81 +132,32 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, cons
       float d2f = 0.0f;
       if (e < n) {
         g = ring[(head + e) & (kRing - 1)];
-        const float dx = g.x - xf, dy = g.y - yf, dz = g.z - zf;
-        d2f = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-        in = d2f <= r2_lo;
-        if (!in && d2f <= r2_hi) {  // within 2e-6 of the rim: the reference's float64 arithmetic decides
-          const double ex = (double)g.x - x, ey = (double)g.y - y, ez = (double)g.z - z;  // compute.py:69-71
-          in = ex * ex + ey * ey + ez * ez < r2;                                          // compute.py:72,74
-        }
+        in = in_roi(g, s, true, d2f);
       }
       if constexpr (MODE != kGridMode) {
-        const unsigned long long hits = __ballot(in);   // executed by every lane of the wave
-        if constexpr (MODE == kFillMode) {
-          if (in) {
-            const double ex = (double)g.x - x, ey = (double)g.y - y, ez = (double)g.z - z;
-            const double d2 = ex * ex + ey * ey + ez * ez;                                // compute.py:72
-            const long long pos = row_base + cursor + __popcll(hits & lower_slots);
-            gidx[pos] = g.index;
-            wts[pos] = roi_weight<W>(d2, r2);                                             // compute.py:82-87
-          }
-        }
-        cursor += __popcll(hits & pt_lanes);
-      } else {
-        if (in) {
-          float w;
-          if constexpr (W == RG_W_CRESSMAN) {
-            // (r2 - d2) / (r2 + d2), compute.py:85: the numerator cancels at the rim, so it comes from the reference's
-            // float64 d2 (unfused, as the test: r2 - d2 > 0 for every hit), rounded once; the denominator in float32
-            const double ex = (double)g.x - x, ey = (double)g.y - y, ez = (double)g.z - z;
-            w = (float)(r2 - (ex * ex + ey * ey + ez * ez)) / (r2f + d2f);                // compute.py:72,85
-          } else {
-            w = weight_from_f32<W>(d2f, inv_r2q);
-          }
-          float val[STRIDE];
-          rg::load_packed<STRIDE>(packed, (unsigned)g.index, val);                        // one gather per hit
-#pragma unroll
-          for (int f = 0; f < NF; ++f) {
-            const bool ok = rg::f32_bits(val[f]) != RG_EXCLUDED_BITS;
-            acc_p[f] += ok ? w * val[f] : 0.0f;  // float32 product, as interpolate.py:82
-            acc_w[f] += ok ? w : 0.0f;
-          }
-        }
+        emit_hit<MODE, W>(in, g, s, pt_lanes, lower_slots, row_base, cursor, gidx, wts);
+      } else if (in) {
+        float val[STRIDE];
+        rg::load_packed<STRIDE>(packed, (unsigned)g.index, val);                          // one gather per hit
+        accumulate<NF>(grid_weight<W>(g, s, d2f), val, acc_p, acc_w);
       }
     }
     head += n;
   };
 
-  const int nrows = cy1 - cy0 + 1;
+  const int nrows = box.cy1 - box.cy0 + 1;
   for (int rb = 0; rb < nrows; rb += 64) {
-    // bounds of up to 64 cell rows with one vector load each (lane <-> cell row)
-    int rs_l = 0, re_l = 0;
-    if (rb + lane < nrows) {
-      const int base = lvl_off + (cy0 + rb + lane) * c.ncx;
-      rs_l = cell_start[base + cx0];
-      re_l = cell_start[base + cx1 + 1];
-    }
-    const int nr = nrows - rb < 64 ? nrows - rb : 64;
-    int crow = -1, jb = 0, je = 0;
-    auto advance = [&]() -> bool {  // next 64-candidate step; all state wave-uniform
-      jb += 64;
-      while (jb >= je) {
-        if (++crow >= nr) return false;
-        jb = __builtin_amdgcn_readlane(rs_l, crow);
-        je = __builtin_amdgcn_readlane(re_l, crow);
-      }
-      return true;
-    };
-    bool have = advance();
+    CellRows rows(cell_start, lvl_off, c.ncx, box, rb, nrows, lane);
+    bool have = rows.advance();
     rg_gate4 gn;
     gn.x = gn.y = gn.z = 0.0f; gn.index = 0;
     bool vn = false;
-    if (have) { vn = jb + lane < je; if (vn) gn = sorted[jb + lane]; }
+    if (have) { vn = rows.jb + lane < rows.je; if (vn) gn = sorted[rows.jb + lane]; }
     while (have) {
       const rg_gate4 g = gn;
       const bool valid = vn;
-      have = advance();
-      if (have) { vn = jb + lane < je; if (vn) gn = sorted[jb + lane]; }  // prefetch the next step
+      have = rows.advance();
+      if (have) { vn = rows.jb + lane < rows.je; if (vn) gn = sorted[rows.jb + lane]; }  // prefetch the next step
       // lower bound of the distance to the nearest sub-box vs the block's largest (inflated) radius
       const float dz = g.z - zf;
       const float dz2 = dz * dz;
@@ -259,25 +170,16 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, cons
       }
       pre = pre && valid;
       const unsigned long long m = __ballot(pre);
-      if (pre) {
-        const int pos = tail + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        ring[pos & (kRing - 1)] = g;
-      }
+      if (pre) ring[ring_position(m, tail) & (kRing - 1)] = g;
       tail += __popcll(m);
       if (tail - head >= 64) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         dense(64);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the drained slots are written again from here on
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();   // the drained slots are written again from here on
       }
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_sync();
   dense(tail - head);
 
   if constexpr (MODE == kCountMode) {
@@ -298,10 +200,6 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, cons
 }
 
 inline long section_waves(int nz, int n_points) { return (((long)n_points + kPts - 1) / kPts) * nz; }
-
-inline dim3 section_grid(const SectionArgs& a) {
-  return dim3((unsigned)((section_waves(a.nz, a.n_points) + 3) / 4));
-}
 
 inline int check_section_args(const char* fn, const rg_gate4* sorted, const int32_t* cell_start, const rg_cellgrid* cells,
                               const float* xs, const float* ys, const float* zc, int nz, int n_points) {
@@ -324,28 +222,13 @@ inline SectionArgs make_section_args(const rg_gate4* sorted, const int32_t* cell
   return a;
 }
 
-template <int W, int NF, int STRIDE>
-int launch(const SectionArgs& a, const float* packed, float fill, float* out, hipStream_t s) {
-  hipLaunchKernelGGL((section_kernel<kGridMode, W, NF, STRIDE>), section_grid(a), dim3(rg::kBlock), 0, s, a, packed, fill,
-                     out, (int*)nullptr, (const long long*)nullptr, (int*)nullptr, (float*)nullptr);
-  return rg::check_launch("rg_roi_section_f32");
+template <int MODE, int W, int NF, int STRIDE>
+int launch(const char* fn, const SectionArgs& a, const float* packed, float fill, float* out, int* counts,
+           const long long* indptr, int* gidx, float* wts, hipStream_t s) {
+  hipLaunchKernelGGL((section_kernel<MODE, W, NF, STRIDE>), dim3((unsigned)((section_waves(a.nz, a.n_points) + 3) / 4)),
+                     dim3(rg::kBlock), 0, s, a, packed, fill, out, counts, indptr, gidx, wts);
+  return rg::check_launch(fn);
 }
-
-template <int W>
-int dispatch(int nf, const SectionArgs& a, const float* packed, float fill, float* out, hipStream_t s) {
-  switch (nf) {
-    case 1: return launch<W, 1, 1>(a, packed, fill, out, s);
-    case 2: return launch<W, 2, 2>(a, packed, fill, out, s);
-    case 3: return launch<W, 3, 4>(a, packed, fill, out, s);
-    case 4: return launch<W, 4, 4>(a, packed, fill, out, s);
-    case 5: return launch<W, 5, 8>(a, packed, fill, out, s);
-    case 6: return launch<W, 6, 8>(a, packed, fill, out, s);
-    case 7: return launch<W, 7, 8>(a, packed, fill, out, s);
-    default: return launch<W, 8, 8>(a, packed, fill, out, s);
-  }
-}
-
-inline int stride_for(int nf) { return nf == 1 ? 1 : nf == 2 ? 2 : nf <= 4 ? 4 : 8; }
 
 }  // namespace
 
@@ -354,24 +237,18 @@ extern "C" int rg_roi_section_f32(const rg_gate4* sorted_gates, const int32_t* c
                                   double min_radius, double beam_factor, int32_t weighting, const float* packed,
                                   int32_t n_fields, int32_t stride, float fill_value, float* out, rg_stream_t stream) {
   const char* fn = "rg_roi_section_f32";
-  RG_REQUIRE(packed && out, RG_EINVAL, "%s: null pointer", fn);
-  RG_REQUIRE(weighting != RG_W_CLOSEST, RG_EUNSUPPORTED, "%s: the closest-gate mode is a lattice mode", fn);
-  RG_REQUIRE(weighting >= RG_W_BARNES2 && weighting <= RG_W_NEAREST, RG_EINVAL, "%s: unknown weighting %d", fn, weighting);
-  RG_REQUIRE(n_fields >= 1 && n_fields <= RG_MAX_FIELDS, RG_EUNSUPPORTED, "%s: n_fields=%d not in 1..%d", fn, n_fields,
-             RG_MAX_FIELDS);
-  RG_REQUIRE(stride == stride_for(n_fields), RG_EINVAL, "%s: stride=%d, expected %d for %d fields", fn, stride,
-             stride_for(n_fields), n_fields);
-  const int rc = check_section_args(fn, sorted_gates, cell_start, cells_host, xs, ys, zc, nz, n_points);
+  int rc = check_grid_args(fn, packed, out, weighting, RG_W_NEAREST, "a lattice mode", n_fields, stride);
   if (rc != RG_OK) return rc;
-  RG_REQUIRE(rg::aligned16(packed), RG_EALIGN, "%s: packed must be 16-byte aligned", fn);
+  rc = check_section_args(fn, sorted_gates, cell_start, cells_host, xs, ys, zc, nz, n_points);
+  if (rc != RG_OK) return rc;
   const SectionArgs a = make_section_args(sorted_gates, cell_start, cells_host, xs, ys, zc, nz, n_points, min_radius,
                                           beam_factor);
-  hipStream_t s = (hipStream_t)stream;
-  switch (weighting) {
-    case RG_W_BARNES2: return dispatch<RG_W_BARNES2>(n_fields, a, packed, fill_value, out, s);
-    case RG_W_CRESSMAN: return dispatch<RG_W_CRESSMAN>(n_fields, a, packed, fill_value, out, s);
-    default: return dispatch<RG_W_NEAREST>(n_fields, a, packed, fill_value, out, s);
-  }
+  return dispatch_weighting(weighting, [&](auto w) {
+    return dispatch_fields(n_fields, [&](auto nf, auto st) {
+      return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value>(
+          fn, a, packed, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    });
+  });
 }
 
 // count -> prefix sum (rg_scan_counts_i64) -> fill: a section as an ordinary CSR of nz * n_points rows
@@ -384,10 +261,8 @@ extern "C" int rg_section_count_f32(const rg_gate4* sorted_gates, const int32_t*
   if (rc != RG_OK) return rc;
   const SectionArgs a = make_section_args(sorted_gates, cell_start, cells_host, xs, ys, zc, nz, n_points, min_radius,
                                           beam_factor);
-  hipLaunchKernelGGL((section_kernel<kCountMode, RG_W_NEAREST, 1, 1>), section_grid(a), dim3(rg::kBlock), 0,
-                     (hipStream_t)stream, a, (const float*)nullptr, 0.0f, (float*)nullptr, counts,
-                     (const long long*)nullptr, (int*)nullptr, (float*)nullptr);
-  return rg::check_launch(fn);
+  return launch<kCountMode, RG_W_NEAREST, 1, 1>(fn, a, nullptr, 0.0f, nullptr, counts, nullptr, nullptr, nullptr,
+                                                (hipStream_t)stream);
 }
 
 extern "C" int rg_section_fill_f32(const rg_gate4* sorted_gates, const int32_t* cell_start, const rg_cellgrid* cells_host,
@@ -396,23 +271,15 @@ extern "C" int rg_section_fill_f32(const rg_gate4* sorted_gates, const int32_t* 
                                    int32_t* gate_idx, float* weights, rg_stream_t stream) {
   const char* fn = "rg_section_fill_f32";
   RG_REQUIRE(indptr && gate_idx && weights, RG_EINVAL, "%s: null pointer", fn);
-  RG_REQUIRE(weighting != RG_W_CLOSEST, RG_EUNSUPPORTED, "%s: the closest-gate mode is a lattice mode", fn);
-  RG_REQUIRE(weighting >= RG_W_BARNES2 && weighting <= RG_W_NEAREST, RG_EINVAL, "%s: unknown weighting %d", fn, weighting);
-  const int rc = check_section_args(fn, sorted_gates, cell_start, cells_host, xs, ys, zc, nz, n_points);
+  int rc = check_weighting(fn, weighting, RG_W_NEAREST, "a lattice mode");
+  if (rc != RG_OK) return rc;
+  rc = check_section_args(fn, sorted_gates, cell_start, cells_host, xs, ys, zc, nz, n_points);
   if (rc != RG_OK) return rc;
   const SectionArgs a = make_section_args(sorted_gates, cell_start, cells_host, xs, ys, zc, nz, n_points, min_radius,
                                           beam_factor);
-  const dim3 grid = section_grid(a), block(rg::kBlock);
-  hipStream_t s = (hipStream_t)stream;
-  const long long* ip = reinterpret_cast<const long long*>(indptr);
-#define RG_FILL(W_)                                                                                                     \
-  hipLaunchKernelGGL((section_kernel<kFillMode, W_, 1, 1>), grid, block, 0, s, a, (const float*)nullptr, 0.0f,                 \
-                     (float*)nullptr, (int*)nullptr, ip, gate_idx, weights)
-  switch (weighting) {
-    case RG_W_BARNES2: RG_FILL(RG_W_BARNES2); break;
-    case RG_W_CRESSMAN: RG_FILL(RG_W_CRESSMAN); break;
-    default: RG_FILL(RG_W_NEAREST); break;
-  }
-#undef RG_FILL
-  return rg::check_launch(fn);
+  return dispatch_weighting(weighting, [&](auto w) {
+    return launch<kFillMode, decltype(w)::value, 1, 1>(fn, a, nullptr, 0.0f, nullptr, nullptr,
+                                                       reinterpret_cast<const long long*>(indptr), gate_idx, weights,
+                                                       (hipStream_t)stream);
+  });
 }

@@ -209,50 +209,75 @@ class RoiSearch:
         return float(min(max(cell, 0.25 * self.min_radius, 25.0), 8.0 * max(self.min_radius, 1.0) + 2000.0))
 
     # ------------------------------------------------------------------------------------------------
-    def count_pairs(self) -> int:
-        """Total number of (voxel, gate) pairs of the geometry (one count pass, nothing is kept)."""
+    def search_args(self, iz0: int = 0, n_levels: Optional[int] = None):
+        """The ten leading arguments of ``rg_geom_count_f32`` / ``rg_geom_fill_f32`` / ``rg_roi_grid_f32``: the search
+        structure, the coordinate tables, the grid shape, the ROI -- for the ``n_levels`` levels from ``iz0`` on (default:
+        all)."""
+        nz, ny, nx = self.grid_shape
+        return (_native.ptr(self.sorted_gates), _native.ptr(self.cell_start), self.cells_from(iz0), _native.ptr(self.xc),
+                _native.ptr(self.yc), _native.ptr(self.zc) + 4 * iz0, nz - iz0 if n_levels is None else n_levels, ny, nx,
+                self.min_radius, self.beam_factor)
+
+    def count_rows(self):
+        """int32 ``[n_vox + 1]``: every voxel's number of neighbours (``rg_geom_count_f32``) and a trailing zero."""
         torch = _native.torch_mod()
-        lib = _native.load_library()
         nz, ny, nx = self.grid_shape
         with torch.cuda.device(self.dev):
             counts = torch.zeros(nz * ny * nx + 1, dtype=torch.int32, device=self.dev)
-            _native.check(lib.rg_geom_count_f32(
-                _native.ptr(self.sorted_gates), _native.ptr(self.cell_start), self.cells, _native.ptr(self.xc),
-                _native.ptr(self.yc), _native.ptr(self.zc), nz, ny, nx, self.min_radius, self.beam_factor,
-                _native.ptr(counts), _native.stream_ptr()), "rg_geom_count_f32")
-            return int(counts.sum(dtype=torch.int64).item())
+            _native.check(_native.load_library().rg_geom_count_f32(*self.search_args(), _native.ptr(counts),
+                                                                   _native.stream_ptr()), "rg_geom_count_f32")
+        return counts
+
+    def fill_rows(self, weighting: str, indptr_ptr: int, gate_idx_ptr: int, weights_ptr: int, iz0: int = 0,
+                  n_levels: Optional[int] = None) -> None:
+        """``rg_geom_fill_f32`` over the levels from ``iz0`` on: row v's pairs go to positions ``indptr[v] ...`` of the two
+        arrays (raw device addresses: the slab builder and the mosaic shift them)."""
+        with _native.torch_mod().cuda.device(self.dev):
+            _native.check(_native.load_library().rg_geom_fill_f32(
+                *self.search_args(iz0, n_levels), _native.WEIGHTINGS[weighting], indptr_ptr, gate_idx_ptr, weights_ptr,
+                _native.stream_ptr()), "rg_geom_fill_f32")
+
+    def count_pairs(self) -> int:
+        """Total number of (voxel, gate) pairs of the geometry (one count pass, nothing is kept)."""
+        return int(self.count_rows().sum(dtype=_native.torch_mod().int64).item())
 
     def build_csr(self, weighting: str = "barnes2") -> DeviceCSR:
-        torch = _native.torch_mod()
-        lib = _native.load_library()
         nz, ny, nx = self.grid_shape
-        n_vox = nz * ny * nx
-        with torch.cuda.device(self.dev):
-            stream = _native.stream_ptr()
-            counts = torch.zeros(n_vox + 1, dtype=torch.int32, device=self.dev)
-            _native.check(lib.rg_geom_count_f32(
-                _native.ptr(self.sorted_gates), _native.ptr(self.cell_start), self.cells, _native.ptr(self.xc),
-                _native.ptr(self.yc), _native.ptr(self.zc), nz, ny, nx, self.min_radius, self.beam_factor,
-                _native.ptr(counts), stream), "rg_geom_count_f32")
-            indptr = torch.empty(n_vox + 1, dtype=torch.int64, device=self.dev)
-            ws_bytes = int(lib.rg_scan_workspace_bytes(n_vox))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.dev)
-            _native.check(lib.rg_scan_counts_i64(_native.ptr(counts), n_vox, _native.ptr(indptr), _native.ptr(ws),
-                                                 ws_bytes, stream), "rg_scan_counts_i64")
-            n_pairs = int(indptr[-1].item())
-            del counts, ws
-            gate_idx = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=self.dev)[:n_pairs]
-            weights = torch.empty(max(n_pairs, 1), dtype=torch.float32, device=self.dev)[:n_pairs]
-            if n_pairs:
-                _native.check(lib.rg_geom_fill_f32(
-                    _native.ptr(self.sorted_gates), _native.ptr(self.cell_start), self.cells, _native.ptr(self.xc),
-                    _native.ptr(self.yc), _native.ptr(self.zc), nz, ny, nx, self.min_radius, self.beam_factor,
-                    _native.WEIGHTINGS[weighting], _native.ptr(indptr), _native.ptr(gate_idx), _native.ptr(weights),
-                    stream), "rg_geom_fill_f32")
-            if n_pairs <= _INT32_MAX:
-                indptr = indptr.to(torch.int32)   # the reference's dtype (compute.py:232) whenever it fits
-            max_gate = int(gate_idx.max().item()) if n_pairs else -1
-        return DeviceCSR(indptr, gate_idx, weights, max_gate)
+        return csr_from_counts(self.count_rows(), nz * ny * nx, lambda indptr, gate_idx, weights: self.fill_rows(
+            weighting, _native.ptr(indptr), _native.ptr(gate_idx), _native.ptr(weights)))
+
+
+def scan_counts(counts, n_rows: int):
+    """Row lengths (int32 ``[n_rows + 1]``, on the device) -> row pointers int64 ``[n_rows + 1]`` (``rg_scan_counts_i64``)."""
+    torch = _native.torch_mod()
+    lib = _native.load_library()
+    dev = counts.device
+    with torch.cuda.device(dev):
+        indptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        ws_bytes = int(lib.rg_scan_workspace_bytes(n_rows))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _native.check(lib.rg_scan_counts_i64(_native.ptr(counts), n_rows, _native.ptr(indptr), _native.ptr(ws), ws_bytes,
+                                             _native.stream_ptr()), "rg_scan_counts_i64")
+    return indptr
+
+
+def csr_from_counts(counts, n_rows: int, fill) -> DeviceCSR:
+    """count -> prefix sum -> fill: the CSR of ``n_rows`` rows whose lengths are ``counts``.  ``fill(indptr, gate_idx,
+    weights)`` writes every row's pairs at ``indptr[row] ...`` (it is not called for an empty CSR).  ``indptr`` comes back
+    in the reference's int32 (compute.py:232) whenever the pair count fits."""
+    torch = _native.torch_mod()
+    dev = counts.device
+    indptr = scan_counts(counts, n_rows)
+    with torch.cuda.device(dev):
+        n_pairs = int(indptr[-1].item())
+        gate_idx = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)[:n_pairs]
+        weights = torch.empty(max(n_pairs, 1), dtype=torch.float32, device=dev)[:n_pairs]
+        if n_pairs:
+            fill(indptr, gate_idx, weights)
+        if n_pairs <= _INT32_MAX:
+            indptr = indptr.to(torch.int32)
+        max_gate = int(gate_idx.max().item()) if n_pairs else -1
+    return DeviceCSR(indptr, gate_idx, weights, max_gate)
 
 
 # weightings whose weights fit the 26-bit code of the packed records, and the code's base: a float32 exponent that is a
@@ -286,17 +311,7 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
         return None
     with torch.cuda.device(dev):
         stream = _native.stream_ptr()
-        counts = torch.zeros(n_vox + 1, dtype=torch.int32, device=dev)
-        _native.check(lib.rg_geom_count_f32(
-            _native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(search.xc),
-            _native.ptr(search.yc), _native.ptr(search.zc), nz, ny, nx, search.min_radius, search.beam_factor,
-            _native.ptr(counts), stream), "rg_geom_count_f32")
-        indptr = torch.empty(n_vox + 1, dtype=torch.int64, device=dev)
-        ws_bytes = int(lib.rg_scan_workspace_bytes(n_vox))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _native.check(lib.rg_scan_counts_i64(_native.ptr(counts), n_vox, _native.ptr(indptr), _native.ptr(ws), ws_bytes,
-                                             stream), "rg_scan_counts_i64")
-        del counts, ws
+        indptr = scan_counts(search.count_rows(), n_vox)
         level_ptr = indptr[::n_xy].cpu().numpy()                 # pair offset at the start of every grid level
         n_pairs = int(level_ptr[-1])
         weights = local = rec = rec_ptr = None
@@ -333,11 +348,8 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
             if p1 > p0:
                 # the fill kernel writes at absolute pair positions: shift the pointers so that the slab's first pair
                 # lands at the start of the scratch buffers (the weights go straight to their final place otherwise)
-                _native.check(lib.rg_geom_fill_f32(
-                    _native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells_from(iz0), _native.ptr(search.xc),
-                    _native.ptr(search.yc), _native.ptr(search.zc) + 4 * iz0, iz1 - iz0, ny, nx, search.min_radius,
-                    search.beam_factor, _native.WEIGHTINGS[weighting], _native.ptr(indptr) + 8 * iz0 * n_xy,
-                    _native.ptr(scratch) - 4 * p0, w_ptr, stream), "rg_geom_fill_f32")
+                search.fill_rows(weighting, _native.ptr(indptr) + 8 * iz0 * n_xy, _native.ptr(scratch) - 4 * p0, w_ptr, iz0,
+                                 iz1 - iz0)
                 max_gate = max(max_gate, int(scratch.max().item()))
             built = CompactCSR._planes(indptr[iz0 * n_xy:iz1 * n_xy + 1], _native.ptr(scratch) - 4 * p0, iz1 - iz0, ny, nx,
                                        l_ptr)

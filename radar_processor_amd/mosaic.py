@@ -25,7 +25,6 @@ Two routes:
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -33,20 +32,17 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native
-from .geometry_builder import WEIGHTINGS, RoiSearch
-from .grid_geometry import DeviceCSR, GridGeometry
+from .geometry_builder import _INT32_MAX, WEIGHTINGS, RoiSearch, csr_from_counts
+from .grid_geometry import GridGeometry
+from .gridding import _stride_for
+from .roi_grid import pack_and_grid
 
-_INT32_MAX = 2 ** 31 - 1
 _GATHER_BYTES = 2 ** 32        # buffer-resource range of the packed-field gather in rg_csr_apply_f32
 
 
 def mosaic_limits(grid_limits, origin) -> Tuple[Tuple[float, float], ...]:
     """The shared grid's limits in the frame of a radar at ``origin = (oz, oy, ox)`` (Python floats)."""
     return tuple((float(lo) - float(o), float(hi) - float(o)) for (lo, hi), o in zip(grid_limits, origin))
-
-
-def _stride_for(n_fields: int) -> int:
-    return 1 if n_fields == 1 else 2 if n_fields == 2 else 4 if n_fields <= 4 else 8
 
 
 def _length(a) -> int:
@@ -160,7 +156,7 @@ def compute_mosaic_geometry(radars, grid_shape, grid_limits, temp_dir: str, min_
     radars = list(radars)
     counts, origins = _check_radars(radars)
     torch = _native.torch_mod()
-    lib = _native.load_library()
+    _native.load_library()
     dev = _native.device()
     nz, ny, nx = (int(s) for s in grid_shape)
     n_vox = nz * ny * nx
@@ -177,7 +173,6 @@ def compute_mosaic_geometry(radars, grid_shape, grid_limits, temp_dir: str, min_
                            device=dev, window=w)
         parts.append(search)
     with torch.cuda.device(dev):
-        stream = _native.stream_ptr()
         total = torch.zeros(n_vox + 1, dtype=torch.int32, device=dev)
         grid_counts = total[:n_vox].view(nz, ny, nx)
         win_counts = []
@@ -185,46 +180,26 @@ def compute_mosaic_geometry(radars, grid_shape, grid_limits, temp_dir: str, min_
             if search is None:
                 win_counts.append(None)
                 continue
-            _, wy, wx = search.grid_shape
-            cnt = torch.zeros(nz * wy * wx, dtype=torch.int32, device=dev)
-            _native.check(lib.rg_geom_count_f32(
-                _native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(search.xc),
-                _native.ptr(search.yc), _native.ptr(search.zc), nz, wy, wx, search.min_radius, search.beam_factor,
-                _native.ptr(cnt), stream), "rg_geom_count_f32")
             iy0, iy1, ix0, ix1 = search.window
-            grid_counts[:, iy0:iy1, ix0:ix1] += cnt.view(nz, wy, wx)
-            win_counts.append(cnt)
-        indptr = torch.empty(n_vox + 1, dtype=torch.int64, device=dev)
-        ws_bytes = int(lib.rg_scan_workspace_bytes(n_vox))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _native.check(lib.rg_scan_counts_i64(_native.ptr(total), n_vox, _native.ptr(indptr), _native.ptr(ws), ws_bytes,
-                                             stream), "rg_scan_counts_i64")
-        del ws, total
-        n_pairs = int(indptr[-1].item())
-        gate_idx = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)[:n_pairs]
-        weights = torch.empty(max(n_pairs, 1), dtype=torch.float32, device=dev)[:n_pairs]
-        # running cursor: indptr plus the counts of the radars already filled.  The fill kernel reads only cursor[v] as the
-        # row base and writes at absolute positions, so every radar fills its segment of each row of its window.
-        cursor = indptr[:n_vox].view(nz, ny, nx).clone()
-        for r, search in enumerate(parts):
-            if search is None or n_pairs == 0:
-                continue
-            _, wy, wx = search.grid_shape
-            iy0, iy1, ix0, ix1 = search.window
-            cur_w = cursor[:, iy0:iy1, ix0:ix1].contiguous()
-            # the radar's gate numbers carry its offset: shift the index column of this build's copy of its sorted gates
-            search.sorted_gates.view(torch.int32).view(-1, 4)[:, 3] += int(offsets[r])
-            _native.check(lib.rg_geom_fill_f32(
-                _native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(search.xc),
-                _native.ptr(search.yc), _native.ptr(search.zc), nz, wy, wx, search.min_radius, search.beam_factor,
-                _native.WEIGHTINGS[weighting], _native.ptr(cur_w), _native.ptr(gate_idx), _native.ptr(weights), stream),
-                "rg_geom_fill_f32")
-            cursor[:, iy0:iy1, ix0:ix1] += win_counts[r].view(nz, wy, wx)
-        del cursor, parts
-        if n_pairs <= _INT32_MAX:
-            indptr = indptr.to(torch.int32)
-        max_gate = int(gate_idx.max().item()) if n_pairs else -1
-    geom = GridGeometry.from_device((nz, ny, nx), grid_limits, DeviceCSR(indptr, gate_idx, weights, max_gate), toa)
+            win_counts.append(search.count_rows()[:-1].view(search.grid_shape))
+            grid_counts[:, iy0:iy1, ix0:ix1] += win_counts[-1]
+
+        def fill(indptr, gate_idx, weights):
+            # running cursor: indptr plus the counts of the radars already filled.  The fill kernel reads only cursor[v] as
+            # the row base and writes at absolute positions, so every radar fills its segment of each row of its window.
+            cursor = indptr[:n_vox].view(nz, ny, nx).clone()
+            for r, search in enumerate(parts):
+                if search is None:
+                    continue
+                iy0, iy1, ix0, ix1 = search.window
+                cur_w = cursor[:, iy0:iy1, ix0:ix1].contiguous()
+                # the radar's gate numbers carry its offset: shift the index column of this build's copy of its sorted gates
+                search.sorted_gates.view(torch.int32).view(-1, 4)[:, 3] += int(offsets[r])
+                search.fill_rows(weighting, _native.ptr(cur_w), _native.ptr(gate_idx), _native.ptr(weights))
+                cursor[:, iy0:iy1, ix0:ix1] += win_counts[r]
+        csr = csr_from_counts(total, n_vox, fill)
+        del parts
+    geom = GridGeometry.from_device((nz, ny, nx), grid_limits, csr, toa)
     geom.gate_offsets = offsets
     geom.origins = origins
     return geom
@@ -457,31 +432,17 @@ def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Seq
 
 
 def _search_grid(search: MosaicSearch, sel, counts, fields, masks, shared_mask, weighting, fill_value, dev):
-    torch = _native.torch_mod()
     lib = _native.load_library()
     nz, ny, nx = search.grid_shape
-    n_vox = nz * ny * nx
-    n_fields = len(fields)
     n_total = sum(counts)
-    offsets = _offsets(counts)[:-1]
-    table = search.table(sel, offsets)
-    out = torch.empty((n_fields, nz, ny, nx), dtype=torch.float32, device=dev)
+    table = search.table(sel, _offsets(counts)[:-1])
     fill = float(np.float32(fill_value))
-    stream = _native.stream_ptr()
-    for f0 in range(0, n_fields, _native.RG_MAX_FIELDS):
-        group = list(range(f0, min(n_fields, f0 + _native.RG_MAX_FIELDS)))
-        nf = len(group)
-        stride = _stride_for(nf)
-        packed = torch.empty(max(n_total, 1) * stride, dtype=torch.float32, device=dev)
-        fptrs = (ctypes.c_void_p * nf)(*[_native.ptr(fields[i]) for i in group])
-        mptrs = (ctypes.c_void_p * nf)(*[_native.ptr(masks[i]) for i in group])
-        _native.check(lib.rg_pack_fields_f32(nf, fptrs, mptrs, _native.ptr(shared_mask), n_total, stride,
-                                             _native.ptr(packed), stream), "rg_pack_fields_f32")
-        out_view = out.view(n_fields, n_vox)[f0:f0 + nf]
+
+    def launch(packed, nf, stride, out_view, stream):
         _native.check(lib.rg_roi_grid_mosaic_f32(
             table, len(sel), nz, ny, nx, search.min_radius, search.beam_factor, _native.WEIGHTINGS[weighting],
             _native.ptr(packed), nf, stride, n_total, fill, _native.ptr(out_view), stream), "rg_roi_grid_mosaic_f32")
-    return out
+    return pack_and_grid(dev, n_total, fields, masks, shared_mask, None, (nz, ny, nx), launch)
 
 
 def _products_of_grids(products, grids, spec) -> List[dict]:

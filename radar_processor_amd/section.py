@@ -14,16 +14,16 @@ NumPy-in / NumPy-out convenience.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _native
-from .geometry_builder import _INT32_MAX, WEIGHTINGS, RoiSearch
-from .grid_geometry import DeviceCSR, GridGeometry
-from .gridding import _coerce_filters, _host_field, _stride_for, _to_host
+from .geometry_builder import WEIGHTINGS, RoiSearch, csr_from_counts
+from .grid_geometry import GridGeometry
+from .gridding import _coerce_filters, _host_field, _to_host
+from .roi_grid import pack_and_grid
 
 
 def section_path(vertices, spacing: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -103,53 +103,28 @@ def section_fields_device(search: RoiSearch, xs, ys, fields: Sequence, masks: Op
     consecutive points being close.  ``fields`` / ``masks`` / ``shared_mask`` / ``fill_value`` / ``out`` as
     :func:`roi_grid_fields_device`.  Returns ``[F, nz, n_points]`` float32."""
     xs, ys = _check_points(search, xs, ys, weighting)
-    n_fields = len(fields)
-    if n_fields == 0:
+    if len(fields) == 0:
         raise ValueError("no fields to grid")
-    torch = _native.torch_mod()
-    dev = search.dev
-    n_gates = search.n_gates
-    for i, f in enumerate(fields):
-        if not (f.is_cuda and f.device == dev and f.dtype == torch.float32 and f.is_contiguous()
-                and f.numel() == n_gates):
-            raise ValueError(f"field {i}: expected a contiguous float32 tensor of {n_gates} gates on {dev}")
-    if masks is None:
-        masks = [None] * n_fields
-    if len(masks) != n_fields:
-        raise ValueError("masks must have one entry (tensor or None) per field")
-    for i, m in enumerate(list(masks) + [shared_mask]):
-        if m is not None and not (m.is_cuda and m.device == dev and m.dtype == torch.uint8 and m.is_contiguous()
-                                  and m.numel() == n_gates):
-            raise ValueError(f"mask {i}: expected a contiguous uint8 tensor of {n_gates} gates on {dev}")
-    nz, n_points = search.grid_shape[0], int(xs.size)
-    n_samples = nz * n_points
-    if out is not None and not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous()
-                                and out.numel() == n_fields * n_samples):
-        # the kernel writes n_fields * nz * n_points floats through a raw pointer: anything else is an out-of-bounds write
-        raise ValueError(f"out must be a contiguous float32 tensor of shape [F, nz, n_points] on {dev}")
-    lib = _native.load_library()
-    if out is None:
-        out = torch.empty((n_fields, nz, n_points), dtype=torch.float32, device=dev)
     fill = float(np.float32(fill_value))
-    with torch.cuda.device(dev):
-        stream = _native.stream_ptr()
-        xs_t, ys_t = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
-        for f0 in range(0, n_fields, _native.RG_MAX_FIELDS):
-            group = list(range(f0, min(n_fields, f0 + _native.RG_MAX_FIELDS)))
-            nf = len(group)
-            stride = _stride_for(nf)
-            packed = torch.empty(max(n_gates, 1) * stride, dtype=torch.float32, device=dev)
-            fptrs = (ctypes.c_void_p * nf)(*[_native.ptr(fields[i]) for i in group])
-            mptrs = (ctypes.c_void_p * nf)(*[_native.ptr(masks[i]) for i in group])
-            _native.check(lib.rg_pack_fields_f32(nf, fptrs, mptrs, _native.ptr(shared_mask), n_gates, stride,
-                                                 _native.ptr(packed), stream), "rg_pack_fields_f32")
-            out_view = out.view(n_fields, n_samples)[f0:f0 + nf]
-            _native.check(lib.rg_roi_section_f32(
-                _native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(xs_t),
-                _native.ptr(ys_t), _native.ptr(search.zc), nz, n_points, search.min_radius, search.beam_factor,
-                _native.WEIGHTINGS[weighting], _native.ptr(packed), nf, stride, fill, _native.ptr(out_view), stream),
-                "rg_roi_section_f32")
-    return out.view(n_fields, nz, n_points)
+    points = []       # the points on the device: copied once, by the first launch -- after everything has been validated
+
+    def launch(packed, nf, stride, out_view, stream):
+        if not points:
+            torch = _native.torch_mod()
+            points.extend((torch.from_numpy(xs).to(search.dev), torch.from_numpy(ys).to(search.dev)))
+        _native.check(_native.load_library().rg_roi_section_f32(
+            *_section_args(search, *points), _native.WEIGHTINGS[weighting], _native.ptr(packed), nf, stride, fill,
+            _native.ptr(out_view), stream), "rg_roi_section_f32")
+    return pack_and_grid(search.dev, search.n_gates, fields, masks, shared_mask, out,
+                         (search.grid_shape[0], int(xs.size)), launch)
+
+
+def _section_args(search: RoiSearch, xs_t, ys_t):
+    """The ten leading arguments of the section entry points: the search structure, the points (device tensors the caller
+    keeps alive), the levels, the ROI."""
+    return (_native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(xs_t),
+            _native.ptr(ys_t), _native.ptr(search.zc), search.grid_shape[0], int(xs_t.numel()), search.min_radius,
+            search.beam_factor)
 
 
 def compute_section_geometry(search: RoiSearch, xs, ys, weighting: str = "barnes2") -> GridGeometry:
@@ -168,29 +143,15 @@ def compute_section_geometry(search: RoiSearch, xs, ys, weighting: str = "barnes
     with torch.cuda.device(dev):
         stream = _native.stream_ptr()
         xs_t, ys_t = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
-        head = (_native.ptr(search.sorted_gates), _native.ptr(search.cell_start), search.cells, _native.ptr(xs_t),
-                _native.ptr(ys_t), _native.ptr(search.zc), nz, n_points, search.min_radius, search.beam_factor)
+        head = _section_args(search, xs_t, ys_t)
         counts = torch.zeros(n_rows + 1, dtype=torch.int32, device=dev)
         _native.check(lib.rg_section_count_f32(*head, _native.ptr(counts), stream), "rg_section_count_f32")
-        indptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
-        ws_bytes = int(lib.rg_scan_workspace_bytes(n_rows))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _native.check(lib.rg_scan_counts_i64(_native.ptr(counts), n_rows, _native.ptr(indptr), _native.ptr(ws), ws_bytes,
-                                             stream), "rg_scan_counts_i64")
-        n_pairs = int(indptr[-1].item())
-        del counts, ws
-        gate_idx = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)[:n_pairs]
-        weights = torch.empty(max(n_pairs, 1), dtype=torch.float32, device=dev)[:n_pairs]
-        if n_pairs:
-            _native.check(lib.rg_section_fill_f32(*head, _native.WEIGHTINGS[weighting], _native.ptr(indptr),
-                                                  _native.ptr(gate_idx), _native.ptr(weights), stream),
-                          "rg_section_fill_f32")
-        if n_pairs <= _INT32_MAX:
-            indptr = indptr.to(torch.int32)       # the reference's dtype (compute.py:232) whenever it fits
-        max_gate = int(gate_idx.max().item()) if n_pairs else -1
+        csr = csr_from_counts(counts, n_rows, lambda indptr, gate_idx, weights: _native.check(lib.rg_section_fill_f32(
+            *head, _native.WEIGHTINGS[weighting], _native.ptr(indptr), _native.ptr(gate_idx), _native.ptr(weights), stream),
+            "rg_section_fill_f32"))
     z_limits = tuple(float(v) for v in search.grid_limits[0])
     geom = GridGeometry.from_device((nz, 1, n_points), (z_limits, (0.0, 0.0), (0.0, _cumulative_distance(xs, ys))),
-                                    DeviceCSR(indptr, gate_idx, weights, max_gate), search.toa)
+                                    csr, search.toa)
     geom.section_x, geom.section_y = xs, ys
     return geom
 
