@@ -191,7 +191,11 @@ typedef struct rg_gate4 { float x, y, z; int32_t index; } rg_gate4; /* 16 bytes:
 /* RG_W_NEAREST is the reference's 'nearest' = uniform mean over the ROI (radar_grid/compute.py:86-87).
  * RG_W_CLOSEST (rg_roi_grid_f32 only) takes the value of the single closest non-excluded gate inside the ROI -- the
  * selection rule of PyART's map_gates_to_grid(weighting_function='nearest') that radar_processor/processor.py:152-163
- * uses behind the 3-D grid cache; PyART is not in the reference tree, so this mode is parity-unpinned. */
+ * uses behind the 3-D grid cache; PyART is not in the reference tree, so this mode is parity-unpinned.  Its contract:
+ * membership is the float64 `d2 < r2` of every mode; among the member gates the field does not exclude, the smallest float32
+ * d2 = fmaf(dz,dz,fmaf(dy,dy,dx*dx)) wins and bit-equal d2 go to the LOWER gate index; the winner's value is stored bit for
+ * bit, fill_value where there is none.  To float64 the winner is at most (1 + 5u)/(1 - 5u), u = 2^-24, farther (in d2) than
+ * the nearest member (oracle.closest_gate_choice derives it; tests/test_gpu_closest.py checks every voxel). */
 typedef enum rg_weighting { RG_W_BARNES2 = 0, RG_W_CRESSMAN = 1, RG_W_NEAREST = 2, RG_W_CLOSEST = 3 } rg_weighting;
 
 /* bytes of scratch rg_geom_bin_gates_f32 needs for n_gates gates */

@@ -652,6 +652,125 @@ def closest_gate_grid(gate_x, gate_y, gate_z, values, excluded, grid_shape, grid
     return out, second
 
 
+_CHOICE_CACHE: dict = {}
+
+
+def closest_gate_choice(gate_x, gate_y, gate_z, excluded, grid_shape, grid_limits, min_radius, beam_factor,
+                        radar_altitude=0.0, toa=np.inf, cache_key=None) -> dict:
+    """Which gate ``rg_roi_grid_f32`` takes in closest-gate mode (``RG_W_CLOSEST``), for EVERY voxel and field, by the rule
+    the kernel documents (radar_processor_amd/csrc/rg_roi_grid.hip) -- nothing is left to a tolerance:
+
+    * gate z: ``z_rel = fl32(gate_z - radar_altitude)``; gates with ``z_rel > toa`` (float32 comparison) or a non-finite
+      coordinate take no part (compute.py:182,193; the binning kernel drops them);
+    * membership: the reference's float64 ``d2 < r2`` from the float32 coordinates, ``r = max(min_radius, beam_factor |v|)``
+      from the float32 voxel centre (compute.py:46-47,69-74; ``roi_rim.voxel_rim`` / ``roi_rim.d2_f64``);
+    * winner of field f (``idx32``): among the members not excluded for f, the minimum of ``(d2f, gate index)`` taken
+      lexicographically, ``d2f`` the kernel's float32 ``fmaf(dz,dz,fmaf(dy,dy,dx*dx))`` (``roi_rim.d2f_kernel``, bit exact);
+      -1 where there is no such member.
+
+    ``excluded``: a sequence of F per-gate boolean arrays (True = excluded for that field; ``None`` = nothing excluded).
+    Returns a dict of ``[F, nz, ny, nx]`` arrays -- ``idx32`` (int64), ``idx64`` (the float64 argmin of d2, ties to the lower
+    index), ``d2_win64`` (float64 d2 of ``idx32``), ``d2_min64`` / ``d2_second64`` (smallest and second smallest float64 d2 of
+    the field's live members, inf where there is none), ``n_tied`` (live members sharing the winning ``d2f``) -- and
+    ``n_members`` ``[nz, ny, nx]`` (members of the voxel whatever the masks).
+
+    What float64 guarantees about ``idx32``.  Each of dx, dy, dz is one float32 rounding of an exact difference of float32
+    values.  ``dx*dx`` is rounded once and then passes through the two fmaf roundings, so the dx^2 term carries the rounding
+    of dx twice (squared) plus three more: (1+u)^5 at most, u = 2^-24; the dy^2 term carries (1+u)^4 and dz^2 (1+u)^3.  All
+    terms are non-negative, so ``d2f = d2 (1 + t)`` with ``|t| <= (1+u)^5 - 1``.  If a is the float32 winner and b the true
+    nearest live member, ``d2f(a) <= d2f(b)`` gives
+
+        d2_64(a) <= d2_64(b) ((1+u) / (1-u))^5  <=  d2_64(b) (1 + 5u) / (1 - 5u)
+
+    (the logarithms are 10u + 10u^3/3 + ... and 10u + 250u^3/3 + ...).  A derived bound, not a measured one
+    (``CLOSEST_D2_BOUND``).  It assumes no underflow: squares in the subnormal range lose relative accuracy, so scenes keep
+    gates either exactly on a voxel centre (d2 = 0, exact) or well away from it.
+
+    ``cache_key``: any hashable; a second call with the same key returns the first call's dict (one evaluation per process,
+    as tests/mosaic_scenes.py caches its CSRs).  Voxels are looped in Python behind a bounding-box cut: small scenes only."""
+    if cache_key is not None and cache_key in _CHOICE_CACHE:
+        return _CHOICE_CACHE[cache_key]
+    from . import roi_rim                      # roi_rim imports this module
+    nz, ny, nx = (int(n) for n in grid_shape)
+    zc, yc, xc = roi_rim.voxel_centres(grid_shape, grid_limits)
+    gx = np.asarray(gate_x, dtype=np.float32).ravel()
+    gy = np.asarray(gate_y, dtype=np.float32).ravel()
+    with np.errstate(invalid="ignore"):
+        z_rel, valid = gate_validity(np.asarray(gate_z, dtype=np.float32).ravel(), radar_altitude, toa)
+    z_rel = np.asarray(z_rel, dtype=np.float32)
+    valid = valid & np.isfinite(gx) & np.isfinite(gy) & np.isfinite(z_rel)
+    n_gates = gx.shape[0]
+    n_f = len(excluded)
+    excl = np.zeros((n_f, n_gates), dtype=bool)
+    for f, m in enumerate(excluded):
+        if m is not None:
+            excl[f] = np.asarray(m, dtype=bool).ravel()
+    keep = np.nonzero(valid)[0]                               # ascending gate index throughout
+    kx, ky, kz = gx[keep].astype(np.float64), gy[keep].astype(np.float64), z_rel[keep].astype(np.float64)
+
+    shape = (n_f, nz, ny, nx)
+    idx32 = np.full(shape, -1, dtype=np.int64)
+    idx64 = np.full(shape, -1, dtype=np.int64)
+    d2_win = np.full(shape, np.inf)
+    d2_min = np.full(shape, np.inf)
+    d2_second = np.full(shape, np.inf)
+    n_tied = np.zeros(shape, dtype=np.int64)
+    n_members = np.zeros((nz, ny, nx), dtype=np.int64)
+    ax = float(np.abs(xc.astype(np.float64)).max())
+    for iz in range(nz):
+        z = float(zc[iz])
+        for iy in range(ny):
+            y = float(yc[iy])
+            # candidates of the row: a box a little wider than the row's largest radius, then the exact tests per voxel
+            r_row = max(min_radius, float(np.sqrt(ax * ax + y * y + z * z)) * beam_factor) * (1.0 + 1e-6) + 1e-3
+            row = np.nonzero((np.abs(ky - y) <= r_row) & (np.abs(kz - z) <= r_row))[0]
+            if row.size == 0:
+                continue
+            rx = kx[row]
+            for ix in range(nx):
+                rim = roi_rim.voxel_rim(xc[ix], yc[iy], zc[iz], min_radius, beam_factor)
+                reach = float(np.sqrt(rim.r2)) * (1.0 + 1e-6) + 1e-3
+                c = keep[row[np.abs(rx - rim.x) <= reach]]
+                if c.size == 0:
+                    continue
+                d2 = roi_rim.d2_f64(gx[c], gy[c], z_rel[c], rim.x, rim.y, rim.z)
+                member = d2 < rim.r2
+                if not member.any():
+                    continue
+                c, d2 = c[member], d2[member]
+                n_members[iz, iy, ix] = c.size
+                d2f = roi_rim.d2f_kernel(gx[c], gy[c], z_rel[c], rim.x, rim.y, rim.z).astype(np.float64)   # exact widening
+                live = ~excl[:, c]                                                      # [F, n]
+                has = live.any(axis=1)
+                if not has.any():
+                    continue
+                k32 = np.where(live, d2f[None, :], np.inf)
+                best = k32.min(axis=1)
+                tied = live & (k32 == best[:, None])
+                first32 = np.argmax(tied, axis=1)              # c ascends: the first tied entry is the lowest gate index
+                k64 = np.where(live, d2[None, :], np.inf)
+                first64 = np.argmin(k64, axis=1)               # argmin returns the first minimum: the lowest index
+                if c.size > 1:
+                    second = np.partition(k64, 1, axis=1)[:, 1]
+                else:
+                    second = np.full(n_f, np.inf)
+                idx32[has, iz, iy, ix] = c[first32[has]]
+                idx64[has, iz, iy, ix] = c[first64[has]]
+                d2_win[has, iz, iy, ix] = d2[first32[has]]
+                d2_min[has, iz, iy, ix] = d2[first64[has]]
+                d2_second[has, iz, iy, ix] = second[has]
+                n_tied[has, iz, iy, ix] = tied.sum(axis=1)[has]
+    out = dict(idx32=idx32, idx64=idx64, d2_win64=d2_win, d2_min64=d2_min, d2_second64=d2_second, n_tied=n_tied,
+               n_members=n_members)
+    if cache_key is not None:
+        _CHOICE_CACHE[cache_key] = out
+    return out
+
+
+# d2_win64 <= d2_min64 * CLOSEST_D2_BOUND on every filled voxel (derived in closest_gate_choice's docstring)
+CLOSEST_D2_BOUND = (1.0 + 5.0 * U32) / (1.0 - 5.0 * U32)
+
+
 # --------------------------------------------------------------------------------------------------
 # 2-D raster stage behind the 3-D grid cache (SURVEY.md §8(f) rows 3 and 4)
 #

@@ -385,6 +385,13 @@ int launch(const char* fn, const Args& a, const float* packed, float fill, float
 
 }  // namespace
 
+// Closest-gate mode (RG_W_CLOSEST), the contract: membership as in every mode (in_roi: the reference's float64 d2 < r2 decides
+// at the rim); among the members a field does not exclude, the smallest float32 d2 (in_roi's fmaf(dz,dz,fmaf(dy,dy,dx*dx)))
+// wins, and bit-equal d2 go to the LOWER gate index -- in keep_closest within a lane and in the cross-slot fold alike, so the
+// choice does not depend on the order or the slot in which the candidates arrive (cell size, per-level lists, ring drains).
+// The value is copied, never computed with: its bits arrive unchanged.  To float64 the winner's d2 is at most
+// (1 + 5u) / (1 - 5u) times the nearest member's, u = 2^-24 (one rounding per coordinate difference, three more on the dx^2
+// term, all terms non-negative).  oracle.closest_gate_choice restates the rule; tests/test_gpu_closest.py checks every voxel.
 extern "C" int rg_roi_grid_f32(const rg_gate4* sorted_gates, const int32_t* cell_start, const rg_cellgrid* cells_host,
                                const float* xc, const float* yc, const float* zc, int32_t nz, int32_t ny, int32_t nx,
                                double min_radius, double beam_factor, int32_t weighting, const float* packed,
