@@ -38,7 +38,8 @@ extern "C" {
  * rg_csr_compact_pack and rg_csr_compact_apply_packed_f32 (round 3); 102 rg_csr_compact_apply_columns_f32, diagnostic tile
  * codes refused by the product build (round 4); 103 the row-wise kernel of rg_csr_compact_apply_packed_f32 takes 1-8 fields
  * (no signature changed: a 102 library answers RG_EUNSUPPORTED for 5-8); 104 rg_cellgrid.levels + the per-level gate lists
- * (rg_geom_bin_levels_count / rg_geom_bin_gates_levels_f32). */
+ * (rg_geom_bin_levels_count / rg_geom_bin_gates_levels_f32); still 104: the packed records' two codings -- no signature
+ * changed, rg_csr_compact_pack_dense was ADDED (a library without it fails to bind by name) and rg_csr_compact_pack refuses work. */
 #define RG_VERSION 104
 #define RG_MAX_FIELDS 8
 
@@ -428,9 +429,20 @@ int rg_csr_compact_apply_f32(const void* indptr, int32_t indptr_is_i64, const ui
                              int32_t stride, int64_t n_gates, float fill_value, float* out, int32_t window_cap,
                              int32_t tile, rg_stream_t stream);
 
-/* Packed pair stream of the compact copy: positions and weights of three consecutive pairs of a segment in one 16-byte
- * record -- 5.33 bytes per pair instead of 6, streamed with one 16-byte load per lane.
- *   record = [w0:26 | p2 bits 0-5] [w1:26 | p2 bits 6-11] [w2:26 | p2 bits 12-15] [p0:16 | p1:16]   (4 x uint32)
+/* Packed pair stream of the compact copy: positions and weights of three consecutive pairs of a segment in one record,
+ * streamed with one aligned 16-byte load per lane.  The coding of a chunk's records follows from the size of its dictionary
+ * (dict_ptr[chunk + 1] - dict_ptr[chunk]), which every reader has at hand:
+ *   WIDE, more than RG_DENSE_MAX_DICT entries: 16 bytes, 16-bit positions, 5.33 bytes per pair; record q at byte 16 * q
+ *     record = [w0:26 | p2 bits 0-5] [w1:26 | p2 bits 6-11] [w2:26 | p2 bits 12-15] [p0:16 | p1:16]   (4 x uint32)
+ *   DENSE, at most RG_DENSE_MAX_DICT entries: 14 bytes, 11-bit positions, 4.67 bytes per pair; record q at byte 14 * q of
+ *     its segment's records.  M1 = w0:26 | p1 bits 0-5, M2 = w1:26 | p2 bits 0-5, W2 = w2:26 | p2 bits 6-10, P = p0:11 |
+ *     p1 bits 6-10 (16 bits), stored as little-endian halfwords
+ *       q even: W2.lo W2.hi M1.lo M1.hi M2.lo M2.hi P        q odd: W2.lo M1.lo M1.hi M2.lo M2.hi W2.hi P
+ *     so that the aligned 16 bytes at (14 * q) & ~3 hold M1 and M2 in dwords 1 and 2 whatever the parity of q, and W2 and
+ *     P come out of dwords 0 and 3 with one funnel shift by 16 * (q & 1) (csrc/rg_compact_layout.hpp: rec_decode /
+ *     rec_encode_dense).
+ * rec_ptr counts 16-byte UNITS: every segment starts on a 16-byte boundary and takes n units (wide) or ceil(14 * n / 16)
+ * units (dense) for its n = ceil(pairs / 3) records.
  *   weight code = float32 bits of the weight - w_base; w_base has its low 26 bits clear (an exponent that is a multiple of
  *   8, shifted left by 23), so adding it back is an OR; the caller guarantees that every code fits 26 bits (all weights
  *   positive, exponents w_base >> 23 .. (w_base >> 23) + 7), which makes the coding lossless.
@@ -442,7 +454,7 @@ int rg_csr_compact_apply_f32(const void* indptr, int32_t indptr_is_i64, const ui
  *                          past the end of a plane are empty).  The four segments of a workgroup are then neighbours in
  *                          the stream and consecutive workgroups read consecutive stretches of it: whatever the physical
  *                          placement of the array, the launch reads it as ONE moving front.
- * rec_ptr is built by the caller.  rg_csr_compact_pack fills `records` from local_idx + weights (error_flag: 1 = rec_ptr
+ * rec_ptr is built by the caller.  rg_csr_compact_pack_dense fills `records` from local_idx + weights (error_flag: 1 = rec_ptr
  * inconsistent with indptr, 2 = a weight outside the code, 4 = a segment with 2^27 records or more); for a slab of whole
  * planes of a larger grid pass the slab's indptr / n_rows, rec_ptr + the slab's first slot and plane0 = its first plane.
  * rg_csr_compact_apply_packed_f32 grids 1-8 fused fields (row-wise kernel; the tile kernel over the records: 1-4) through
@@ -465,6 +477,15 @@ int rg_csr_compact_apply_f32(const void* indptr, int32_t indptr_is_i64, const ui
  * window_cap as for rg_csr_compact_apply_f32; the row-wise kernel keeps one entry more (an all-EXCLUDED sentinel). */
 #define RG_REC_ORDER_SEGMENT 0
 #define RG_REC_ORDER_DISPATCH 1
+#define RG_DENSE_MAX_DICT 2048
+/* rg_csr_compact_pack_dense is the packer: rg_csr_compact_pack's arguments plus `dict_ptr` ([chunks + 1] of the grid -- or
+ * of the slab -- the row pointers describe; only the differences of neighbouring entries are read), from which it takes
+ * every chunk's coding.  rg_csr_compact_pack itself knows no dictionary sizes and therefore cannot choose a coding: it is
+ * kept for binary compatibility and returns RG_EUNSUPPORTED whenever there is something to pack. */
+int rg_csr_compact_pack_dense(const void* indptr, int32_t indptr_is_i64, const uint16_t* local_idx, const float* weights,
+                              int64_t n_rows, int64_t line_len, int64_t lines_per_plane, const int64_t* dict_ptr,
+                              const int64_t* rec_ptr, int32_t rec_order, int64_t plane0, uint32_t w_base, void* records,
+                              int32_t* error_flag, rg_stream_t stream);
 int rg_csr_compact_pack(const void* indptr, int32_t indptr_is_i64, const uint16_t* local_idx, const float* weights,
                         int64_t n_rows, int64_t line_len, int64_t lines_per_plane, const int64_t* rec_ptr,
                         int32_t rec_order, int64_t plane0, uint32_t w_base, void* records, int32_t* error_flag,

@@ -34,6 +34,7 @@ RG_COMPACT_LINES = 4          # grid lines (= wavefronts) per chunk of the compa
 RG_COMPACT_MAX_WINDOW = 8192
 RG_COMPACT_ROTATION = 5       # block -> chunk column rotation per line group (header: RG_COMPACT_ROTATION)
 RG_REC_ORDER_SEGMENT, RG_REC_ORDER_DISPATCH = 0, 1
+RG_DENSE_MAX_DICT = 2048      # chunks with at most this many dictionary entries keep 14-byte records (header: RG_DENSE_MAX_DICT)
 
 
 class NativeUnavailable(RuntimeError):
@@ -110,6 +111,8 @@ SIGNATURES = {
                                            c_int32, c_int32, c_void_p]),
     "rg_csr_compact_pack": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                       c_int32, c_int64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p]),
+    "rg_csr_compact_pack_dense": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                            c_void_p, c_int32, c_int64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p]),
     "rg_csr_compact_apply_packed_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, ctypes.c_uint32, c_void_p,
                                                   c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32,
                                                   c_int32, c_int64, c_float, c_void_p, c_int32, c_int32, c_void_p]),

@@ -121,6 +121,74 @@ __device__ __forceinline__ Segment chunk_segment(const ChunkGrid& g, unsigned ch
 
 using rg::stride_for;
 
+// ---- the packed records: two codings, chosen per CHUNK by the size of its dictionary ---------------------------------------
+// A record is three consecutive pairs of a segment: three 26-bit weight codes (float32 bits - w_base) and three positions.
+//   WIDE  (16 bytes, 16-bit positions), every chunk with more than RG_DENSE_MAX_DICT dictionary entries (split chunks too):
+//     [w0:26 | p2 bits 0-5] [w1:26 | p2 bits 6-11] [w2:26 | p2 bits 12-15] [p0:16 | p1:16]; record q at byte 16 * q.
+//   DENSE (14 bytes, 11-bit positions), every chunk with at most RG_DENSE_MAX_DICT = 2048 entries.  Three words and a half:
+//     M1 = w0:26 | p1 bits 0-5     M2 = w1:26 | p2 bits 0-5     W2 = w2:26 | p2 bits 6-10 | 0     P = p0:11 | p1 bits 6-10  (16 bits)
+//     stored as seven little-endian halfwords from byte 14 * q of the segment's (16-byte aligned) records:
+//       q even:  W2.lo W2.hi M1.lo M1.hi M2.lo M2.hi P           q odd:  W2.lo M1.lo M1.hi M2.lo M2.hi W2.hi P
+//     A reader loads the ALIGNED 16 bytes d0..d3 at (14 * q) & ~3 -- the record starts at byte 0 of the load when q is even
+//     and at byte 2 when it is odd -- and finds M1 = d1 and M2 = d2 either way.  With sh = 16 * (q & 1):
+//       W2 = ({d3, d0} >> sh) & 0xFFFFFFFF  (one v_alignbit_b32: d0 itself, or d0.hi | d3.lo << 16)      P = (d3 >> sh) & 0xFFFF
+//     so the parity costs one funnel shift and two bit-field offsets, no select.
+// rec_ptr counts 16-byte UNITS in both codings: a segment of n records starts on a 16-byte boundary and takes n units (wide)
+// or ceil(14 * n / 16) units (dense); the last record's load never leaves them (n odd leaves >= 2 bytes of padding).
+constexpr int kDenseMaxDict = RG_DENSE_MAX_DICT;
+__host__ __device__ inline bool rec_is_dense(long nd_all) { return nd_all <= kDenseMaxDict; }
+__host__ __device__ inline long rec_units(long n_rec, bool dense) { return dense ? (14 * n_rec + 15) >> 4 : n_rec; }
+
+struct RecFields {      // a decoded record: weight codes still carry the position bits above bit 25
+  unsigned wc[3];
+  unsigned pos[3];
+};
+
+// `ld`: the 16 bytes loaded for the record; `par` (dense only): any word whose bit 0 is the parity of the record's number in
+// its segment.  Shift amounts reach the instructions unmasked where the hardware takes them modulo 32 anyway.
+template <bool DENSE>
+__device__ __forceinline__ RecFields rec_decode(const rg_u32x4& ld, unsigned par) {
+  RecFields r;
+  if constexpr (DENSE) {
+    const unsigned sh = par << 4;                                   // v_alignbit_b32 / v_bfe_u32 read bits 0-4 of it: 0 or 16
+    const unsigned w2 = __builtin_amdgcn_alignbit(ld.w, ld.x, sh);
+    r.wc[0] = ld.y;
+    r.wc[1] = ld.z;
+    r.wc[2] = w2;
+    r.pos[0] = __builtin_amdgcn_ubfe(ld.w, sh, 11u);
+    const unsigned p1h = __builtin_amdgcn_ubfe(ld.w, sh + 11u, 5u);
+    r.pos[1] = __builtin_amdgcn_alignbit(p1h, ld.y, 26);           // ld.y >> 26 | p1h << 6
+    r.pos[2] = __builtin_amdgcn_alignbit(w2 >> 26, ld.z, 26);      // ld.z >> 26 | (w2 >> 26) << 6
+  } else {
+    r.wc[0] = ld.x;
+    r.wc[1] = ld.y;
+    r.wc[2] = ld.z;
+    r.pos[0] = ld.w & 0xFFFFu;
+    r.pos[1] = ld.w >> 16;
+    unsigned p2b = ld.y >> 26, p2c = ld.z >> 26;
+    asm volatile("" : "+v"(p2b), "+v"(p2c));     // keep the shifts apart: each OR then folds into a v_lshl_or_b32
+    r.pos[2] = (p2c << 12) | ((p2b << 6) | (ld.x >> 26));
+  }
+  return r;
+}
+
+// The seven halfwords of a dense record in storage order (the pack kernel; the inverse of rec_decode<true>).
+__device__ __forceinline__ void rec_encode_dense(const unsigned (&code)[3], const unsigned (&pos)[3], bool odd, unsigned short (&h)[7]) {
+  const unsigned m1 = (code[0] & 0x3FFFFFFu) | ((pos[1] & 0x3Fu) << 26);
+  const unsigned m2 = (code[1] & 0x3FFFFFFu) | ((pos[2] & 0x3Fu) << 26);
+  const unsigned w2 = (code[2] & 0x3FFFFFFu) | (((pos[2] >> 6) & 0x1Fu) << 26);
+  const unsigned short p = (unsigned short)((pos[0] & 0x7FFu) | (((pos[1] >> 6) & 0x1Fu) << 11));
+  const unsigned short m1l = (unsigned short)m1, m1h = (unsigned short)(m1 >> 16), m2l = (unsigned short)m2,
+                       m2h = (unsigned short)(m2 >> 16), w2h = (unsigned short)(w2 >> 16);
+  h[0] = (unsigned short)w2;
+  h[1] = odd ? m1l : w2h;
+  h[2] = odd ? m1h : m1l;
+  h[3] = odd ? m2l : m1h;
+  h[4] = odd ? m2h : m2l;
+  h[5] = odd ? w2h : m2h;
+  h[6] = p;
+}
+
 bool make_chunk_grid(int64_t n_rows, int64_t line_len, int64_t lines_per_plane, ChunkGrid* cg) {
   if (line_len <= 0) line_len = n_rows > 0 ? n_rows : 1;
   if (n_rows % line_len != 0) return false;

@@ -29,13 +29,15 @@
 // interchange format.
 //
 // Roofline: HBM.  Bytes per launch = 6*P + 4*D + sizeof(indptr)*(V+1) + 8*(C+1) + F*(5*G + 4*V)  with D = total
-// dictionary entries, C = chunks; with the packed records (see rg_csr_compact_pack) 16*R + 8*(S+1) replace 6*P.
+// dictionary entries, C = chunks; with the packed records (see rg_csr_compact_pack_dense) 16*U + 8*(S+1) replace 6*P, U = the
+// 16-byte units the records take: ceil(14 n / 16) per segment of n records in a chunk of at most 2048 gates, n elsewhere.
 #include "rg_compact_layout.hpp"
 
 namespace {
 
-// PACKED: positions and weights come from 16-byte records of three pairs each (see rg_csr_compact_pack) instead of the
-// 2-byte position and 4-byte weight arrays: 5.33 instead of 6 bytes per pair, one dwordx4 per lane and 192 pairs.
+// PACKED: positions and weights come from records of three pairs each (see rg_csr_compact_pack_dense: 14 or 16 bytes, by the
+// chunk's dictionary size) instead of the 2-byte position and 4-byte weight arrays: 4.67 / 5.33 instead of 6 bytes per pair, one
+// aligned dwordx4 per lane and 192 pairs.
 template <typename IndT, int NF, int STRIDE, int TILE, bool PACKED = false>
 __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
     const IndT* __restrict__ indptr, const uint16_t* __restrict__ lidx, const float* __restrict__ wts,
@@ -96,7 +98,9 @@ __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
   const uint16_t* __restrict__ li = lidx + seg_b;
   const float* __restrict__ wi = wts + seg_b;
   const int lane2 = lane * 2, lane4 = lane * 4;
-  long rec_b = 0, rec_n = 0;                 // this segment's records (PACKED)
+  long rec_b = 0, rec_n = 0;                 // this segment's records (PACKED), in 16-byte units
+  const bool dense = PACKED && rec_is_dense(nd_all);                        // 14-byte records (rg_compact_layout.hpp)
+  const int rec_off = dense ? lane * 14 - (lane & 1) * 2 : lane * 16;       // the lane's aligned load within a wave-load
   if constexpr (PACKED) {
     if (nrows) {
       const long slot = rec_order == RG_REC_ORDER_DISPATCH ? (long)blockIdx.x * kH + wv : sg.seg;
@@ -106,10 +110,12 @@ __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
   }
   auto stream = [&](Stage& sgs, int t) {   // t wave-uniform: the resources live in SGPRs
     if constexpr (PACKED) {
-      const long r_t = t / 3;               // tiles are multiples of 192 pairs = 64 records
-      const rsrc_t rr = make_rsrc(rec + rec_b + r_t, (rec_n - r_t) * 16);
+      const long r_t = t / 3;               // tiles are multiples of 192 pairs = 64 records: they start on an even record
+      const long rbytes = r_t * (dense ? 14 : 16);
+      const rsrc_t rr = make_rsrc(reinterpret_cast<const char*>(rec + rec_b) + rbytes, rec_n * 16 - rbytes);
+      const int step = dense ? 64 * 14 : 1024;
 #pragma unroll
-      for (int k = 0; k < IT / 3; ++k) sgs.r[k] = rg_buffer_load_v4u32(rr, lane * 16 + k * 1024, 0, 0);
+      for (int k = 0; k < IT / 3; ++k) sgs.r[k] = rg_buffer_load_v4u32(rr, rec_off + k * step, 0, 0);
     } else {
       const rsrc_t ri = make_rsrc(li + t, ((long)span - t) * 2);
       const rsrc_t rw = make_rsrc(wi + t, ((long)span - t) * 4);
@@ -121,19 +127,18 @@ __global__ __launch_bounds__(64 * kH) void csr_compact_kernel(
     }
   };
   // pair slot `it` of a stage -> (position, weight) and its index in the tile.  Plain: pair it*64 + lane.  Packed: lane
-  // holds record k = it / 3 of the tile's k-th wave-load, i.e. pairs k*192 + 3*lane + (it % 3); a record is
-  // [w0:26 | p2[0:6]] [w1:26 | p2[6:12]] [w2:26 | p2[12:16]] [p0:16 | p1:16], w = float32 bits minus w_base.
+  // holds record k = it / 3 of the tile's k-th wave-load, i.e. pairs k*192 + 3*lane + (it % 3); the record's coding
+  // (16 bytes, or 14 in a chunk of at most 2048 gates) is rg_compact_layout.hpp's; w = float32 bits minus w_base.
   auto decode = [&](const Stage& sgs, int (&ci)[IT], float (&cw)[IT]) {
     if constexpr (PACKED) {
 #pragma unroll
       for (int k = 0; k < IT / 3; ++k) {
-        const rg_u32x4 q = sgs.r[k];
-        cw[3 * k] = __builtin_bit_cast(float, (q.x & 0x3FFFFFFu) + w_base);
-        cw[3 * k + 1] = __builtin_bit_cast(float, (q.y & 0x3FFFFFFu) + w_base);
-        cw[3 * k + 2] = __builtin_bit_cast(float, (q.z & 0x3FFFFFFu) + w_base);
-        ci[3 * k] = (int)(q.w & 0xFFFFu);
-        ci[3 * k + 1] = (int)(q.w >> 16);
-        ci[3 * k + 2] = (int)((q.x >> 26) | ((q.y >> 26) << 6) | ((q.z >> 26) << 12));
+        const RecFields f = dense ? rec_decode<true>(sgs.r[k], (unsigned)lane) : rec_decode<false>(sgs.r[k], 0u);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          cw[3 * k + j] = __builtin_bit_cast(float, (f.wc[j] & 0x3FFFFFFu) + w_base);
+          ci[3 * k + j] = (int)f.pos[j];
+        }
       }
     } else {
 #pragma unroll
@@ -362,14 +367,19 @@ extern "C" int rg_csr_compact_apply_f32(const void* indptr, int32_t indptr_is_i6
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Packed pair stream: positions AND weights of three consecutive pairs of a segment in one 16-byte record.
+// Packed pair stream: positions AND weights of three consecutive pairs of a segment in one record.
 //   weight code = float32 bits of the weight minus w_base (= smallest exponent among the geometry's weights << 23); it
 //   must fit 26 bits, i.e. all weights positive and within 8 binades -- Barnes weights span exp(-4)+1e-5 .. 1+1e-5, 7
 //   binades; the host checks and falls back to the plain arrays otherwise.  Lossless: the kernel adds w_base back.
-//   record = [w0:26 | p2 bits 0-5] [w1:26 | p2 bits 6-11] [w2:26 | p2 bits 12-15] [p0:16 | p1:16]
-//   Every segment (one wavefront's rows) starts a new record; rec_ptr[seg] = its first record, segments numbered
-//   line-major (line * ceil(line_len / 64) + sx).  5.33 bytes per pair instead of 6, and the kernel streams them with one
-//   dwordx4 per lane and 192 pairs instead of six 2- and 4-byte loads.
+//   Two codings (bit layouts: rg_compact_layout.hpp), chosen per CHUNK from the size of its dictionary, which every reader
+//   has at hand -- no flag travels with the records:
+//     more than 2048 entries (the chunks at the radar, split chunks):  16 bytes, 16-bit positions, 5.33 bytes per pair
+//     at most 2048 entries (99.9 % of the bench geometry's pairs):     14 bytes, 11-bit positions, 4.67 bytes per pair
+//   The LOGICAL record is the same in both: record q of a segment holds its pairs 3q .. 3q + 2, so lanes, batch slots,
+//   chains and the order of the adds do not know which coding they read.
+//   Every segment (one wavefront's rows) starts on a 16-byte boundary; rec_ptr[slot] = its first 16-byte unit, and it takes
+//   ceil(pairs / 3) units (wide) or ceil(14 * ceil(pairs / 3) / 16) (dense, the padding zeroed).  A dense record is read with
+//   the aligned dwordx4 at (14 q) & ~3 -- its bytes start at byte 0 (q even) or 2 (q odd) of the load.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -377,7 +387,8 @@ template <typename IndT>
 __global__ __launch_bounds__(256) void compact_pack_kernel(const IndT* __restrict__ indptr,
                                                             const uint16_t* __restrict__ lidx,
                                                             const float* __restrict__ wts, ChunkGrid cg, long n_slots,
-                                                            int rec_order, const int64_t* __restrict__ rec_ptr,
+                                                            int rec_order, const int64_t* __restrict__ dict_ptr,
+                                                            const int64_t* __restrict__ rec_ptr,
                                                             unsigned w_base, rg_u32x4* __restrict__ rec,
                                                             int32_t* __restrict__ error_flag) {
   const int lane = threadIdx.x & 63;
@@ -385,9 +396,11 @@ __global__ __launch_bounds__(256) void compact_pack_kernel(const IndT* __restric
   if (slot >= n_slots) return;
   long r0;
   int nrows;
+  unsigned chunk;
   if (rec_order == RG_REC_ORDER_DISPATCH) {      // slot = block * H + wavefront: the segment that wavefront reads
     const unsigned bid = (unsigned)(slot / kH);
-    const Segment sg = chunk_segment(cg, block_chunk(cg, bid), (int)(slot - (long)bid * kH));
+    chunk = block_chunk(cg, bid);
+    const Segment sg = chunk_segment(cg, chunk, (int)(slot - (long)bid * kH));
     r0 = sg.r0;
     nrows = sg.nrows;
   } else {                                       // slot = segment number, line-major
@@ -396,12 +409,17 @@ __global__ __launch_bounds__(256) void compact_pack_kernel(const IndT* __restric
     const unsigned x0 = sx * cg.seg_base + (sx < cg.seg_extra ? sx : cg.seg_extra);
     r0 = line * cg.line_len + x0;
     nrows = (int)(cg.seg_base + (sx < cg.seg_extra ? 1u : 0u));
+    const long plane = line / cg.lines_per_plane;
+    chunk = (unsigned)((plane * cg.nyg + (line - plane * cg.lines_per_plane) / kH) * cg.nsx + sx);
   }
+  const bool dense = rec_is_dense(dict_ptr[chunk + 1] - dict_ptr[chunk]);     // the coding of this chunk's records
   const long p0 = nrows ? (long)indptr[r0] : 0, p1 = nrows ? (long)indptr[r0 + nrows] : 0;
-  const long rb = rec_ptr[slot], rn = rec_ptr[slot + 1] - rb;
-  if (lane == 0 && rn != (p1 - p0 + 2) / 3) atomicOr(error_flag, 1);
+  const long rn = (p1 - p0 + 2) / 3;             // records; rec_ptr counts 16-byte units
+  const long rb = rec_ptr[slot], units = rec_ptr[slot + 1] - rb;
+  if (lane == 0 && units != rec_units(rn, dense)) atomicOr(error_flag, 1);
   if (lane == 0 && rn >= (1L << 27)) atomicOr(error_flag, 4);   // the apply kernels use 32-bit byte offsets per segment
-  if (rn != (p1 - p0 + 2) / 3) return;           // never write outside the records rec_ptr gives this segment
+  if (units != rec_units(rn, dense)) return;     // never write outside the units rec_ptr gives this segment
+  unsigned short* const half = reinterpret_cast<unsigned short*>(rec + rb);
   for (long r = lane; r < rn; r += 64) {
     unsigned code[3], pos[3];
 #pragma unroll
@@ -414,49 +432,74 @@ __global__ __launch_bounds__(256) void compact_pack_kernel(const IndT* __restric
         code[j] = bits - w_base;
         if (bits < w_base || code[j] > 0x3FFFFFFu) atomicOr(error_flag, 2);   // not codable: the host checked, so never
         pos[j] = lidx[p];
+        if (dense && pos[j] >= (unsigned)kDenseMaxDict) atomicOr(error_flag, 8);   // a position outside its dictionary
       }
     }
-    rg_u32x4 q;
-    q.x = (code[0] & 0x3FFFFFFu) | ((pos[2] & 0x3Fu) << 26);
-    q.y = (code[1] & 0x3FFFFFFu) | (((pos[2] >> 6) & 0x3Fu) << 26);
-    q.z = (code[2] & 0x3FFFFFFu) | (((pos[2] >> 12) & 0xFu) << 26);
-    q.w = pos[0] | (pos[1] << 16);
-    rec[rb + r] = q;
+    if (dense) {
+      unsigned short h[7];
+      rec_encode_dense(code, pos, (r & 1) != 0, h);
+#pragma unroll
+      for (int j = 0; j < 7; ++j) half[7 * r + j] = h[j];
+    } else {
+      rg_u32x4 q;
+      q.x = (code[0] & 0x3FFFFFFu) | ((pos[2] & 0x3Fu) << 26);
+      q.y = (code[1] & 0x3FFFFFFu) | (((pos[2] >> 6) & 0x3Fu) << 26);
+      q.z = (code[2] & 0x3FFFFFFu) | (((pos[2] >> 12) & 0xFu) << 26);
+      q.w = pos[0] | (pos[1] << 16);
+      rec[rb + r] = q;
+    }
   }
+  if (dense && 7 * rn + lane < 8 * units) half[7 * rn + lane] = 0;   // the padding up to the next unit (at most 7 halfwords)
 }
 
 }  // namespace
 
-extern "C" int rg_csr_compact_pack(const void* indptr, int32_t indptr_is_i64, const uint16_t* local_idx,
-                                   const float* weights, int64_t n_rows, int64_t line_len, int64_t lines_per_plane,
-                                   const int64_t* rec_ptr, int32_t rec_order, int64_t plane0, uint32_t w_base,
-                                   void* records, int32_t* error_flag, rg_stream_t stream) {
-  RG_REQUIRE(n_rows >= 0 && plane0 >= 0, RG_EINVAL, "rg_csr_compact_pack: negative size");
+extern "C" int rg_csr_compact_pack_dense(const void* indptr, int32_t indptr_is_i64, const uint16_t* local_idx,
+                                         const float* weights, int64_t n_rows, int64_t line_len, int64_t lines_per_plane,
+                                         const int64_t* dict_ptr, const int64_t* rec_ptr, int32_t rec_order, int64_t plane0,
+                                         uint32_t w_base, void* records, int32_t* error_flag, rg_stream_t stream) {
+  RG_REQUIRE(n_rows >= 0 && plane0 >= 0, RG_EINVAL, "rg_csr_compact_pack_dense: negative size");
   RG_REQUIRE(rec_order == RG_REC_ORDER_SEGMENT || rec_order == RG_REC_ORDER_DISPATCH, RG_EINVAL,
-             "rg_csr_compact_pack: rec_order=%d is neither RG_REC_ORDER_SEGMENT nor RG_REC_ORDER_DISPATCH", rec_order);
+             "rg_csr_compact_pack_dense: rec_order=%d is neither RG_REC_ORDER_SEGMENT nor RG_REC_ORDER_DISPATCH", rec_order);
   if (n_rows == 0) return RG_OK;
-  RG_REQUIRE(indptr && rec_ptr && error_flag, RG_EINVAL, "rg_csr_compact_pack: null pointer");
-  RG_REQUIRE(rg::aligned16(records), RG_EALIGN, "rg_csr_compact_pack: records must be 16-byte aligned");
+  RG_REQUIRE(indptr && dict_ptr && rec_ptr && error_flag, RG_EINVAL, "rg_csr_compact_pack_dense: null pointer");
+  RG_REQUIRE(rg::aligned16(records), RG_EALIGN, "rg_csr_compact_pack_dense: records must be 16-byte aligned");
   ChunkGrid cg;
   RG_REQUIRE(make_chunk_grid(n_rows, line_len, lines_per_plane, &cg), RG_EINVAL,
-             "rg_csr_compact_pack: n_rows=%ld is not planes x lines_per_plane=%ld x line_len=%ld", (long)n_rows,
+             "rg_csr_compact_pack_dense: n_rows=%ld is not planes x lines_per_plane=%ld x line_len=%ld", (long)n_rows,
              (long)lines_per_plane, (long)line_len);
-  RG_REQUIRE(chunk_count(cg) <= 0x7FFFFFFFL / kH, RG_EUNSUPPORTED, "rg_csr_compact_pack: too many chunks for one launch");
+  RG_REQUIRE(chunk_count(cg) <= 0x7FFFFFFFL / kH, RG_EUNSUPPORTED, "rg_csr_compact_pack_dense: too many chunks for one launch");
   cg.grp0 = (unsigned)(((unsigned long)plane0 * cg.nyg) & 0xFFFFFFFFul);   // the rotation counts line groups mod 2^32
   const long n_slots = rec_order == RG_REC_ORDER_DISPATCH ? chunk_count(cg) * kH
                                                           : cg.n_planes * cg.lines_per_plane * (long)cg.nsx;
   const long blocks = (n_slots + 3) / 4;
-  RG_REQUIRE(blocks <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_pack: too many segments for one launch");
+  RG_REQUIRE(blocks <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_pack_dense: too many segments for one launch");
   hipStream_t s = (hipStream_t)stream;
   if (indptr_is_i64)
     hipLaunchKernelGGL(compact_pack_kernel<int64_t>, dim3((unsigned)blocks), dim3(256), 0, s,
-                       static_cast<const int64_t*>(indptr), local_idx, weights, cg, n_slots, rec_order, rec_ptr, w_base,
+                       static_cast<const int64_t*>(indptr), local_idx, weights, cg, n_slots, rec_order, dict_ptr, rec_ptr, w_base,
                        static_cast<rg_u32x4*>(records), error_flag);
   else
     hipLaunchKernelGGL(compact_pack_kernel<int32_t>, dim3((unsigned)blocks), dim3(256), 0, s,
-                       static_cast<const int32_t*>(indptr), local_idx, weights, cg, n_slots, rec_order, rec_ptr, w_base,
+                       static_cast<const int32_t*>(indptr), local_idx, weights, cg, n_slots, rec_order, dict_ptr, rec_ptr, w_base,
                        static_cast<rg_u32x4*>(records), error_flag);
-  return rg::check_launch("rg_csr_compact_pack");
+  return rg::check_launch("rg_csr_compact_pack_dense");
+}
+
+// The packer of the 16-byte-only stream: it is given no dictionary sizes, so it cannot tell which chunks take the dense
+// coding that every reader expects.  Kept exported with its signature; refuses any work.
+extern "C" int rg_csr_compact_pack(const void* indptr, int32_t indptr_is_i64, const uint16_t* local_idx,
+                                   const float* weights, int64_t n_rows, int64_t line_len, int64_t lines_per_plane,
+                                   const int64_t* rec_ptr, int32_t rec_order, int64_t plane0, uint32_t w_base,
+                                   void* records, int32_t* error_flag, rg_stream_t stream) {
+  (void)indptr; (void)indptr_is_i64; (void)local_idx; (void)weights; (void)line_len; (void)lines_per_plane; (void)rec_ptr;
+  (void)w_base; (void)records; (void)error_flag; (void)stream;
+  RG_REQUIRE(n_rows >= 0 && plane0 >= 0, RG_EINVAL, "rg_csr_compact_pack: negative size");
+  RG_REQUIRE(rec_order == RG_REC_ORDER_SEGMENT || rec_order == RG_REC_ORDER_DISPATCH, RG_EINVAL,
+             "rg_csr_compact_pack: rec_order=%d is neither RG_REC_ORDER_SEGMENT nor RG_REC_ORDER_DISPATCH", rec_order);
+  RG_REQUIRE(n_rows == 0, RG_EUNSUPPORTED,
+             "rg_csr_compact_pack: the record coding depends on every chunk's dictionary size; call rg_csr_compact_pack_dense");
+  return RG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -466,7 +509,7 @@ extern "C" int rg_csr_compact_pack(const void* indptr, int32_t indptr_is_i64, co
 // it is LDS- and latency-bound, not HBM-bound.  A packed record already holds three CONSECUTIVE
 // pairs, so here the lanes of a row read the row's records straight from memory -- L = 2^k lanes per row, lane j takes
 // records q0 + j, q0 + j + L, ... of the row's record range [rs / 3, ceil(re / 3)) -- and reduce them in registers: no
-// tile, no transposition; LDS carries only the window gathers.  64 / L rows share a wave-load (L * 16 contiguous bytes
+// tile, no transposition; LDS carries only the window gathers.  64 / L rows share a wave-load (L * 16 -- dense coding: L * 14 -- contiguous bytes
 // each, neighbouring rows adjacent in memory); a record that straddles two rows is read by both (an L1 hit) and each
 // takes its own pairs.  Pairs outside the lane's row are redirected to a sentinel window entry whose slots are all
 // EXCLUDED, so the arithmetic needs no extra test.
@@ -496,7 +539,9 @@ constexpr int kRowwiseChunksPerBlock = 1;   // consecutive chunks one workgroup 
 // held to the column mode's wavefronts per SIMD for two to four fields (5, 4, 4) and to at least 5 for one field.  Measured
 // (-Rpass-analysis=kernel-resource-usage, no scratch): 80 / 90 / 112 / 120 VGPRs for 1-4 fields, i.e. 6 / 5 / 4 / 4
 // wavefronts per SIMD -- the column mode's 77 / 83 / 101 / 107 keep the same counts.
-#define RG_ROWWISE_BOUNDS __launch_bounds__(64 * kH, (COLS == 2 ? (NF <= 2 ? 5 : 4) : 1))
+// COLS == 0, four to six fields: 95 VGPRs before the records had two codings, 97 with the second streaming loop left to itself
+// -- one register over the 96 that five wavefronts per SIMD allow --, so these three are held to five (no scratch either way).
+#define RG_ROWWISE_BOUNDS __launch_bounds__(64 * kH, (COLS == 2 ? (NF <= 2 ? 5 : 4) : (COLS == 0 && NF >= 4 && NF <= 6) ? 5 : 1))
 // COLS (rg_csr_compact_apply_columns_f32, csrc/rg_csr_columns.hip): the chunks a workgroup takes one after the other are
 // not consecutive blocks of the dispatch order but the LEVELS of one column of chunks -- the same (line group, segment)
 // patch from plane z0 to z1 - 1 of its level piece -- so that lane == row sees the voxels of its (y, x) column in ascending
@@ -636,7 +681,9 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     rec_b = rec_ptr[slot];
     rec_n = rec_ptr[slot + 1] - rec_b;
   }
-  const rsrc_t rr = make_rsrc(rec + rec_b, rec_n * 16);
+  const rsrc_t rr = make_rsrc(rec + rec_b, rec_n * 16);      // rec_ptr counts 16-byte units in both codings
+  // the coding of this chunk's records (rg_compact_layout.hpp): 14 bytes each in a chunk of at most 2048 gates, else 16
+  const bool dense = rec_is_dense(nd_all);
   constexpr int kOutOfRange = 0x7FFFFFF0;            // byte offset no segment reaches: the load returns zeros
 
   // ---- lanes per row ------------------------------------------------------------------------------------------
@@ -731,13 +778,15 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   struct Step {
     int lo0;           // (first pair of the lane's row) - 3 * q: pair i of slot k is the row's iff 0 <= i - lo < len,
     unsigned len;      //   lo = lo0 - 3 * k * L; len = pairs of the row (0: no row)
-    int rem;           // records of the row from q on: slot k holds one iff k * L < rem
+    int rem;           // records of the row from q on: slot k holds one iff k * L < rem.  Dense records: 2 * that + (q & 1) --
+                       //   k * L < rem iff 2 * k * L + 1 < 2 * rem + parity, so the parity of q rides along for free
     int off0;          // byte offset of record q in the segment's records
     int myrow, rho;
     int left;          // trips of the round still to do, this batch included (wave-uniform)
     bool live;
   };
-  auto setup = [&](int rho) -> Step {
+  auto setup = [&](auto dtag, int rho) -> Step {
+    constexpr int rec_bytes = decltype(dtag)::value ? 14 : 16;
     Step r;
     r.rho = rho;
     r.myrow = rho * rpr + rgrp;
@@ -752,29 +801,37 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     const int q = q0 + sub;
     r.lo0 = qs - 3 * q;
     r.len = (unsigned)(qe - qs);
-    r.rem = q1 - q;
-    r.off0 = q * 16;
+    r.rem = decltype(dtag)::value ? 2 * (q1 - q) + (q & 1) : q1 - q;
+    r.off0 = q * rec_bytes;
     r.left = rho < rounds ? __builtin_amdgcn_readfirstlane(__shfl(trips_row, (rho * rpr) & 63, 64)) : 0;
     return r;
   };
-  auto advance = [&](const Step& r) -> Step {      // the step after r (wave-uniform choice)
+  auto advance = [&](auto dtag, const Step& r) -> Step {      // the step after r (wave-uniform choice)
+    constexpr int rec_bytes = decltype(dtag)::value ? 14 : 16;
     if (r.left > KPRE) {
       Step n = r;
       n.lo0 -= 3 * (KPRE << lgl);
-      n.rem -= KPRE << lgl;
-      n.off0 += 16 * (KPRE << lgl);
+      if constexpr (decltype(dtag)::value) n.rem = (n.rem - 2 * (KPRE << lgl)) ^ ((KPRE << lgl) & 1);   // q + KPRE * L: its parity
+      else n.rem -= KPRE << lgl;
+      n.off0 += rec_bytes * (KPRE << lgl);
       n.left -= KPRE;
       return n;
     }
-    return setup(r.rho + 1);
+    return setup(dtag, r.rho + 1);
   };
-  auto issue = [&](const Step& r, rg_u32x4 (&regs)[KPRE]) {
+  // dense: the aligned 16 bytes that hold the record -- it starts at byte 0 of the load when q is even, at byte 2 when odd
+  auto issue = [&](auto dtag, const Step& r, rg_u32x4 (&regs)[KPRE]) {
+    constexpr bool kDense = decltype(dtag)::value;
 #pragma unroll
-    for (int k = 0; k < KPRE; ++k)
-      regs[k] = rg_buffer_load_v4u32(rr, (k << lgl) < r.rem ? r.off0 + 16 * (k << lgl) : kOutOfRange, 0, 0);
+    for (int k = 0; k < KPRE; ++k) {
+      const int off = kDense ? (r.off0 + 14 * (k << lgl)) & ~3 : r.off0 + 16 * (k << lgl);
+      const bool has = kDense ? 2 * (k << lgl) + 1 < r.rem : (k << lgl) < r.rem;
+      regs[k] = rg_buffer_load_v4u32(rr, has ? off : kOutOfRange, 0, 0);
+    }
   };
-  auto run = [&](auto wtag) {
+  auto run = [&](auto wtag, auto dtag) {
     constexpr bool kWindowed = decltype(wtag)::value;
+    constexpr bool kDense = decltype(dtag)::value;
     // The running sums of the lane's row, across the round's steps: TWO chains -- batch slot k of every step adds into
     // chain k mod 2's (sum w*v, sum w) --, added up when the round ends.  Two independent chains half as long as round 2's
     // single one: worst relative error against the reference's ZDR fixtures 8.7e-6 -> 6.5e-6 at no cost (bench grid
@@ -829,18 +886,17 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     auto consume = [&](const Step& r, const rg_u32x4& q4, int k) {     // k: slot of the step's batch (compile-time)
       // the record's pairs i = 0, 1, 2 belong to the lane's row iff lo <= i < lo + len (len = 0 for a lane without record)
       const int lo = r.lo0 - 3 * (k << lgl);
-      const unsigned len = (k << lgl) < r.rem ? r.len : 0u;
+      const unsigned len = (kDense ? 2 * (k << lgl) + 1 < r.rem : (k << lgl) < r.rem) ? r.len : 0u;
       float w[3];
       int pos[3];
+      // dense: bit 0 of rem is the parity of q; the record's number is q + k * L (k * L is odd only for odd k and L = 1)
+      const RecFields rf = rec_decode<kDense>(q4, !kDense ? 0u : (k & 1) ? (unsigned)r.rem ^ (unsigned)(k << lgl) : (unsigned)r.rem);
       // w_base has its low 26 bits clear (the entry point checks), so code | w_base == code + w_base
-      w[0] = __builtin_bit_cast(float, (q4.x & wmask) | w_base);
-      w[1] = __builtin_bit_cast(float, (q4.y & wmask) | w_base);
-      w[2] = __builtin_bit_cast(float, (q4.z & wmask) | w_base);
-      pos[0] = (int)(q4.w & 0xFFFFu);
-      pos[1] = (int)(q4.w >> 16);
-      unsigned p2b = q4.y >> 26, p2c = q4.z >> 26;
-      asm volatile("" : "+v"(p2b), "+v"(p2c));     // keep the shifts apart: each OR then folds into a v_lshl_or_b32
-      pos[2] = (int)((p2c << 12) | ((p2b << 6) | (q4.x >> 26)));
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        w[i] = __builtin_bit_cast(float, (rf.wc[i] & wmask) | w_base);
+        pos[i] = (int)rf.pos[i];
+      }
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         const bool mine = (unsigned)(i - lo) < len;
@@ -1014,21 +1070,25 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     };
 
     rg_u32x4 regs_a[KPRE], regs_b[KPRE];
-    Step sa = setup(0), sb;
-    issue(sa, regs_a);
+    Step sa = setup(dtag, 0), sb;
+    issue(dtag, sa, regs_a);
     for (;;) {     // two register stages, alternating: nothing in flight is ever copied
-      sb = advance(sa);
-      issue(sb, regs_b);
+      sb = advance(dtag, sa);
+      issue(dtag, sb, regs_b);
       process(sa, regs_a, sb.rho != sa.rho);
       if (sb.rho >= rounds) break;
-      sa = advance(sb);
-      issue(sa, regs_a);
+      sa = advance(dtag, sb);
+      issue(dtag, sa, regs_a);
       process(sb, regs_b, sa.rho != sb.rho);
       if (sa.rho >= rounds) break;
     }
   };
-  if (span > 0) {
-    if (windowed) run(std::true_type{}); else run(std::false_type{});
+  if (span > 0) {       // the streaming loop exists once per (window | per-pair gathers) x (dense | wide records): workgroup-uniform
+    if (dense) {
+      if (windowed) run(std::true_type{}, std::true_type{}); else run(std::false_type{}, std::true_type{});
+    } else {
+      if (windowed) run(std::true_type{}, std::false_type{}); else run(std::false_type{}, std::false_type{});
+    }
   }
   // PLANES: the selection words of lane == row, read again at every level (from L2: 4 bytes per selection and row) rather than
   // kept in registers through the streaming loop, where they would cost two fields a wavefront per SIMD

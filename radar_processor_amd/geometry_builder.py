@@ -293,8 +293,10 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
     index array of the whole grid -- half of the standard CSR -- never exists, so a geometry of P pairs needs about
     6.2*P bytes instead of 8*P (+2.2*P for the copy).
 
-    ``packed``: additionally fold every slab's positions and weights into the 16-byte records of
-    ``rg_csr_compact_pack`` (three pairs each) and keep ONLY those: 5.4*P bytes, and the kernel's fastest stream.  The
+    ``packed``: additionally fold every slab's positions and weights into the records of ``rg_csr_compact_pack_dense``
+    (three pairs each: 14 bytes in the chunks of at most 2048 gates, 16 bytes elsewhere) and keep ONLY those: 4.8-5.4*P
+    bytes, and the kernel's fastest stream.  A chunk's coding follows from its dictionary, which exists only once its
+    slab has been processed, so the slabs' record pointers are laid end to end as the slabs are packed.  The
     weight code is lossless for weights within 8 binades of the weighting's smallest possible value (Barnes, uniform);
     should a weight fall outside (it cannot for those weightings), the pack kernel flags it and the caller falls back.
 
@@ -319,12 +321,14 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
         if packed:
             from . import grid_geometry
             rec_order = grid_geometry.DEFAULT_REC_ORDER
-            rec_ptr = CompactCSR.record_pointers(indptr, search.grid_shape, rec_order)
+            rec_ptr = CompactCSR.record_pointers(indptr, search.grid_shape, rec_order)      # all 16 bytes: the upper bound
             if rec_ptr is None:
                 return None
             slots_per_plane = (rec_ptr.numel() - 1) // nz      # chunks never cross a plane: neither do the slots
             n_rec = int(rec_ptr[-1])
             rec = torch.empty((max(n_rec, 1), 4), dtype=torch.int32, device=dev)[:n_rec]
+            rec_ptr.zero_()                                    # filled in slab by slab, in 16-byte units
+            n_units = 0
             w_base = _PACK_BASE_EXPONENT[weighting] << 23
             err = torch.zeros(1, dtype=torch.int32, device=dev)
         else:
@@ -357,13 +361,23 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
                 return None
             count_parts.append(built[0])
             dict_parts.append(built[1])
+            if packed:
+                # the slab's record pointers: its chunks' codings are known now (built[0]: their dictionary sizes)
+                dict_ptr_slab = torch.zeros(built[0].numel() + 1, dtype=torch.int64, device=dev)
+                dict_ptr_slab[1:] = torch.cumsum(built[0], 0)
+                rp = CompactCSR.record_pointers(indptr[iz0 * n_xy:iz1 * n_xy + 1], (iz1 - iz0, ny, nx), rec_order,
+                                                dict_ptr_slab, plane0=iz0)
+                s0 = iz0 * slots_per_plane
+                rec_ptr[s0 + 1:s0 + rp.numel()] = rp[1:] + n_units
+                rec_ptr[s0] = n_units
+                n_units += int(rp[-1])
             if packed and p1 > p0:
-                _native.check(lib.rg_csr_compact_pack(
+                _native.check(lib.rg_csr_compact_pack_dense(
                     _native.ptr(indptr) + 8 * iz0 * n_xy, 1, l_ptr, w_ptr, (iz1 - iz0) * n_xy, nx, ny,
-                    _native.ptr(rec_ptr) + 8 * iz0 * slots_per_plane, rec_order, iz0, w_base, _native.ptr(rec),
-                    _native.ptr(err), stream), "rg_csr_compact_pack")
+                    _native.ptr(dict_ptr_slab), _native.ptr(rec_ptr) + 8 * s0, rec_order, iz0, w_base, _native.ptr(rec),
+                    _native.ptr(err), stream), "rg_csr_compact_pack_dense")
                 if int(err.item()):
-                    logger.info(f"rg_csr_compact_pack flag {int(err.item())} (a weight outside the 26-bit code, or an over-long "
+                    logger.info(f"rg_csr_compact_pack_dense flag {int(err.item())} (a weight outside the 26-bit code, or an over-long "
                                 "segment): keeping the plain compact layout instead")
                     return None
                 del w_slab, l_slab
@@ -372,7 +386,17 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
         counts_all = torch.cat(count_parts) if count_parts else torch.zeros(0, dtype=torch.int64, device=dev)
         compact = CompactCSR._finish(indptr, search.grid_shape, local, counts_all, dict_parts)
         if packed:
+            if n_units < n_rec:       # the dense chunks left room at the end: keep a copy of the right size where it fits
+                free_b, _ = torch.cuda.mem_get_info(dev)
+                if free_b >= 16 * n_units + (2 << 30):
+                    trimmed = torch.empty((max(n_units, 1), 4), dtype=torch.int32, device=dev)[:n_units]
+                    trimmed.copy_(rec[:n_units])
+                    rec = trimmed
+                else:
+                    rec = rec[:n_units]
             compact.rec, compact.rec_ptr, compact.rec_order, compact.w_base = rec, rec_ptr, rec_order, w_base
+            logger.info(f"Packed pair stream: {16 * n_units / 1e6:.1f} MB ({16 * n_units / max(n_pairs, 1):.2f} bytes per pair; "
+                        f"{100 * compact.dense_fraction():.2f} % of the pairs in 14-byte records)")
         if n_pairs <= _INT32_MAX:
             indptr = indptr.to(torch.int32)
     return DeviceCSR(indptr, None, weights, max_gate, n_pairs=n_pairs), compact

@@ -26,6 +26,10 @@ _NOT_COMPACTABLE = 0x40000000     # chunk_counts marker of rg_csr_compact_count
 # order in which the apply kernels' workgroups read them, so that a launch sweeps the array as one moving front;
 # SEGMENT = line-major segments (round 2's layout, kept for A/B measurements: bench.py --rec-order segment).
 DEFAULT_REC_ORDER = _native.RG_REC_ORDER_DISPATCH
+# Coding of the packed records a sidecar holds (save_device_layout / load_device_layout).  2: 14-byte records in the chunks
+# of at most RG_DENSE_MAX_DICT gates, 16-byte records elsewhere, rec_ptr in 16-byte units.  Files without the tag hold
+# 16-byte records throughout, which no kernel of this build reads: they are refused and the layout is derived again.
+REC_FORMAT = 2
 
 
 class DeviceCSR:
@@ -70,9 +74,10 @@ class CompactCSR:
         self.grid_shape = tuple(int(v) for v in grid_shape)   # (planes, lines per plane, rows per line)
         self.chunk_pairs = chunk_pairs      # int64 [chunks]: pairs per chunk    } kept to choose the window for a
         self.chunk_counts = chunk_counts    # int64 [chunks]: distinct gates     } given field count (window_for)
-        # packed pair stream for passes of 1-8 fields (ensure_packed): 16-byte records of three pairs, or None
-        self.rec = None                     # int32 [n_rec, 4]
-        self.rec_ptr = None                 # int64 [slots + 1]: records of the segment in slot s (see rec_order)
+        # packed pair stream for passes of 1-8 fields (ensure_packed): records of three pairs -- 14 bytes each in the chunks
+        # of at most RG_DENSE_MAX_DICT gates, 16 bytes in the others --, or None
+        self.rec = None                     # int32 [n_units, 4]: 16-byte units
+        self.rec_ptr = None                 # int64 [slots + 1]: first unit of the segment in slot s (see rec_order)
         self.rec_order = DEFAULT_REC_ORDER  # RG_REC_ORDER_SEGMENT (slot = segment) / RG_REC_ORDER_DISPATCH (slot_of_segments)
         self.w_base = 0                     # weight code = float32 bits - w_base
         self._pack_tried = False
@@ -84,8 +89,9 @@ class CompactCSR:
 
     def ensure_packed(self, csr: "DeviceCSR") -> bool:
         """Build (once) the packed pair stream ``rg_csr_compact_apply_packed_f32`` reads: positions and weights of three
-        consecutive pairs of a segment in one 16-byte record -- 5.33 instead of 6 bytes per pair, one 16-byte load per
-        lane.  The weight is stored as its float32 bits minus ``w_base`` in 26 bits, which is lossless exactly when all
+        consecutive pairs of a segment in one record -- 14 bytes where the chunk's dictionary has at most
+        ``RG_DENSE_MAX_DICT`` entries (11-bit positions: 4.67 bytes per pair), 16 bytes elsewhere (5.33) instead of 6 bytes
+        per pair, one 16-byte load per lane.  The weight is stored as its float32 bits minus ``w_base`` in 26 bits, which is lossless exactly when all
         weights are positive and span at most 8 binades (Barnes weights: exp(-4)+1e-5 .. 1+1e-5, 7 binades; a uniform
         weight trivially); other geometries (Cressman: weights down to 0) keep the plain arrays.  Returns whether the
         stream exists.  Costs 5.4 bytes per pair of HBM on top of the copy; skipped when that does not fit."""
@@ -113,7 +119,7 @@ class CompactCSR:
                         "of 8, the compact copy keeps the plain arrays")
             return False
         nz, ny, nx = self.grid_shape
-        rec_ptr = self.record_pointers(csr.indptr, self.grid_shape, self.rec_order)
+        rec_ptr = self.record_pointers(csr.indptr, self.grid_shape, self.rec_order, self.dict_ptr)
         if rec_ptr is None:                      # the kernels address a segment's records with 32-bit byte offsets
             logger.info("a segment holds more than 2^27 records: the compact copy keeps the plain arrays")
             return False
@@ -122,23 +128,37 @@ class CompactCSR:
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         w_base = base << 23
         with torch.cuda.device(dev):
-            _native.check(lib.rg_csr_compact_pack(_native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(self.local_idx),
-                                                  _native.ptr(csr.weights), csr.n_vox, nx, ny, _native.ptr(rec_ptr),
-                                                  self.rec_order, 0, w_base, _native.ptr(rec), _native.ptr(err),
-                                                  _native.stream_ptr()),
-                          "rg_csr_compact_pack")
+            _native.check(lib.rg_csr_compact_pack_dense(_native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(self.local_idx),
+                                                        _native.ptr(csr.weights), csr.n_vox, nx, ny, _native.ptr(self.dict_ptr),
+                                                        _native.ptr(rec_ptr), self.rec_order, 0, w_base, _native.ptr(rec),
+                                                        _native.ptr(err), _native.stream_ptr()),
+                          "rg_csr_compact_pack_dense")
         if int(err.item()):
-            raise _native.NativeError(f"rg_csr_compact_pack reported flag {int(err.item())}")
+            raise _native.NativeError(f"rg_csr_compact_pack_dense reported flag {int(err.item())}")
         self.rec, self.rec_ptr, self.w_base = rec, rec_ptr, w_base
-        logger.info(f"Packed pair stream: {rec.numel() * 4 / 1e6:.1f} MB ({16 * n_rec / csr.n_pairs:.2f} bytes per pair)")
+        logger.info(f"Packed pair stream: {rec.numel() * 4 / 1e6:.1f} MB ({16 * n_rec / csr.n_pairs:.2f} bytes per pair; "
+                    f"{100 * self.dense_fraction():.2f} % of the pairs in 14-byte records)")
         return True
 
+    def dense_chunks(self):
+        """bool ``[chunks]``: the chunks whose records are 14 bytes (at most ``RG_DENSE_MAX_DICT`` dictionary entries)."""
+        return (self.dict_ptr[1:] - self.dict_ptr[:-1]) <= _native.RG_DENSE_MAX_DICT
+
+    def dense_fraction(self) -> float:
+        """Share of the pairs that lie in chunks with 14-byte records."""
+        if self.chunk_pairs is None or self.chunk_pairs.numel() == 0:
+            return 0.0
+        total = max(int(self.chunk_pairs.sum()), 1)
+        return float(int(self.chunk_pairs[self.dense_chunks()].sum()) / total)
+
     @classmethod
-    def slot_of_segments(cls, line, sx, grid_shape, rec_order: int):
+    def slot_of_segments(cls, line, sx, grid_shape, rec_order: int, plane0: int = 0):
         """Slot (index into ``rec_ptr``) of segment ``sx`` of grid line ``line`` (int64 tensors, lines counted through all
         planes).  ``RG_REC_ORDER_SEGMENT``: the line-major segment number.  ``RG_REC_ORDER_DISPATCH``: ``block * H + w``
         for the wavefront ``w`` of the workgroup ``block`` that reads the segment -- the inverse of the kernels'
-        block -> chunk rotation (``block_chunk`` in csrc/rg_csr_compact.hip, 32-bit unsigned arithmetic)."""
+        block -> chunk rotation (``block_chunk`` in csrc/rg_csr_compact.hip, 32-bit unsigned arithmetic).  ``plane0``: the
+        grid is a slab of whole planes of a larger one and this is its first plane there -- lines and slots stay the slab's
+        own, the rotation counts the line groups in front of it."""
         nz, ny, nx = (int(v) for v in grid_shape)
         nsx, nyg, _ = cls.layout(grid_shape)
         if rec_order == _native.RG_REC_ORDER_SEGMENT:
@@ -147,14 +167,17 @@ class CompactCSR:
         plane = line // ny
         y = line - plane * ny
         grp = plane * nyg + y // lines
-        shift = ((grp * _native.RG_COMPACT_ROTATION) & 0xFFFFFFFF) % nsx
+        shift = (((grp + int(plane0) * nyg) * _native.RG_COMPACT_ROTATION) & 0xFFFFFFFF) % nsx
         col = (sx - shift) % nsx                     # the block column whose rotated column is sx
         return (grp * nsx + col) * lines + y % lines
 
     @classmethod
-    def record_pointers(cls, indptr, grid_shape, rec_order: int):
-        """``rec_ptr`` (int64 ``[slots + 1]``) for the row pointers of a whole grid: every segment gets
-        ``ceil(pairs / 3)`` records, laid out in slot order.  ``None`` when a segment would hold 2^27 records or more."""
+    def record_pointers(cls, indptr, grid_shape, rec_order: int, dict_ptr=None, plane0: int = 0):
+        """``rec_ptr`` (int64 ``[slots + 1]``) for the row pointers of a whole grid (or of a slab of whole planes that starts
+        at plane ``plane0`` of a larger one), in 16-byte units laid out in slot order: a segment of ``n = ceil(pairs / 3)``
+        records takes ``ceil(14 * n / 16)`` units where its chunk's dictionary (``dict_ptr``, int64 ``[chunks + 1]``) has at
+        most ``RG_DENSE_MAX_DICT`` entries and ``n`` units elsewhere -- everywhere without ``dict_ptr``, which is also the
+        upper bound of any layout.  ``None`` when a segment would hold 2^27 records or more."""
         torch = _native.torch_mod()
         dev = indptr.device
         nz, ny, nx = (int(v) for v in grid_shape)
@@ -165,13 +188,21 @@ class CompactCSR:
         n_rec_seg = ((edges[:, 1:] - edges[:, :-1]) + 2) // 3
         if n_rec_seg.numel() and int(n_rec_seg.max()) >= 1 << 27:
             return None
+        if dict_ptr is not None and n_rec_seg.numel():
+            lines = _native.RG_COMPACT_LINES
+            line_all = torch.arange(nz * ny, device=dev, dtype=torch.int64)
+            grp = (line_all // ny) * nyg + (line_all % ny) // lines                        # line group of every line
+            chunk = grp[:, None] * nsx + torch.arange(nsx, device=dev, dtype=torch.int64)[None, :]
+            dp = dict_ptr.to(dev)
+            dense = (dp[chunk + 1] - dp[chunk]) <= _native.RG_DENSE_MAX_DICT
+            n_rec_seg = torch.where(dense, (14 * n_rec_seg + 15) // 16, n_rec_seg)
         if rec_order == _native.RG_REC_ORDER_SEGMENT:
             per_slot = n_rec_seg.reshape(-1)
         else:
             line = torch.arange(nz * ny, device=dev, dtype=torch.int64)[:, None].expand(nz * ny, nsx)
             sx = torch.arange(nsx, device=dev, dtype=torch.int64)[None, :].expand(nz * ny, nsx)
             per_slot = torch.zeros(n_chunks * _native.RG_COMPACT_LINES, dtype=torch.int64, device=dev)
-            per_slot[cls.slot_of_segments(line, sx, grid_shape, rec_order).reshape(-1)] = n_rec_seg.reshape(-1)
+            per_slot[cls.slot_of_segments(line, sx, grid_shape, rec_order, plane0).reshape(-1)] = n_rec_seg.reshape(-1)
         rec_ptr = torch.zeros(per_slot.numel() + 1, dtype=torch.int64, device=dev)
         rec_ptr[1:] = torch.cumsum(per_slot, 0)
         return rec_ptr
@@ -328,8 +359,9 @@ class CompactCSR:
                    chunk_pairs, counts)
 
     def _record_fields(self, csr: "DeviceCSR", r0: int, r1: int):
-        """Positions (int64) and weights (float32) of the pairs of rows ``[r0, r1)``, unpacked from the 16-byte records
-        (the inverse of ``rg_csr_compact_pack``; used when the plain ``local_idx`` / ``weights`` arrays do not exist)."""
+        """Positions (int64) and weights (float32) of the pairs of rows ``[r0, r1)``, unpacked from the records (the inverse
+        of ``rg_csr_compact_pack_dense``, both codings: csrc/rg_compact_layout.hpp; used when the plain ``local_idx`` /
+        ``weights`` arrays do not exist)."""
         torch = _native.torch_mod()
         dev = csr.indptr.device
         nz, ny, nx = self.grid_shape
@@ -349,12 +381,34 @@ class CompactCSR:
         row_of_pair = torch.repeat_interleave(torch.arange(r1 - r0, device=dev), lens, output_size=n)
         pair = torch.arange(n, device=dev, dtype=torch.int64) + ip[0]
         q = pair - seg_first_pair[row_of_pair]                                 # pair's offset inside its segment
-        rec = self.rec[self.rec_ptr[seg[row_of_pair]] + q // 3].to(torch.int64) & 0xFFFFFFFF      # [n, 4] as unsigned
-        j = q % 3
-        code = torch.where(j == 0, rec[:, 0], torch.where(j == 1, rec[:, 1], rec[:, 2])) & 0x3FFFFFF
+        unit0 = self.rec_ptr[seg[row_of_pair]]                                 # first 16-byte unit of the pair's segment
+        rq, j = q // 3, q % 3
+        chunk_of_row = self.chunk_of_rows(rows, self.grid_shape)
+        dense = ((self.dict_ptr[chunk_of_row + 1] - self.dict_ptr[chunk_of_row]) <= _native.RG_DENSE_MAX_DICT)[row_of_pair]
+        code = torch.empty(n, dtype=torch.int64, device=dev)
+        pos = torch.empty(n, dtype=torch.int64, device=dev)
+        wide = ~dense
+        if bool(wide.any()):
+            rec = self.rec[unit0[wide] + rq[wide]].to(torch.int64) & 0xFFFFFFFF      # [m, 4] as unsigned
+            jw = j[wide]
+            code[wide] = torch.where(jw == 0, rec[:, 0], torch.where(jw == 1, rec[:, 1], rec[:, 2])) & 0x3FFFFFF
+            p2 = (rec[:, 0] >> 26) | ((rec[:, 1] >> 26) << 6) | (((rec[:, 2] >> 26) & 0xF) << 12)
+            pos[wide] = torch.where(jw == 0, rec[:, 3] & 0xFFFF, torch.where(jw == 1, rec[:, 3] >> 16, p2))
+        if bool(dense.any()):
+            half = self.rec.view(torch.int16).reshape(-1)
+            rd, jd = rq[dense], j[dense]
+            h = half[(unit0[dense] * 8 + 7 * rd)[:, None] + torch.arange(7, device=dev)[None, :]].to(torch.int64) & 0xFFFF
+            odd = (rd & 1) == 1
+            pair_w = lambda lo, hi: h[:, lo] | (h[:, hi] << 16)                  # noqa: E731  two halfwords as one word
+            w2 = torch.where(odd, pair_w(0, 5), pair_w(0, 1))
+            m1 = torch.where(odd, pair_w(1, 2), pair_w(2, 3))
+            m2 = torch.where(odd, pair_w(3, 4), pair_w(4, 5))
+            pw = h[:, 6]
+            code[dense] = torch.where(jd == 0, m1, torch.where(jd == 1, m2, w2)) & 0x3FFFFFF
+            p1 = (m1 >> 26) | ((pw >> 11) << 6)
+            p2 = (m2 >> 26) | ((w2 >> 26) << 6)
+            pos[dense] = torch.where(jd == 0, pw & 0x7FF, torch.where(jd == 1, p1, p2))
         weights = (code + self.w_base).to(torch.int32).view(torch.float32)
-        p2 = (rec[:, 0] >> 26) | ((rec[:, 1] >> 26) << 6) | (((rec[:, 2] >> 26) & 0xF) << 12)
-        pos = torch.where(j == 0, rec[:, 3] & 0xFFFF, torch.where(j == 1, rec[:, 3] >> 16, p2))
         return pos, weights
 
     def decode_weights(self, csr: "DeviceCSR", row0: int = 0, row1: Optional[int] = None, rows_per_slab: int = 500_000):
@@ -671,7 +725,8 @@ def save_device_layout(geometry: GridGeometry, filepath: str, device=None) -> bo
                   chunk_pairs=compact.chunk_pairs.cpu().numpy(), chunk_counts=compact.chunk_counts.cpu().numpy())
     if compact.rec is not None:
         arrays.update(rec=compact.rec.cpu().numpy(), rec_ptr=compact.rec_ptr.cpu().numpy(),
-                      rec_order=np.array([compact.rec_order]), w_base=np.array([compact.w_base], dtype=np.uint32))
+                      rec_order=np.array([compact.rec_order]), w_base=np.array([compact.w_base], dtype=np.uint32),
+                      rec_format=np.array([REC_FORMAT]))
     if compact.local_idx is not None:
         arrays["local_idx"] = compact.local_idx.cpu().numpy()
     np.savez(filepath, **arrays)
@@ -689,6 +744,10 @@ def load_device_layout(geometry: GridGeometry, filepath: str, device=None) -> bo
     with np.load(filepath, allow_pickle=False) as data:
         if bytes(data["key"]).decode() != _reference_arrays_digest(geometry):
             logger.warning(f"{filepath} was derived from another geometry: ignored")
+            return False
+        if "rec" in data and ("rec_format" not in data or int(data["rec_format"][0]) != REC_FORMAT):
+            logger.warning(f"{filepath} holds records in another coding than this build reads (no or another rec_format tag): "
+                           "ignored, the device layout is derived again")
             return False
         csr = geometry.device_csr(device)
         dev = csr.indptr.device

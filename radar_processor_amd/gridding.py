@@ -369,13 +369,14 @@ class CsrGridder:
         return {"tries": tries, "probe_ms": probe_ms, "kept": kept}
 
     def compact_bytes(self) -> Optional[int]:
-        """Bytes one launch of the compact kernel must move: 16-bit position + weight per pair, the dictionaries and
-        their offsets, the row pointers, every field once, every grid once (``None`` without a compact copy)."""
+        """Bytes one launch of the compact kernel must move: the packed records as stored (or 16-bit position + weight per
+        pair), the dictionaries and their offsets, the row pointers, every field once, every grid once (``None`` without a
+        compact copy)."""
         if self.compact is None:
             return None
         csr, c = self.csr, self.compact
         ip = 8 if csr.is_i64 else 4
-        if self.packed_stream:      # 16-byte records of three pairs + one record offset per segment
+        if self.packed_stream:      # the records' 16-byte units (14-byte records where the chunk is dense) + one offset per segment
             stream = 16 * int(c.rec.shape[0]) + 8 * int(c.rec_ptr.numel())
         else:
             stream = 6 * csr.n_pairs
