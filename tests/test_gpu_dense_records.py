@@ -4,12 +4,13 @@ planes modes), the tile kernel and ``CompactCSR.decode``.
 
 Everything here runs on small HAND-MADE compact copies: the test chooses every chunk's dictionary and every pair's
 position itself (the builder's positions depend on the order in which its hash set sees the gates), so that it can put
-position 2047 next to weight code 0x3FFFFFF wherever it wants.  ``_encode`` below, plain NumPy, is the specification of
+position 2047 next to weight code 0x3FFFFFF wherever it wants.  ``slab_scenes.encode_records``, plain NumPy, is the specification of
 the record stream: the pack kernel has to reproduce it byte for byte.
 """
 import numpy as np
 import pytest
 
+import slab_scenes as scenes
 from oracle import radar_grid_oracle as oracle
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +19,6 @@ DENSE_MAX = 2048
 NZ, NY, NX = 2, 8, 130                       # 3 segments of 44 / 43 / 43 rows per line, 2 line groups per plane: 12 chunks
 SHAPE = (NZ, NY, NX)
 LIMITS = ((0.0, 1.0), (0.0, 1.0), (0.0, 1.0))
-STARTS = [0, 44, 87, 130]
 NSX, NYG, LINES = 3, 2, 4
 N_CHUNKS = NZ * NYG * NSX
 W_BASE = 120 << 23                           # the weights below span exponents 120 .. 127
@@ -40,12 +40,7 @@ def rg():
 
 def _segments():
     """(line, sx, first row, rows, chunk) of every segment, line-major."""
-    out = []
-    for line in range(NZ * NY):
-        plane, y = divmod(line, NY)
-        for sx in range(NSX):
-            out.append((line, sx, line * NX + STARTS[sx], STARTS[sx + 1] - STARTS[sx], (plane * NYG + y // LINES) * NSX + sx))
-    return out
+    return scenes.segments(SHAPE)
 
 
 def _make(kind):
@@ -108,44 +103,9 @@ def _make(kind):
 
 
 def _encode(case, slot_of, n_slots):
-    """The record stream as bytes + rec_ptr (16-byte units), restated from the layout's description.
-    ``slot_of[(line, sx)]``: the segment's slot."""
-    indptr, pos, sizes = case["indptr"], case["pos"], case["sizes"]
-    code = case["wts"].view(np.uint32).astype(np.int64) - W_BASE
-    assert code.min() >= 0 and code.max() <= CODE_MAX
-    units = np.zeros(n_slots, dtype=np.int64)
-    blobs = {}
-    for (line, sx, r0, nrows, chunk) in _segments():
-        p0, p1 = int(indptr[r0]), int(indptr[r0 + nrows])
-        n = (p1 - p0 + 2) // 3
-        c = np.zeros(3 * n, dtype=np.int64)
-        p = np.zeros(3 * n, dtype=np.int64)
-        c[:p1 - p0], p[:p1 - p0] = code[p0:p1], pos[p0:p1]
-        c, p = c.reshape(n, 3), p.reshape(n, 3)
-        if sizes[chunk] <= DENSE_MAX:                            # 14 bytes: seven halfwords, W2.hi moves in odd records
-            assert p.max(initial=0) < 2048
-            m1 = c[:, 0] | ((p[:, 1] & 0x3F) << 26)
-            m2 = c[:, 1] | ((p[:, 2] & 0x3F) << 26)
-            w2 = c[:, 2] | ((p[:, 2] >> 6) << 26)
-            pw = p[:, 0] | ((p[:, 1] >> 6) << 11)
-            lo, hi = (lambda x: x & 0xFFFF), (lambda x: x >> 16)
-            even = np.stack([lo(w2), hi(w2), lo(m1), hi(m1), lo(m2), hi(m2), pw], axis=1)
-            odd = np.stack([lo(w2), lo(m1), hi(m1), lo(m2), hi(m2), hi(w2), pw], axis=1)
-            half = np.where((np.arange(n) % 2 == 1)[:, None], odd, even).astype("<u2")
-            n_units = (14 * n + 15) // 16
-            blob = np.zeros(16 * n_units, dtype=np.uint8)        # zero padding up to the next unit
-            blob[:14 * n] = half.reshape(-1).view(np.uint8)
-        else:                                                    # 16 bytes
-            words = np.stack([c[:, 0] | ((p[:, 2] & 0x3F) << 26), c[:, 1] | (((p[:, 2] >> 6) & 0x3F) << 26),
-                              c[:, 2] | ((p[:, 2] >> 12) << 26), p[:, 0] | (p[:, 1] << 16)], axis=1).astype("<u4")
-            n_units = n
-            blob = words.reshape(-1).view(np.uint8)
-        units[slot_of[(line, sx)]] = n_units
-        blobs[slot_of[(line, sx)]] = blob
-    rec_ptr = np.zeros(n_slots + 1, dtype=np.int64)
-    np.cumsum(units, out=rec_ptr[1:])
-    stream = np.concatenate([blobs[s] for s in sorted(blobs)] + [np.zeros(0, dtype=np.uint8)])
-    return stream, rec_ptr
+    """The record stream as bytes + rec_ptr (16-byte units): ``slab_scenes.encode_records``, the NumPy restatement of the
+    layout's description.  ``slot_of[(line, sx)]``: the segment's slot."""
+    return scenes.encode_records(case, SHAPE, slot_of, n_slots, W_BASE)
 
 
 class _Case:
