@@ -319,6 +319,40 @@ int rg_section_fill_f32(const rg_gate4* sorted_gates, const int32_t* cell_start,
                         int32_t* gate_idx, float* weights, rg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * A vertical cross-section through a mosaic: rg_roi_section_f32 over up to RG_MAX_RADARS search structures in one launch,
+ *     out[f][k * n_points + i] = sum_r sum_{live j} w_j * v_j / sum_r sum_{live j} w_j   (fill_value where the sum is not > 0)
+ * where radar r's neighbours and weights of sample (k, i) are those of radar_grid/compute.py:46-91 at (xs_r[i], ys_r[i],
+ * zc_r[k]) -- the point and the level in radar r's frame -- and the mean is radar_grid/interpolate.py:69-104 over the union
+ * of every radar's neighbours.  Per radar the arithmetic is rg_roi_section_f32's; hits of all radars add into the same
+ * float32 accumulators, radar by radar in table order.  One entry with gate_offset 0 returns exactly the bits of
+ * rg_roi_section_f32 on the same search structure and points.
+ *
+ * Entry r describes radar r:
+ *   sorted_gates, cell_start, cells   its cell-sorted gates; a gate's index is the radar's OWN gate number;
+ *   xs, ys                            float32 [n_points], device: the points relative to this radar.  A point the radar
+ *                                     cannot serve (outside the rectangle its search structure was built for) carries a
+ *                                     NaN: it has no neighbours among this radar's gates.  A block of 4 consecutive points
+ *                                     without a live one reads nothing of the radar's search structure;
+ *   zc                                float32 [nz], device: the levels relative to this radar;
+ *   gate_offset, n_gates              radar r's gate g is packed slot gate_offset + g of `packed`;
+ *                                     gate_offset + n_gates <= n_gates_total.
+ * An entry with n_gates == 0 or a null sorted_gates takes no part: none of its pointers is read.  The table is read on
+ * the host and passed by value in the kernel arguments.  RG_W_CLOSEST is not supported (RG_EUNSUPPORTED).
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rg_section_radar {
+  const rg_gate4* sorted_gates;
+  const int32_t* cell_start;
+  rg_cellgrid cells;
+  const float *xs, *ys, *zc;
+  int64_t gate_offset, n_gates;
+} rg_section_radar;
+
+int rg_roi_section_mosaic_f32(const rg_section_radar* radars_host, int32_t n_radars, int32_t nz, int32_t n_points,
+                              double min_radius, double beam_factor, int32_t weighting, const float* packed,
+                              int32_t n_fields, int32_t stride, int64_t n_gates_total, float fill_value, float* out,
+                              rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * (f)3  processor-style collapse of the cached 3-D grid to the 2-D product plane:
  * radar_processor/processor.py:480-551 (collapse_grid_to_2d) and radar_processor/utils.py:336-387
  * (collapse_field_3d_to_2d).  'cappi' (nearest level, :530-533) and 'colmax' (:534-535) are

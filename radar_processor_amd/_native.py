@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "libradargrid_hip.so")
 ABI_VERSION = 104          # include/radargrid_hip.h: RG_VERSION -- load_library refuses a library built from another header
 
 RG_MAX_FIELDS = 8
-RG_MAX_RADARS = 16         # radars one rg_roi_grid_mosaic_f32 launch takes
+RG_MAX_RADARS = 16         # radars one rg_roi_grid_mosaic_f32 / rg_roi_section_mosaic_f32 launch takes
 RG_EXCLUDED_BITS = 0x7FD1CE5D
 
 RG_OK, RG_EINVAL, RG_EALIGN, RG_ELAUNCH, RG_EWORKSPACE, RG_EUNSUPPORTED, RG_ENODEVICE = 0, -1, -2, -3, -4, -5, -6
@@ -56,6 +56,12 @@ class MosaicRadar(Structure):
     _fields_ = [("sorted_gates", c_void_p), ("cell_start", c_void_p), ("cells", CellGrid), ("xc", c_void_p),
                 ("yc", c_void_p), ("zc", c_void_p), ("ix0", c_int32), ("iy0", c_int32), ("nx_win", c_int32),
                 ("ny_win", c_int32), ("gate_offset", c_int64), ("n_gates", c_int64)]
+
+
+class SectionRadar(Structure):
+    """``rg_section_radar``: one radar of an ``rg_roi_section_mosaic_f32`` launch (device pointers, host-side table)."""
+    _fields_ = [("sorted_gates", c_void_p), ("cell_start", c_void_p), ("cells", CellGrid), ("xs", c_void_p),
+                ("ys", c_void_p), ("zc", c_void_p), ("gate_offset", c_int64), ("n_gates", c_int64)]
 
 
 class PlaneTest(Structure):
@@ -149,6 +155,8 @@ SIGNATURES = {
     "rg_roi_section_f32": (c_int32, [c_void_p, c_void_p, POINTER(CellGrid), c_void_p, c_void_p, c_void_p, c_int32,
                                      c_int32, c_double, c_double, c_int32, c_void_p, c_int32, c_int32, c_float, c_void_p,
                                      c_void_p]),
+    "rg_roi_section_mosaic_f32": (c_int32, [POINTER(SectionRadar), c_int32, c_int32, c_int32, c_double, c_double, c_int32,
+                                            c_void_p, c_int32, c_int32, c_int64, c_float, c_void_p, c_void_p]),
     "rg_section_count_f32": (c_int32, [c_void_p, c_void_p, POINTER(CellGrid), c_void_p, c_void_p, c_void_p, c_int32,
                                        c_int32, c_double, c_double, c_void_p, c_void_p]),
     "rg_section_fill_f32": (c_int32, [c_void_p, c_void_p, POINTER(CellGrid), c_void_p, c_void_p, c_void_p, c_int32,

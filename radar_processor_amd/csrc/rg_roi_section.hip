@@ -32,6 +32,16 @@
 // not defined.  Points outside the rectangle the search structure was built for read clamped cells: memory-safe, but their
 // neighbours are not guaranteed -- the Python surface refuses both before a launch.
 //
+// Several radars on one section (rg_roi_section_mosaic_f32, MOSAIC): the block visits the radars of the table in order.  For
+// each it rebuilds its samples from that radar's own xs / ys / zc (the points in that radar's frame: the distance to the
+// antenna, hence the radius of influence, differs per radar), its sub-boxes and cell box from that radar's cells, streams
+// that radar's candidates, gathers from that radar's part of the packed fields and adds the hits into the ONE set of float32
+// accumulators; the ring is drained before the next radar starts, so a radar's candidates never move another radar's slot
+// assignment -- one radar at gate offset 0 gives the bits of rg_roi_section_f32.  A point a radar cannot serve carries a NaN
+// in that radar's arrays (dead, as above); a block without a live point skips the radar before anything of its search
+// structure is read, and an entry without gates is skipped before its points are.  The table travels by value in the kernel
+// arguments (16 x 112 bytes) and is indexed with the wave-uniform visit number: scalar loads, no scratch.
+//
 // Compiled with -ffp-contract=off like every TU (the exact test must not be fused); the float32 tests use explicit fmaf,
 // their error is covered by the rim band (rg_roi_search.hpp).
 #include "rg_common.hpp"
@@ -53,11 +63,32 @@ constexpr unsigned long long slot_lanes_of_point0() {   // the lanes that own po
   return m;
 }
 
-template <int MODE, int W, int NF, int STRIDE>
-__global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, const float* __restrict__ packed, float fill,
+// One radar of a mosaic section: its search structure, the points and levels in its frame, its gate 0 inside the shared
+// packed fields.  sorted == nullptr: the radar takes no part (no gates, or no search structure) and nothing of it is read.
+struct SectionRadar {
+  const rg_gate4* sorted;
+  const int* cell_start;
+  Cells c;
+  const float* xs;
+  const float* ys;
+  const float* zc;
+  const float* packed;
+};
+struct SectionMosaicArgs {
+  SectionRadar r[RG_MAX_RADARS];
+  int n_radars;
+  int nz, n_points;
+  long n_samples;      // nz * n_points
+  double min_radius, beam_factor;
+};
+
+template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false>
+__global__ __launch_bounds__(rg::kBlock) void section_kernel(std::conditional_t<MOSAIC, SectionMosaicArgs, SectionArgs> a,
+                                                             const float* __restrict__ packed, float fill,
                                                              float* __restrict__ out, int* __restrict__ counts,
                                                              const long long* __restrict__ indptr, int* __restrict__ gidx,
                                                              float* __restrict__ wts) {
+  static_assert(!MOSAIC || MODE == kGridMode, "the mosaic section grids; its CSR is built radar by radar");
   __shared__ rg_gate4 ring_all[rg::kBlock / rg::kWave][kRing];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -72,16 +103,47 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, cons
   const int pl = lane & (kPts - 1);                                             // point of the block this lane owns
   const int slot = lane >> kLgPts;                                              // which of the kSlots records of a dense step
   const int ip = i0 + pl;
-  const Cells c = a.c;
-  const rg_gate4* sorted = a.sorted;
-  const int* cell_start = a.cell_start;
-  const int lvl_off = c.levels > 1 ? (c.level0 + iz) * (c.ncx * c.ncy) : 0;     // per-level gate lists: this level's cells
-
-  // ---- this lane's sample: the reference's float64 ROI (compute.py:46-47,57) and its float32 bounds ----------------
   const bool inside = ip < a.n_points;
-  const float xf = inside ? a.xs[ip] : 0.0f, yf = inside ? a.ys[ip] : 0.0f;
+
+  // acc_p = sum w*v, acc_w = sum w (this lane's point, this lane's record slot; with MOSAIC over all radars)
+  float acc_p[NF], acc_w[NF];
+#pragma unroll
+  for (int f = 0; f < NF; ++f) { acc_p[f] = 0.0f; acc_w[f] = 0.0f; }
+  int head = 0, tail = 0;    // ring positions (wave-uniform, monotone; head == tail between two radars)
+  // builder modes: hits of this lane's point so far (identical in the point's slot lanes) and its row base
+  int cursor = 0;
+  long long row_base = 0;
+  const size_t row = (size_t)iz * (size_t)a.n_points + (size_t)(inside ? ip : 0);
+  if constexpr (MODE == kFillMode) {
+    if (inside) row_base = indptr[row];
+  }
+  const unsigned long long pt_lanes = slot_lanes_of_point0() << pl;             // the slot lanes of point pl
+  const unsigned long long lower_slots = pt_lanes & ((1ull << (kPts * slot)) - 1ull);
+
+  int n_visits = 1;
+  if constexpr (MOSAIC) n_visits = a.n_radars;
+  for (int visit = 0; visit < n_visits; ++visit) {
+  // the search structure, the points and the levels of the radar being visited (the only one without MOSAIC)
+  const rg_gate4* sorted;
+  const int* cell_start;
+  const float *pxs, *pys, *pzc, *pk;
+  if constexpr (MOSAIC) {
+    const SectionRadar& R = a.r[visit];
+    if (R.sorted == nullptr) continue;                                          // takes no part (wave-uniform): nothing is read
+    sorted = R.sorted; cell_start = R.cell_start; pxs = R.xs; pys = R.ys; pzc = R.zc; pk = R.packed;
+  } else {
+    sorted = a.sorted; cell_start = a.cell_start; pxs = a.xs; pys = a.ys; pzc = a.zc; pk = packed;
+  }
+  // ---- this lane's sample: the reference's float64 ROI (compute.py:46-47,57) and its float32 bounds ----------------
+  const float xf = inside ? pxs[ip] : 0.0f, yf = inside ? pys[ip] : 0.0f;
   const bool live = inside && __builtin_isfinite(xf) && __builtin_isfinite(yf);
-  const double z = (double)a.zc[iz];                                            // common to the whole wave
+  if constexpr (MOSAIC) {
+    if (__ballot(live) == 0ull) continue;                                       // no point of the block is the radar's (wave-uniform)
+  }
+  Cells c;
+  if constexpr (MOSAIC) c = a.r[visit].c; else c = a.c;
+  const int lvl_off = c.levels > 1 ? (c.level0 + iz) * (c.ncx * c.ncy) : 0;     // per-level gate lists: this level's cells
+  const double z = (double)pzc[iz];                                             // common to the whole wave
   const float zf = (float)z;
   const Sample s = make_sample(live ? (double)xf : 0.0, live ? (double)yf : 0.0, z, live, a.min_radius, a.beam_factor);
   // ---- block-wide (wave-uniform) quantities: largest radius, the four sub-boxes and the block's box ----------------
@@ -108,21 +170,6 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, cons
   CellBox box = {0, -1, 0, -1};
   if (any_live) box = cell_box(xlo, xhi, ylo, yhi, rmax, c);
 
-  // acc_p = sum w*v, acc_w = sum w (this lane's point, this lane's record slot)
-  float acc_p[NF], acc_w[NF];
-#pragma unroll
-  for (int f = 0; f < NF; ++f) { acc_p[f] = 0.0f; acc_w[f] = 0.0f; }
-  int head = 0, tail = 0;    // ring positions (wave-uniform, monotone)
-  // builder modes: hits of this lane's point so far (identical in the point's slot lanes) and its row base
-  int cursor = 0;
-  long long row_base = 0;
-  const size_t row = (size_t)iz * (size_t)a.n_points + (size_t)(inside ? ip : 0);
-  if constexpr (MODE == kFillMode) {
-    if (inside) row_base = indptr[row];
-  }
-  const unsigned long long pt_lanes = slot_lanes_of_point0() << pl;             // the slot lanes of point pl
-  const unsigned long long lower_slots = pt_lanes & ((1ull << (kPts * slot)) - 1ull);
-
   auto dense = [&](int n) {  // test n queued records against the block's points, kSlots records per step
     for (int e0 = 0; e0 < n; e0 += kSlots) {
       const int e = e0 + slot;
@@ -138,7 +185,7 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, cons
         emit_hit<MODE, W>(in, g, s, pt_lanes, lower_slots, row_base, cursor, gidx, wts);
       } else if (in) {
         float val[STRIDE];
-        rg::load_packed<STRIDE>(packed, (unsigned)g.index, val);                          // one gather per hit
+        rg::load_packed<STRIDE>(pk, (unsigned)g.index, val);                              // one gather per hit
         accumulate<NF>(grid_weight<W>(g, s, d2f), val, acc_p, acc_w);
       }
     }
@@ -181,6 +228,8 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(SectionArgs a, cons
   }
   wave_sync();
   dense(tail - head);
+  if constexpr (MOSAIC) wave_sync();   // the next radar writes the ring from here on
+  }  // visit
 
   if constexpr (MODE == kCountMode) {
     if (slot == 0 && inside) counts[row] = cursor;
@@ -222,10 +271,10 @@ inline SectionArgs make_section_args(const rg_gate4* sorted, const int32_t* cell
   return a;
 }
 
-template <int MODE, int W, int NF, int STRIDE>
-int launch(const char* fn, const SectionArgs& a, const float* packed, float fill, float* out, int* counts,
+template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false, class Args>
+int launch(const char* fn, const Args& a, const float* packed, float fill, float* out, int* counts,
            const long long* indptr, int* gidx, float* wts, hipStream_t s) {
-  hipLaunchKernelGGL((section_kernel<MODE, W, NF, STRIDE>), dim3((unsigned)((section_waves(a.nz, a.n_points) + 3) / 4)),
+  hipLaunchKernelGGL((section_kernel<MODE, W, NF, STRIDE, MOSAIC>), dim3((unsigned)((section_waves(a.nz, a.n_points) + 3) / 4)),
                      dim3(rg::kBlock), 0, s, a, packed, fill, out, counts, indptr, gidx, wts);
   return rg::check_launch(fn);
 }
@@ -247,6 +296,50 @@ extern "C" int rg_roi_section_f32(const rg_gate4* sorted_gates, const int32_t* c
     return dispatch_fields(n_fields, [&](auto nf, auto st) {
       return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value>(
           fn, a, packed, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    });
+  });
+}
+
+// A section through several radars: per radar, radar_grid/compute.py:46-91 at the points in that radar's frame, and
+// radar_grid/interpolate.py:69-104 over the union of all radars' neighbours.  Every refusal happens before any launch.
+extern "C" int rg_roi_section_mosaic_f32(const rg_section_radar* radars_host, int32_t n_radars, int32_t nz,
+                                         int32_t n_points, double min_radius, double beam_factor, int32_t weighting,
+                                         const float* packed, int32_t n_fields, int32_t stride, int64_t n_gates_total,
+                                         float fill_value, float* out, rg_stream_t stream) {
+  const char* fn = "rg_roi_section_mosaic_f32";
+  RG_REQUIRE(radars_host, RG_EINVAL, "%s: null radar table", fn);
+  RG_REQUIRE(n_radars >= 1, RG_EINVAL, "%s: n_radars=%d", fn, n_radars);
+  RG_REQUIRE(n_radars <= RG_MAX_RADARS, RG_EUNSUPPORTED, "%s: n_radars=%d exceeds %d", fn, n_radars, RG_MAX_RADARS);
+  RG_REQUIRE(nz >= 1 && n_points >= 1, RG_EINVAL, "%s: bad section shape (nz=%d, n_points=%d)", fn, nz, n_points);
+  int rc = check_grid_args(fn, packed, out, weighting, RG_W_NEAREST, "a single-radar lattice mode", n_fields, stride);
+  if (rc != RG_OK) return rc;
+  // the gather takes a 32-bit slot number (rg::load_packed)
+  RG_REQUIRE(n_gates_total >= 0 && n_gates_total <= 0x7FFFFFFFL, RG_EUNSUPPORTED,
+             "%s: n_gates_total=%lld not in 0 .. 2^31 - 1", fn, (long long)n_gates_total);
+  RG_REQUIRE(section_waves(nz, n_points) < 0xFFFFFFF0L, RG_EUNSUPPORTED, "%s: section too large for one launch", fn);
+  SectionMosaicArgs a = {};
+  a.n_radars = n_radars;
+  a.nz = nz; a.n_points = n_points;
+  a.n_samples = (long)nz * n_points;
+  a.min_radius = min_radius; a.beam_factor = beam_factor;
+  for (int r = 0; r < n_radars; ++r) {
+    const rg_section_radar& e = radars_host[r];
+    // the kernel gathers packed[gate_offset + index] through a raw pointer: the offsets are what keep it in bounds
+    RG_REQUIRE(e.gate_offset >= 0 && e.n_gates >= 0 && e.gate_offset + e.n_gates <= n_gates_total, RG_EINVAL,
+               "%s: radar %d: gates %lld + %lld exceed n_gates_total=%lld", fn, r, (long long)e.gate_offset,
+               (long long)e.n_gates, (long long)n_gates_total);
+    if (e.n_gates == 0 || e.sorted_gates == nullptr) continue;   // takes no part: never visited, pointers not read
+    rc = check_section_args(fn, e.sorted_gates, e.cell_start, &e.cells, e.xs, e.ys, e.zc, nz, n_points);
+    if (rc != RG_OK) return rc;
+    SectionRadar& m = a.r[r];
+    m.sorted = e.sorted_gates; m.cell_start = e.cell_start; m.c = to_cells(&e.cells);
+    m.xs = e.xs; m.ys = e.ys; m.zc = e.zc;
+    m.packed = packed + e.gate_offset * stride;
+  }
+  return dispatch_weighting(weighting, [&](auto w) {
+    return dispatch_fields(n_fields, [&](auto nf, auto st) {
+      return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value, true>(
+          fn, a, nullptr, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
     });
   });
 }
