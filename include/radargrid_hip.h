@@ -39,7 +39,8 @@ extern "C" {
  * codes refused by the product build (round 4); 103 the row-wise kernel of rg_csr_compact_apply_packed_f32 takes 1-8 fields
  * (no signature changed: a 102 library answers RG_EUNSUPPORTED for 5-8); 104 rg_cellgrid.levels + the per-level gate lists
  * (rg_geom_bin_levels_count / rg_geom_bin_gates_levels_f32); still 104: the packed records' two codings -- no signature
- * changed, rg_csr_compact_pack_dense was ADDED (a library without it fails to bind by name) and rg_csr_compact_pack refuses work. */
+ * changed, rg_csr_compact_pack_dense was ADDED (a library without it fails to bind by name) and rg_csr_compact_pack refuses work; the
+ * mosaic combine rules -- rg_roi_grid_mosaic_combine_f32 and rg_roi_section_mosaic_combine_f32 were ADDED, no signature changed. */
 #define RG_VERSION 104
 #define RG_MAX_FIELDS 8
 
@@ -295,6 +296,34 @@ int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_t n_radars,
                            rg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * How a mosaic combines its radars: rg_roi_grid_mosaic_combine_f32 and rg_roi_section_mosaic_combine_f32 take the
+ * arguments of rg_roi_grid_mosaic_f32 / rg_roi_section_mosaic_f32 plus `combine` and `out_radar`, check them as those do
+ * (RG_W_CLOSEST stays RG_EUNSUPPORTED) and refuse an unknown combine code with RG_EINVAL.
+ *
+ * For field f and voxel (or section sample) v, radar k of the call's table HAS A VALUE when its own live weight sum is
+ * > 0; its value m_k is exactly what the mean entry point stores for a table holding only entry k -- the same arithmetic in
+ * the same order, from sums that start at zero when the radar's visit starts.
+ *   RG_COMBINE_MEAN           the joint mean: the bits of rg_roi_grid_mosaic_f32 / rg_roi_section_mosaic_f32.
+ *   RG_COMBINE_MAX            walk the table in order; radar k takes over when nothing is held yet, or m_k > held, or the
+ *                             held value is NaN and m_k is not.  Equal values, and -0.0 against +0.0, stay with the earlier
+ *                             table position.
+ *   RG_COMBINE_NEAREST_RADAR  among the radars that have a value, the one with the smallest D_k = x*x + y*y + z*z, in
+ *                             float64, unfused, from the float32 coordinates of v in radar k's frame (the expression under
+ *                             the square root of the radius of influence); equal D goes to the earlier table position.  A
+ *                             radar whose window misses v -- whose point is NaN -- has no value there.
+ * The winner's bits are copied, never computed with.  No radar has a value: fill_value.  The choice is per field (masks
+ * are per field).
+ * out_radar (may be null): uint8 [n_fields][n_samples], the table position of the radar that supplied the value, 255 where
+ * the value is the fill.  With RG_COMBINE_MEAN a non-null out_radar is RG_EINVAL.
+ * ------------------------------------------------------------------------------------------------- */
+typedef enum rg_combine { RG_COMBINE_MEAN = 0, RG_COMBINE_MAX = 1, RG_COMBINE_NEAREST_RADAR = 2 } rg_combine;
+
+int rg_roi_grid_mosaic_combine_f32(const rg_mosaic_radar* radars_host, int32_t n_radars, int32_t nz, int32_t ny,
+                                   int32_t nx, double min_radius, double beam_factor, int32_t weighting,
+                                   const float* packed, int32_t n_fields, int32_t stride, int64_t n_gates_total,
+                                   float fill_value, float* out, int32_t combine, uint8_t* out_radar, rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Vertical cross-section along any path: K2's arithmetic at n_points sample columns (xs[i], ys[i]) -- float32 metres in
  * the radar frame, device pointers; not necessarily equally spaced, sorted or distinct -- times the nz levels of zc.
  * Sample (k, i) is what radar_grid/compute.py:46-91 + radar_grid/interpolate.py:69-104 would put into a voxel lying exactly
@@ -351,6 +380,11 @@ int rg_roi_section_mosaic_f32(const rg_section_radar* radars_host, int32_t n_rad
                               double min_radius, double beam_factor, int32_t weighting, const float* packed,
                               int32_t n_fields, int32_t stride, int64_t n_gates_total, float fill_value, float* out,
                               rg_stream_t stream);
+/* ... with a combine rule (rg_combine, above): sample (k, i) is row k * n_points + i of out and of out_radar */
+int rg_roi_section_mosaic_combine_f32(const rg_section_radar* radars_host, int32_t n_radars, int32_t nz, int32_t n_points,
+                                      double min_radius, double beam_factor, int32_t weighting, const float* packed,
+                                      int32_t n_fields, int32_t stride, int64_t n_gates_total, float fill_value, float* out,
+                                      int32_t combine, uint8_t* out_radar, rg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * (f)3  processor-style collapse of the cached 3-D grid to the 2-D product plane:

@@ -22,7 +22,7 @@ from .grid_products import (EARTH_RADIUS, EFFECTIVE_RADIUS_FACTOR, column_argmax
                             get_elevation_from_z_level)
 from .gridding import PlaneProducts, apply_geometry, apply_geometry_multi, grid_fields_device, grid_products_device
 from .roi_grid import roi_grid_fields_device
-from .mosaic import (MosaicSearch, apply_mosaic, apply_mosaic_multi, compute_mosaic_geometry,
+from .mosaic import (MOSAIC_COMBINES, NO_RADAR, MosaicSearch, apply_mosaic, apply_mosaic_multi, compute_mosaic_geometry,
                      compute_mosaic_section_geometry, mosaic_fields_device, mosaic_limits, mosaic_section_fields_device,
                      mosaic_section_points, mosaic_vertical_section, path_reach, reach_window)
 from .section import (compute_section_geometry, section_fields_device, section_path, section_rectangle,
@@ -51,7 +51,7 @@ __all__ = [
     # build-specific additions
     "save_device_layout", "load_device_layout", "column_argmax", "grid_fields_device", "grid_products_device", "PlaneProducts", "roi_grid_fields_device", "build_grid3d_package", "device_gate_mask", "RoiSearch", "DeviceCSR",
     "mosaic_limits", "reach_window", "compute_mosaic_geometry", "apply_mosaic", "apply_mosaic_multi", "MosaicSearch",
-    "mosaic_fields_device",
+    "mosaic_fields_device", "MOSAIC_COMBINES", "NO_RADAR",
     "mosaic_section_points", "path_reach", "mosaic_section_fields_device", "compute_mosaic_section_geometry",
     "mosaic_vertical_section",
     "section_path", "section_rectangle", "section_fields_device", "compute_section_geometry", "vertical_section",

@@ -20,12 +20,14 @@ ABI_VERSION = 104          # include/radargrid_hip.h: RG_VERSION -- load_library
 
 RG_MAX_FIELDS = 8
 RG_MAX_RADARS = 16         # radars one rg_roi_grid_mosaic_f32 / rg_roi_section_mosaic_f32 launch takes
+RG_NO_RADAR = 255          # out_radar of the combine entry points: the value is the fill
 RG_EXCLUDED_BITS = 0x7FD1CE5D
 
 RG_OK, RG_EINVAL, RG_EALIGN, RG_ELAUNCH, RG_EWORKSPACE, RG_EUNSUPPORTED, RG_ENODEVICE = 0, -1, -2, -3, -4, -5, -6
 GATE_OPS = {"below": 0, "above": 1, "between": 2, "outside": 3, "equal": 4, "invalid": 5}
 COLUMN_OPS = {"max": 0, "min": 1, "mean": 2}
 WEIGHTINGS = {"barnes2": 0, "cressman": 1, "nearest": 2, "closest": 3}
+COMBINES = {"mean": 0, "max": 1, "nearest_radar": 2}     # rg_combine: how a mosaic launch combines its radars
 RG_MAX_PLANE_TESTS = 12
 RG_TEST_LO, RG_TEST_HI, RG_TEST_LO_INCLUSIVE, RG_TEST_NONFINITE = 1, 2, 4, 8
 RG_MINMAX_WORKSPACE_BYTES = 32768
@@ -152,11 +154,17 @@ SIGNATURES = {
                                   c_float, c_void_p, c_void_p]),
     "rg_roi_grid_mosaic_f32": (c_int32, [POINTER(MosaicRadar), c_int32, c_int32, c_int32, c_int32, c_double, c_double,
                                          c_int32, c_void_p, c_int32, c_int32, c_int64, c_float, c_void_p, c_void_p]),
+    "rg_roi_grid_mosaic_combine_f32": (c_int32, [POINTER(MosaicRadar), c_int32, c_int32, c_int32, c_int32, c_double,
+                                                 c_double, c_int32, c_void_p, c_int32, c_int32, c_int64, c_float, c_void_p,
+                                                 c_int32, c_void_p, c_void_p]),
     "rg_roi_section_f32": (c_int32, [c_void_p, c_void_p, POINTER(CellGrid), c_void_p, c_void_p, c_void_p, c_int32,
                                      c_int32, c_double, c_double, c_int32, c_void_p, c_int32, c_int32, c_float, c_void_p,
                                      c_void_p]),
     "rg_roi_section_mosaic_f32": (c_int32, [POINTER(SectionRadar), c_int32, c_int32, c_int32, c_double, c_double, c_int32,
                                             c_void_p, c_int32, c_int32, c_int64, c_float, c_void_p, c_void_p]),
+    "rg_roi_section_mosaic_combine_f32": (c_int32, [POINTER(SectionRadar), c_int32, c_int32, c_int32, c_double, c_double,
+                                                    c_int32, c_void_p, c_int32, c_int32, c_int64, c_float, c_void_p,
+                                                    c_int32, c_void_p, c_void_p]),
     "rg_section_count_f32": (c_int32, [c_void_p, c_void_p, POINTER(CellGrid), c_void_p, c_void_p, c_void_p, c_int32,
                                        c_int32, c_double, c_double, c_void_p, c_void_p]),
     "rg_section_fill_f32": (c_int32, [c_void_p, c_void_p, POINTER(CellGrid), c_void_p, c_void_p, c_void_p, c_int32,

@@ -68,11 +68,15 @@ struct MosaicArgs {
   int nz, ny, nx;
   long n_vox;
   double min_radius, beam_factor;
+  unsigned char* out_radar;   // rg_roi_grid_mosaic_combine_f32, RG_COMBINE_MAX / _NEAREST_RADAR: who supplied the value (or null)
 };
 
 // MOSAIC (grid mode only): a voxel block visits every radar whose window meets it, in table order, runs the search of that
 // radar over its lists and coordinates and adds its hits into the block's one set of accumulators; the radar's queue is
 // drained before the next radar starts, so a radar's candidates never move another radar's slot assignment.
+// COMBINE (with MOSAIC) = RG_COMBINE_MAX / RG_COMBINE_NEAREST_RADAR: the block has one set of accumulators still, but every
+// radar's visit ends with rg_roi_search.hpp's finish_visit -- the radar's own mean, offered to the held value of each voxel
+// and field, the sums cleared -- and the final store writes what is held.  RG_COMBINE_MEAN compiles none of it.
 template <int NF, int STRIDE>
 __device__ __forceinline__ void keep_closest(float d2f, int index, const float (&val)[STRIDE], float (&acc_p)[NF],
                                              float (&acc_w)[NF], int (&best_idx)[NF]) {
@@ -86,13 +90,14 @@ __device__ __forceinline__ void keep_closest(float d2f, int index, const float (
   }
 }
 
-template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false>
+template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false, int COMBINE = RG_COMBINE_MEAN>
 __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_t<MOSAIC, MosaicArgs, SearchArgs> a,
                                                                const float* __restrict__ packed, float fill,
                                                                float* __restrict__ out, int* __restrict__ counts,
                                                                const long long* __restrict__ indptr,
                                                                int* __restrict__ gidx, float* __restrict__ wts) {
   static_assert(!MOSAIC || MODE == kGridMode, "the mosaic grids; it builds no CSR");
+  static_assert(MOSAIC || COMBINE == RG_COMBINE_MEAN, "one radar has nothing to combine");
   constexpr int kVB = BX * BY;        // voxels per block
   constexpr int kSlots = 64 / kVB;    // queued records tested per dense step
   static_assert(kSlots == 4, "the builder's slot masks assume 4 records per dense step");
@@ -156,6 +161,8 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
     int best_idx[NF];
 #pragma unroll
     for (int f = 0; f < NF; ++f) { acc_p[f] = 0.0f; acc_w[f] = CLOSEST ? __builtin_inff() : 0.0f; best_idx[f] = 0x7FFFFFFF; }
+    Held<COMBINE, NF> held;  // MAX / NEAREST_RADAR: per field the winner so far (the mean: empty)
+    if constexpr (COMBINE != RG_COMBINE_MEAN) held.clear();
     int head = 0, tail = 0;  // ring positions (wave-uniform, monotone)
     int ready = 0;           // records [head, ready) are complete (grid mode: their values have been parked)
 
@@ -330,12 +337,26 @@ __global__ __launch_bounds__(rg::kBlock) void roi_block_kernel(std::conditional_
     wave_sync();
     dense(tail - head);
     wave_sync();
+    if constexpr (COMBINE != RG_COMBINE_MEAN) {
+      finish_visit<COMBINE, kVB>(visit, COMBINE == RG_COMBINE_NEAREST_RADAR ? antenna_d2(x, y, z) : 0.0, acc_p, acc_w, held);
+    }
     }   // visit: the radar's queue is empty
 
     if constexpr (MODE == kCountMode) {
       if (slot == 0 && vlive) counts[((size_t)iz * a.ny + (iy0 + byl)) * a.nx + (ix0 + b0 + bxl)] = cursor;
       continue;
     } else if constexpr (MODE == kFillMode) {
+      continue;
+    } else if constexpr (COMBINE != RG_COMBINE_MEAN) {
+      if (slot == 0 && vlive) {   // the four slot lanes of a voxel hold the same bits
+        const size_t v = ((size_t)iz * a.ny + (iy0 + byl)) * a.nx + (ix0 + b0 + bxl);
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+          const unsigned who = held.radar(f);
+          out[(size_t)f * a.n_vox + v] = who != 0xFFu ? held.v[f] : fill;
+          if (a.out_radar) a.out_radar[(size_t)f * a.n_vox + v] = (unsigned char)who;
+        }
+      }
       continue;
     }
     // ---- fold the 4 record slots; lanes 0..15 hold the block's 16 voxels ----------------------------------
@@ -374,10 +395,10 @@ inline int check_lattice_launch(const char* fn, int nz, int ny, int nx) {
   return RG_OK;
 }
 
-template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false, class Args>
+template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false, int COMBINE = RG_COMBINE_MEAN, class Args>
 int launch(const char* fn, const Args& a, const float* packed, float fill, float* out, int* counts, const long long* indptr,
            int* gidx, float* wts, hipStream_t s) {
-  hipLaunchKernelGGL((roi_block_kernel<MODE, W, NF, STRIDE, MOSAIC>),
+  hipLaunchKernelGGL((roi_block_kernel<MODE, W, NF, STRIDE, MOSAIC, COMBINE>),
                      dim3((unsigned)((lattice_waves(a.nz, a.ny, a.nx) + 3) / 4)), dim3(rg::kBlock), 0, s, a, packed, fill,
                      out, counts, indptr, gidx, wts);
   return rg::check_launch(fn);
@@ -414,16 +435,18 @@ extern "C" int rg_roi_grid_f32(const rg_gate4* sorted_gates, const int32_t* cell
 
 // Several radars on one grid: per radar, radar_grid/compute.py:46-91 in that radar's frame and radar_grid/interpolate.py:69-104
 // over the union of all radars' neighbours (a joint mean the reference does not have: it grids one radar per geometry).
-extern "C" int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_t n_radars, int32_t nz, int32_t ny,
-                                      int32_t nx, double min_radius, double beam_factor, int32_t weighting,
-                                      const float* packed, int32_t n_fields, int32_t stride, int64_t n_gates_total,
-                                      float fill_value, float* out, rg_stream_t stream) {
-  const char* fn = "rg_roi_grid_mosaic_f32";
+namespace {
+int grid_mosaic(const char* fn, const rg_mosaic_radar* radars_host, int32_t n_radars, int32_t nz, int32_t ny, int32_t nx,
+                double min_radius, double beam_factor, int32_t weighting, const float* packed, int32_t n_fields,
+                int32_t stride, int64_t n_gates_total, float fill_value, float* out, int32_t combine,
+                unsigned char* out_radar, rg_stream_t stream) {
   RG_REQUIRE(radars_host, RG_EINVAL, "%s: null radar table", fn);
   RG_REQUIRE(n_radars >= 1, RG_EINVAL, "%s: n_radars=%d", fn, n_radars);
   RG_REQUIRE(n_radars <= RG_MAX_RADARS, RG_EUNSUPPORTED, "%s: n_radars=%d exceeds %d", fn, n_radars, RG_MAX_RADARS);
   RG_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1, RG_EINVAL, "%s: bad grid shape (%d,%d,%d)", fn, nz, ny, nx);
   int rc = check_grid_args(fn, packed, out, weighting, RG_W_NEAREST, "single-radar", n_fields, stride);
+  if (rc != RG_OK) return rc;
+  rc = check_combine(fn, combine, out_radar);
   if (rc != RG_OK) return rc;
   // the gather takes a 32-bit slot number (rg::load_packed)
   RG_REQUIRE(n_gates_total >= 0 && n_gates_total <= 0x7FFFFFFFL, RG_EUNSUPPORTED,
@@ -435,6 +458,7 @@ extern "C" int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_
   a.nz = nz; a.ny = ny; a.nx = nx;
   a.n_vox = (long)nz * ny * nx;
   a.min_radius = min_radius; a.beam_factor = beam_factor;
+  a.out_radar = out_radar;
   for (int r = 0; r < n_radars; ++r) {
     const rg_mosaic_radar& e = radars_host[r];
     RG_REQUIRE(e.nx_win >= 0 && e.ny_win >= 0 && e.ix0 >= 0 && e.iy0 >= 0 && (long)e.ix0 + e.nx_win <= nx &&
@@ -454,12 +478,41 @@ extern "C" int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_
     m.packed = packed + e.gate_offset * stride;
     m.ix0 = e.ix0; m.iy0 = e.iy0; m.nxw = e.nx_win; m.nyw = e.ny_win;
   }
+  if (combine == RG_COMBINE_MEAN) {
+    return dispatch_weighting(weighting, [&](auto w) {
+      return dispatch_fields(n_fields, [&](auto nf, auto st) {
+        return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value, true>(
+            fn, a, nullptr, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+      });
+    });
+  }
   return dispatch_weighting(weighting, [&](auto w) {
     return dispatch_fields(n_fields, [&](auto nf, auto st) {
-      return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value, true>(
-          fn, a, nullptr, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+      return dispatch_combine(combine, [&](auto cb) {
+        return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value, true, decltype(cb)::value>(
+            fn, a, nullptr, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+      });
     });
   });
+}
+}  // namespace
+
+extern "C" int rg_roi_grid_mosaic_f32(const rg_mosaic_radar* radars_host, int32_t n_radars, int32_t nz, int32_t ny,
+                                      int32_t nx, double min_radius, double beam_factor, int32_t weighting,
+                                      const float* packed, int32_t n_fields, int32_t stride, int64_t n_gates_total,
+                                      float fill_value, float* out, rg_stream_t stream) {
+  return grid_mosaic("rg_roi_grid_mosaic_f32", radars_host, n_radars, nz, ny, nx, min_radius, beam_factor, weighting, packed,
+                     n_fields, stride, n_gates_total, fill_value, out, RG_COMBINE_MEAN, nullptr, stream);
+}
+
+// ... with a combine rule (rg_combine): RG_COMBINE_MEAN launches the kernel above, the other two their own instantiations
+extern "C" int rg_roi_grid_mosaic_combine_f32(const rg_mosaic_radar* radars_host, int32_t n_radars, int32_t nz, int32_t ny,
+                                              int32_t nx, double min_radius, double beam_factor, int32_t weighting,
+                                              const float* packed, int32_t n_fields, int32_t stride,
+                                              int64_t n_gates_total, float fill_value, float* out, int32_t combine,
+                                              uint8_t* out_radar, rg_stream_t stream) {
+  return grid_mosaic("rg_roi_grid_mosaic_combine_f32", radars_host, n_radars, nz, ny, nx, min_radius, beam_factor, weighting,
+                     packed, n_fields, stride, n_gates_total, fill_value, out, combine, out_radar, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

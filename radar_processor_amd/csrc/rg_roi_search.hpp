@@ -227,6 +227,73 @@ __device__ __forceinline__ void accumulate(float w, const float (&val)[STRIDE], 
   }
 }
 
+// ---- how a mosaic combines its radars (rg_combine, radargrid_hip.h) ------------------------------------------------------
+// RG_COMBINE_MEAN adds every radar's hits into one set of sums (the kernels' own visit loops; nothing here is used).  Under
+// RG_COMBINE_MAX / RG_COMBINE_NEAREST_RADAR every radar of the table finishes its OWN mean at the end of its visit -- sums
+// from zero, the final fold's shuffles, the final store's division: the bits the mean entry point stores for a table
+// holding that radar alone -- and offers it to the sample's held value.  The winner's bits are copied, never computed with.
+
+// D of a sample seen from the radar being visited: the float64, unfused expression make_sample forms under its sqrt
+__device__ __forceinline__ double antenna_d2(double x, double y, double z) { return x * x + y * y + z * z; }
+
+// The take-over test, the one place it is written.  has: radar k has a value (its live weight sum is > 0); any: a value is
+// held already.  The table is walked in order, so staying on equality gives ties to the earlier position: equal values and
+// -0.0 against +0.0 under MAX (neither is > the other), equal D under NEAREST_RADAR.  MAX: a held NaN yields to a number.
+template <int COMBINE>
+__device__ __forceinline__ bool takes_over(bool has, float m, double d, bool any, float held, double held_d) {
+  static_assert(COMBINE == RG_COMBINE_MAX || COMBINE == RG_COMBINE_NEAREST_RADAR, "the mean holds nothing");
+  if constexpr (COMBINE == RG_COMBINE_MAX) {
+    return has && (!any || m > held || (held != held && m == m));
+  } else {
+    return has && (!any || d < held_d);
+  }
+}
+
+// A sample's held state for NF fields (the choice is per field: masks are): the value, under NEAREST_RADAR the holder's D,
+// and the holder's table position, eight bits a field packed four to a register (255: nothing held).  Identical in all
+// lanes that own the sample.  The mean keeps none.
+template <int COMBINE, int NF>
+struct Held {
+  float v[NF];
+  double d[COMBINE == RG_COMBINE_NEAREST_RADAR ? NF : 1];
+  unsigned who[(NF + 3) / 4];
+
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int f = 0; f < NF; ++f) v[f] = 0.0f;
+#pragma unroll
+    for (int f = 0; f < (COMBINE == RG_COMBINE_NEAREST_RADAR ? NF : 1); ++f) d[f] = 0.0;
+#pragma unroll
+    for (int q = 0; q < (NF + 3) / 4; ++q) who[q] = 0xFFFFFFFFu;
+  }
+  __device__ __forceinline__ unsigned radar(int f) const { return (who[f >> 2] >> (8 * (f & 3))) & 0xFFu; }
+  __device__ __forceinline__ void offer(int f, int k, bool has, float m, double dk) {
+    constexpr bool NEAREST = COMBINE == RG_COMBINE_NEAREST_RADAR;
+    const bool take = takes_over<COMBINE>(has, m, dk, radar(f) != 0xFFu, v[f], d[NEAREST ? f : 0]);
+    v[f] = take ? m : v[f];
+    if constexpr (NEAREST) d[f] = take ? dk : d[f];
+    const unsigned sh = 8u * (unsigned)(f & 3);
+    who[f >> 2] = take ? (who[f >> 2] & ~(0xFFu << sh)) | ((unsigned)k << sh) : who[f >> 2];
+  }
+};
+template <int NF>
+struct Held<RG_COMBINE_MEAN, NF> {};
+
+// The end of radar k's visit under MAX / NEAREST_RADAR: fold the record slots of every field exactly as the mean's final
+// fold does (xor shuffles over FIRST, 2 * FIRST, .. 32 -- the lanes that own one sample; each ends with the same bits), form
+// the radar's ratio as the mean's final store does, offer it, and clear the sums for the next radar.  dk: antenna_d2.
+template <int COMBINE, int FIRST, int NF>
+__device__ __forceinline__ void finish_visit(int k, double dk, float (&acc_p)[NF], float (&acc_w)[NF], Held<COMBINE, NF>& held) {
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    float p = acc_p[f], w = acc_w[f];
+#pragma unroll
+    for (int m = FIRST; m < 64; m <<= 1) { p += __shfl_xor(p, m, 64); w += __shfl_xor(w, m, 64); }
+    held.offer(f, k, w > 0.0f, (float)((double)p / (double)w), dk);
+    acc_p[f] = 0.0f; acc_w[f] = 0.0f;
+  }
+}
+
 // ---- the candidate stream -------------------------------------------------------------------------------------------------
 // The cells a block's search box covers: its xy box widened by its largest radius (all wave-uniform)
 struct CellBox {
@@ -321,6 +388,15 @@ inline int check_grid_args(const char* fn, const float* packed, const float* out
   return RG_OK;
 }
 
+// The combine rule of a mosaic entry point (rg_combine) and its provenance output, which the joint mean does not have
+inline int check_combine(const char* fn, int combine, const void* out_radar) {
+  RG_REQUIRE(combine >= RG_COMBINE_MEAN && combine <= RG_COMBINE_NEAREST_RADAR, RG_EINVAL, "%s: unknown combine rule %d", fn,
+             combine);
+  RG_REQUIRE(combine != RG_COMBINE_MEAN || out_radar == nullptr, RG_EINVAL,
+             "%s: out_radar with RG_COMBINE_MEAN (a joint mean has no one radar behind it)", fn);
+  return RG_OK;
+}
+
 inline SearchArgs make_args(const rg_gate4* sorted, const int32_t* cell_start, const rg_cellgrid* cells, const float* xc,
                             const float* yc, const float* zc, int nz, int ny, int nx, double min_radius,
                             double beam_factor) {
@@ -361,6 +437,12 @@ int dispatch_weighting(int weighting, F&& f) {
     case RG_W_CRESSMAN: return f(int_c<RG_W_CRESSMAN>{});
     default: return f(int_c<RG_W_NEAREST>{});
   }
+}
+
+// combine (RG_COMBINE_MAX or RG_COMBINE_NEAREST_RADAR, checked by the caller; the mean has its own launch) -> f(int_c<COMBINE>)
+template <class F>
+int dispatch_combine(int combine, F&& f) {
+  return combine == RG_COMBINE_MAX ? f(int_c<RG_COMBINE_MAX>{}) : f(int_c<RG_COMBINE_NEAREST_RADAR>{});
 }
 
 }  // namespace roi

@@ -41,6 +41,9 @@
 // in that radar's arrays (dead, as above); a block without a live point skips the radar before anything of its search
 // structure is read, and an entry without gates is skipped before its points are.  The table travels by value in the kernel
 // arguments (16 x 112 bytes) and is indexed with the wave-uniform visit number: scalar loads, no scratch.
+// With a combine rule (rg_roi_section_mosaic_combine_f32, COMBINE = RG_COMBINE_MAX / RG_COMBINE_NEAREST_RADAR) every radar's
+// visit ends with rg_roi_search.hpp's finish_visit -- the radar's own mean of each sample and field, offered to the held
+// value, the sums cleared -- and the final store writes what is held; RG_COMBINE_MEAN compiles none of it.
 //
 // Compiled with -ffp-contract=off like every TU (the exact test must not be fused); the float32 tests use explicit fmaf,
 // their error is covered by the rim band (rg_roi_search.hpp).
@@ -80,15 +83,17 @@ struct SectionMosaicArgs {
   int nz, n_points;
   long n_samples;      // nz * n_points
   double min_radius, beam_factor;
+  unsigned char* out_radar;   // RG_COMBINE_MAX / _NEAREST_RADAR: who supplied the value (or null)
 };
 
-template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false>
+template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false, int COMBINE = RG_COMBINE_MEAN>
 __global__ __launch_bounds__(rg::kBlock) void section_kernel(std::conditional_t<MOSAIC, SectionMosaicArgs, SectionArgs> a,
                                                              const float* __restrict__ packed, float fill,
                                                              float* __restrict__ out, int* __restrict__ counts,
                                                              const long long* __restrict__ indptr, int* __restrict__ gidx,
                                                              float* __restrict__ wts) {
   static_assert(!MOSAIC || MODE == kGridMode, "the mosaic section grids; its CSR is built radar by radar");
+  static_assert(MOSAIC || COMBINE == RG_COMBINE_MEAN, "one radar has nothing to combine");
   __shared__ rg_gate4 ring_all[rg::kBlock / rg::kWave][kRing];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -109,6 +114,8 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(std::conditional_t<
   float acc_p[NF], acc_w[NF];
 #pragma unroll
   for (int f = 0; f < NF; ++f) { acc_p[f] = 0.0f; acc_w[f] = 0.0f; }
+  Held<COMBINE, NF> held;    // MAX / NEAREST_RADAR: per field the winner so far (the mean: empty)
+  if constexpr (COMBINE != RG_COMBINE_MEAN) held.clear();
   int head = 0, tail = 0;    // ring positions (wave-uniform, monotone; head == tail between two radars)
   // builder modes: hits of this lane's point so far (identical in the point's slot lanes) and its row base
   int cursor = 0;
@@ -229,6 +236,9 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(std::conditional_t<
   wave_sync();
   dense(tail - head);
   if constexpr (MOSAIC) wave_sync();   // the next radar writes the ring from here on
+  if constexpr (COMBINE != RG_COMBINE_MEAN) {
+    finish_visit<COMBINE, kPts>(visit, COMBINE == RG_COMBINE_NEAREST_RADAR ? antenna_d2(s.x, s.y, s.z) : 0.0, acc_p, acc_w, held);
+  }
   }  // visit
 
   if constexpr (MODE == kCountMode) {
@@ -236,6 +246,15 @@ __global__ __launch_bounds__(rg::kBlock) void section_kernel(std::conditional_t<
     return;
   } else if constexpr (MODE == kFillMode) {
     return;
+  } else if constexpr (COMBINE != RG_COMBINE_MEAN) {
+    if (slot == 0 && inside) {   // the slot lanes of a point hold the same bits
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        const unsigned who = held.radar(f);
+        out[(size_t)f * (size_t)a.n_samples + row] = who != 0xFFu ? held.v[f] : fill;
+        if (a.out_radar) a.out_radar[(size_t)f * (size_t)a.n_samples + row] = (unsigned char)who;
+      }
+    }
   } else {
     // ---- fold the record slots; lanes 0 .. kPts - 1 hold the block's points, consecutive samples of the level -------
 #pragma unroll
@@ -271,10 +290,10 @@ inline SectionArgs make_section_args(const rg_gate4* sorted, const int32_t* cell
   return a;
 }
 
-template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false, class Args>
+template <int MODE, int W, int NF, int STRIDE, bool MOSAIC = false, int COMBINE = RG_COMBINE_MEAN, class Args>
 int launch(const char* fn, const Args& a, const float* packed, float fill, float* out, int* counts,
            const long long* indptr, int* gidx, float* wts, hipStream_t s) {
-  hipLaunchKernelGGL((section_kernel<MODE, W, NF, STRIDE, MOSAIC>), dim3((unsigned)((section_waves(a.nz, a.n_points) + 3) / 4)),
+  hipLaunchKernelGGL((section_kernel<MODE, W, NF, STRIDE, MOSAIC, COMBINE>), dim3((unsigned)((section_waves(a.nz, a.n_points) + 3) / 4)),
                      dim3(rg::kBlock), 0, s, a, packed, fill, out, counts, indptr, gidx, wts);
   return rg::check_launch(fn);
 }
@@ -302,16 +321,18 @@ extern "C" int rg_roi_section_f32(const rg_gate4* sorted_gates, const int32_t* c
 
 // A section through several radars: per radar, radar_grid/compute.py:46-91 at the points in that radar's frame, and
 // radar_grid/interpolate.py:69-104 over the union of all radars' neighbours.  Every refusal happens before any launch.
-extern "C" int rg_roi_section_mosaic_f32(const rg_section_radar* radars_host, int32_t n_radars, int32_t nz,
-                                         int32_t n_points, double min_radius, double beam_factor, int32_t weighting,
-                                         const float* packed, int32_t n_fields, int32_t stride, int64_t n_gates_total,
-                                         float fill_value, float* out, rg_stream_t stream) {
-  const char* fn = "rg_roi_section_mosaic_f32";
+namespace {
+int section_mosaic(const char* fn, const rg_section_radar* radars_host, int32_t n_radars, int32_t nz, int32_t n_points,
+                   double min_radius, double beam_factor, int32_t weighting, const float* packed, int32_t n_fields,
+                   int32_t stride, int64_t n_gates_total, float fill_value, float* out, int32_t combine,
+                   unsigned char* out_radar, rg_stream_t stream) {
   RG_REQUIRE(radars_host, RG_EINVAL, "%s: null radar table", fn);
   RG_REQUIRE(n_radars >= 1, RG_EINVAL, "%s: n_radars=%d", fn, n_radars);
   RG_REQUIRE(n_radars <= RG_MAX_RADARS, RG_EUNSUPPORTED, "%s: n_radars=%d exceeds %d", fn, n_radars, RG_MAX_RADARS);
   RG_REQUIRE(nz >= 1 && n_points >= 1, RG_EINVAL, "%s: bad section shape (nz=%d, n_points=%d)", fn, nz, n_points);
   int rc = check_grid_args(fn, packed, out, weighting, RG_W_NEAREST, "a single-radar lattice mode", n_fields, stride);
+  if (rc != RG_OK) return rc;
+  rc = check_combine(fn, combine, out_radar);
   if (rc != RG_OK) return rc;
   // the gather takes a 32-bit slot number (rg::load_packed)
   RG_REQUIRE(n_gates_total >= 0 && n_gates_total <= 0x7FFFFFFFL, RG_EUNSUPPORTED,
@@ -322,6 +343,7 @@ extern "C" int rg_roi_section_mosaic_f32(const rg_section_radar* radars_host, in
   a.nz = nz; a.n_points = n_points;
   a.n_samples = (long)nz * n_points;
   a.min_radius = min_radius; a.beam_factor = beam_factor;
+  a.out_radar = out_radar;
   for (int r = 0; r < n_radars; ++r) {
     const rg_section_radar& e = radars_host[r];
     // the kernel gathers packed[gate_offset + index] through a raw pointer: the offsets are what keep it in bounds
@@ -336,12 +358,41 @@ extern "C" int rg_roi_section_mosaic_f32(const rg_section_radar* radars_host, in
     m.xs = e.xs; m.ys = e.ys; m.zc = e.zc;
     m.packed = packed + e.gate_offset * stride;
   }
+  if (combine == RG_COMBINE_MEAN) {
+    return dispatch_weighting(weighting, [&](auto w) {
+      return dispatch_fields(n_fields, [&](auto nf, auto st) {
+        return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value, true>(
+            fn, a, nullptr, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+      });
+    });
+  }
   return dispatch_weighting(weighting, [&](auto w) {
     return dispatch_fields(n_fields, [&](auto nf, auto st) {
-      return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value, true>(
-          fn, a, nullptr, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+      return dispatch_combine(combine, [&](auto cb) {
+        return launch<kGridMode, decltype(w)::value, decltype(nf)::value, decltype(st)::value, true, decltype(cb)::value>(
+            fn, a, nullptr, fill_value, out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+      });
     });
   });
+}
+}  // namespace
+
+extern "C" int rg_roi_section_mosaic_f32(const rg_section_radar* radars_host, int32_t n_radars, int32_t nz,
+                                         int32_t n_points, double min_radius, double beam_factor, int32_t weighting,
+                                         const float* packed, int32_t n_fields, int32_t stride, int64_t n_gates_total,
+                                         float fill_value, float* out, rg_stream_t stream) {
+  return section_mosaic("rg_roi_section_mosaic_f32", radars_host, n_radars, nz, n_points, min_radius, beam_factor, weighting,
+                        packed, n_fields, stride, n_gates_total, fill_value, out, RG_COMBINE_MEAN, nullptr, stream);
+}
+
+// ... with a combine rule (rg_combine): RG_COMBINE_MEAN launches the kernel above, the other two their own instantiations
+extern "C" int rg_roi_section_mosaic_combine_f32(const rg_section_radar* radars_host, int32_t n_radars, int32_t nz,
+                                                 int32_t n_points, double min_radius, double beam_factor, int32_t weighting,
+                                                 const float* packed, int32_t n_fields, int32_t stride,
+                                                 int64_t n_gates_total, float fill_value, float* out, int32_t combine,
+                                                 uint8_t* out_radar, rg_stream_t stream) {
+  return section_mosaic("rg_roi_section_mosaic_combine_f32", radars_host, n_radars, nz, n_points, min_radius, beam_factor,
+                        weighting, packed, n_fields, stride, n_gates_total, fill_value, out, combine, out_radar, stream);
 }
 
 // count -> prefix sum (rg_scan_counts_i64) -> fill: a section as an ordinary CSR of nz * n_points rows

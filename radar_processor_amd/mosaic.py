@@ -45,6 +45,8 @@ from .roi_grid import pack_and_grid
 from .section import _check_points, _cumulative_distance, section_path, section_rectangle
 
 _GATHER_BYTES = 2 ** 32        # buffer-resource range of the packed-field gather in rg_csr_apply_f32
+MOSAIC_COMBINES = tuple(_native.COMBINES)      # "mean", "max", "nearest_radar": the combine rules of the CSR-free route
+NO_RADAR = _native.RG_NO_RADAR                 # in a ``radar`` map: no radar has a value there (the grid holds the fill)
 
 
 def mosaic_limits(grid_limits, origin) -> Tuple[Tuple[float, float], ...]:
@@ -462,9 +464,28 @@ def _check_device_inputs(fields, masks, shared_masks, counts, n_fields, torch, d
                 raise ValueError(f"radar {r} mask {f}: expected a contiguous cuda uint8 tensor on {dev}")
 
 
+def _check_combine(combine: str, return_radar: bool, is_geometry: bool = False) -> None:
+    """The combine rule of a CSR-free mosaic call; raises ValueError, touches no device."""
+    if combine not in _native.COMBINES:
+        raise ValueError(f"Unknown combine rule: {combine} (one of {', '.join(_native.COMBINES)})")
+    if return_radar and combine == "mean":
+        raise ValueError("return_radar needs combine='max' or 'nearest_radar': a joint mean has no one radar behind it")
+    if is_geometry and combine != "mean":
+        raise ValueError(f"combine='{combine}' needs a MosaicSearch: a mosaic geometry is one CSR over all radars, a joint "
+                         "mean by construction")
+
+
+def _radar_indices(radar, sel, torch):
+    """``out_radar`` of a combine launch (table positions, 255 = none) -> indices of the radars in the MosaicSearch."""
+    lut = torch.full((256,), _native.RG_NO_RADAR, dtype=torch.uint8, device=radar.device)
+    lut[:len(sel)] = torch.tensor(sel, dtype=torch.uint8, device=radar.device)
+    return lut[radar.long()]
+
+
 def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Sequence] = None,
                          shared_masks: Optional[Sequence] = None, weighting: str = "barnes2", fill_value: float = np.nan,
-                         products=None, radars: Optional[Sequence[int]] = None):
+                         products=None, radars: Optional[Sequence[int]] = None, combine: str = "mean",
+                         return_radar: bool = False):
     """Grid device-resident fields of several radars onto the shared grid.
 
     ``target``: a mosaic ``GridGeometry`` (:func:`compute_mosaic_geometry`) or a :class:`MosaicSearch`.
@@ -473,12 +494,21 @@ def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Seq
     ``MosaicSearch`` the call holds, in that order (default: all) -- any subset; for a geometry it must be all of them, in
     order (its gate numbering is fixed).  ``weighting`` applies to the search route only (a geometry carries its weights).
 
+    ``combine`` (search route only): ``"mean"`` -- the joint weighted mean over the union of every radar's neighbours
+    (``rg_roi_grid_mosaic_f32``); ``"max"`` -- per voxel and field the largest of the radars' own means; ``"nearest_radar"``
+    -- the mean of the radar whose antenna is closest to the voxel, among those that have one
+    (``rg_roi_grid_mosaic_combine_f32``: one launch, no per-radar grids; the rules, ties included, are in
+    ``include/radargrid_hip.h``).  A radar's own mean is, bit for bit, what ``radars=[r]`` returns.  ``return_radar=True``
+    (not with ``"mean"``) returns ``(grids, radar)``: ``radar`` uint8 ``[F, nz, ny, nx]``, the index in the
+    ``MosaicSearch`` of the radar that supplied each value, 255 where the value is the fill.
+
     Returns ``[F, nz, ny, nx]`` float32, or with a ``PlaneProducts`` what ``grid_products_device`` returns: the geometry
     route goes through ``grid_products_device`` itself (``fused=True`` planes come out of its epilogue), the search route
     grids, then reduces with the separate kernels.  Every argument is validated before the device is touched."""
     is_geometry = isinstance(target, GridGeometry)
     if not is_geometry and not isinstance(target, MosaicSearch):
         raise TypeError("target must be a mosaic GridGeometry or a MosaicSearch")
+    _check_combine(combine, return_radar, is_geometry)
     if is_geometry:
         offsets = _mosaic_layout(target)
         n_all = len(offsets) - 1
@@ -511,10 +541,11 @@ def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Seq
                 return grid_products_device(target, cat_fields, cat_field_masks, cat_shared, products=products,
                                             fill_value=fill_value)
             return grid_fields_device(target, cat_fields, cat_field_masks, cat_shared, fill_value=fill_value)
-        grids = _search_grid(target, sel, counts, cat_fields, cat_field_masks, cat_shared, weighting, fill_value, dev)
+        grids, radar = _search_grid(target, sel, counts, cat_fields, cat_field_masks, cat_shared, weighting, fill_value,
+                                    dev, combine, return_radar)
     if products is not None:
-        return _products_of_grids(products, grids, target)
-    return grids
+        grids = _products_of_grids(products, grids, target)
+    return (grids, radar) if return_radar else grids
 
 
 def _select(n_all: int, radars) -> List[int]:
@@ -571,18 +602,42 @@ def _concat_on_device(fields, masks, shared_masks, counts, n_fields, torch, dev)
     return cat_fields, cat_field_masks, cat_masks(lambda k: shared_masks[k])
 
 
-def _search_grid(search: MosaicSearch, sel, counts, fields, masks, shared_mask, weighting, fill_value, dev):
+def _combine_launcher(entry, name: str, head, weighting, n_total, fill, combine, radar):
+    """``pack_and_grid``'s launch callback for a combine entry point: the groups of fields arrive in order, each writes
+    its rows of ``radar`` (uint8 ``[F, n_out]``, or ``None``)."""
+    done = [0]
+
+    def launch(packed, nf, stride, out_view, stream):
+        who = None if radar is None else radar[done[0]:done[0] + nf]
+        done[0] += nf
+        _native.check(entry(*head, _native.WEIGHTINGS[weighting], _native.ptr(packed), nf, stride, n_total, fill,
+                            _native.ptr(out_view), _native.COMBINES[combine], _native.ptr(who), stream), name)
+    return launch
+
+
+def _search_grid(search: MosaicSearch, sel, counts, fields, masks, shared_mask, weighting, fill_value, dev,
+                 combine="mean", return_radar=False):
+    """``(grids, radar)``; ``radar`` is ``None`` unless asked for."""
     lib = _native.load_library()
     nz, ny, nx = search.grid_shape
     n_total = sum(counts)
     table = search.table(sel, _offsets(counts)[:-1])
     fill = float(np.float32(fill_value))
-
-    def launch(packed, nf, stride, out_view, stream):
-        _native.check(lib.rg_roi_grid_mosaic_f32(
-            table, len(sel), nz, ny, nx, search.min_radius, search.beam_factor, _native.WEIGHTINGS[weighting],
-            _native.ptr(packed), nf, stride, n_total, fill, _native.ptr(out_view), stream), "rg_roi_grid_mosaic_f32")
-    return pack_and_grid(dev, n_total, fields, masks, shared_mask, None, (nz, ny, nx), launch)
+    if combine == "mean":
+        def launch(packed, nf, stride, out_view, stream):
+            _native.check(lib.rg_roi_grid_mosaic_f32(
+                table, len(sel), nz, ny, nx, search.min_radius, search.beam_factor, _native.WEIGHTINGS[weighting],
+                _native.ptr(packed), nf, stride, n_total, fill, _native.ptr(out_view), stream), "rg_roi_grid_mosaic_f32")
+        return pack_and_grid(dev, n_total, fields, masks, shared_mask, None, (nz, ny, nx), launch), None
+    torch = _native.torch_mod()
+    radar = torch.empty((len(fields), nz * ny * nx), dtype=torch.uint8, device=dev) if return_radar else None
+    head = (table, len(sel), nz, ny, nx, search.min_radius, search.beam_factor)
+    launch = _combine_launcher(lib.rg_roi_grid_mosaic_combine_f32, "rg_roi_grid_mosaic_combine_f32", head, weighting,
+                               n_total, fill, combine, radar)
+    grids = pack_and_grid(dev, n_total, fields, masks, shared_mask, None, (nz, ny, nx), launch)
+    if radar is not None:
+        radar = _radar_indices(radar, sel, torch).view(len(fields), nz, ny, nx)
+    return grids, radar
 
 
 def _products_of_grids(products, grids, spec) -> List[dict]:
@@ -644,17 +699,20 @@ def _no_closest(weighting: str) -> None:
 
 def mosaic_section_fields_device(search: MosaicSearch, xs, ys, fields: Sequence[Sequence], masks: Optional[Sequence] = None,
                                  shared_masks: Optional[Sequence] = None, weighting: str = "barnes2",
-                                 fill_value: float = np.nan, radars: Optional[Sequence[int]] = None):
+                                 fill_value: float = np.nan, radars: Optional[Sequence[int]] = None, combine: str = "mean",
+                                 return_radar: bool = False):
     """Grid device-resident fields of several radars at the columns ``(xs[i], ys[i])`` -- float32 metres in the shared grid
     frame, inside the search's rectangle -- straight from the gates (``rg_roi_section_mosaic_f32``): sample ``(k, i)`` is
     the masked weighted mean over the union of every radar's neighbours of the point, each radar in its own frame
     (:func:`mosaic_section_points`).  ``search``: a :class:`MosaicSearch` of a lattice, or of the path itself
     (:meth:`MosaicSearch.for_path`).  ``fields`` / ``masks`` / ``shared_masks`` / ``radars`` as in
     :func:`mosaic_fields_device`; more than ``RG_MAX_FIELDS`` fields go in groups.  Returns ``[F, nz, n_points]`` float32.
-    Every argument is validated before the device is touched."""
+    ``combine`` / ``return_radar`` as in :func:`mosaic_fields_device` (``rg_roi_section_mosaic_combine_f32``; ``radar`` is
+    uint8 ``[F, nz, n_points]``).  Every argument is validated before the device is touched."""
     if not isinstance(search, MosaicSearch):
         raise TypeError("search must be a MosaicSearch")
     _no_closest(weighting)
+    _check_combine(combine, return_radar)
     all_points = mosaic_section_points(search, xs, ys)
     sel = _select(search.n_radars, radars)
     counts, fields, n_fields, masks, shared_masks, n_total = _check_fields(sel, search.n_gates, fields, masks, shared_masks)
@@ -675,11 +733,21 @@ def mosaic_section_fields_device(search: MosaicSearch, xs, ys, fields: Sequence[
                   (torch.from_numpy(all_points[r][0]).to(dev), torch.from_numpy(all_points[r][1]).to(dev)) for r in sel]
         table = search.section_table(sel, _offsets(counts)[:-1], points)
 
-        def launch(packed, nf, stride, out_view, stream):
-            _native.check(lib.rg_roi_section_mosaic_f32(
-                table, len(sel), nz, n_points, search.min_radius, search.beam_factor, _native.WEIGHTINGS[weighting],
-                _native.ptr(packed), nf, stride, n_total, fill, _native.ptr(out_view), stream), "rg_roi_section_mosaic_f32")
-        return pack_and_grid(dev, n_total, cat_fields, cat_field_masks, cat_shared, None, (nz, n_points), launch)
+        if combine == "mean":
+            def launch(packed, nf, stride, out_view, stream):
+                _native.check(lib.rg_roi_section_mosaic_f32(
+                    table, len(sel), nz, n_points, search.min_radius, search.beam_factor, _native.WEIGHTINGS[weighting],
+                    _native.ptr(packed), nf, stride, n_total, fill, _native.ptr(out_view), stream),
+                    "rg_roi_section_mosaic_f32")
+            return pack_and_grid(dev, n_total, cat_fields, cat_field_masks, cat_shared, None, (nz, n_points), launch)
+        radar = torch.empty((n_fields, nz * n_points), dtype=torch.uint8, device=dev) if return_radar else None
+        head = (table, len(sel), nz, n_points, search.min_radius, search.beam_factor)
+        launch = _combine_launcher(lib.rg_roi_section_mosaic_combine_f32, "rg_roi_section_mosaic_combine_f32", head,
+                                   weighting, n_total, fill, combine, radar)
+        out = pack_and_grid(dev, n_total, cat_fields, cat_field_masks, cat_shared, None, (nz, n_points), launch)
+        if radar is None:
+            return out
+        return out, _radar_indices(radar, sel, torch).view(n_fields, nz, n_points)
 
 
 def compute_mosaic_section_geometry(radars, xs, ys, z_limits, nz, min_radius: float = 250.0, beam_factor: float = 0.01746,
@@ -741,14 +809,16 @@ def compute_mosaic_section_geometry(radars, xs, ys, z_limits, nz, min_radius: fl
 
 def mosaic_vertical_section(radars, fields: Sequence, vertices, spacing, z_limits, nz, additional_filters=None,
                             min_radius: float = 250.0, beam_factor: float = 0.01746, weighting: str = "barnes2",
-                            toa: float = 17000.0, fill_value: float = np.nan):
+                            toa: float = 17000.0, fill_value: float = np.nan, combine: str = "mean"):
     """One masked field of every radar on the vertical section along the polyline ``vertices`` (grid frame) sampled every
     ``spacing`` metres (:func:`section_path`), ``nz`` levels over ``z_limits``: NumPy in, NumPy out.  ``radars``:
     ``[(gate_x, gate_y, gate_z, origin), ...]``, at most ``RG_MAX_RADARS``; ``fields[r]`` radar r's (masked) field in the
     reference format, ``additional_filters[r]`` its list of ``GateFilter``.  Returns ``(section float32 [nz, n_points],
-    s float64 [n_points])`` -- :func:`mosaic_section_fields_device` on :meth:`MosaicSearch.for_path`."""
+    s float64 [n_points])`` -- :func:`mosaic_section_fields_device` on :meth:`MosaicSearch.for_path`, with its ``combine``
+    rule (``"mean"``, ``"max"`` or ``"nearest_radar"``)."""
     xs, ys, s = section_path(vertices, spacing)
     _no_closest(weighting)
+    _check_combine(combine, False)
     radars = list(radars)
     counts, _ = _check_radars(radars, max_radars=_native.RG_MAX_RADARS)
     fields = list(fields)
@@ -767,5 +837,6 @@ def mosaic_vertical_section(radars, fields: Sequence, vertices, spacing, z_limit
     torch = _native.torch_mod()
     f_ts = [[torch.from_numpy(v).to(search.dev)] for v, _ in host]
     m_ts = [[torch.from_numpy(m).to(search.dev) if m.any() else None] for _, m in host]
-    out = mosaic_section_fields_device(search, xs, ys, f_ts, m_ts, weighting=weighting, fill_value=fill_value)
+    out = mosaic_section_fields_device(search, xs, ys, f_ts, m_ts, weighting=weighting, fill_value=fill_value,
+                                       combine=combine)
     return _to_host(out[0]), s
