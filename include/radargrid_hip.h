@@ -57,7 +57,9 @@ typedef enum rg_status {
 } rg_status;
 
 /* Quiet-NaN bit pattern that marks "gate excluded for this field" inside packed fields.  A data NaN that
- * is NOT masked keeps its own payload and propagates like in NumPy (interpolate.py:78-82). */
+ * is NOT masked keeps its own payload and propagates like in NumPy (interpolate.py:78-82), with one exception: an
+ * unmasked value that carries exactly these bits is stored by rg_pack_fields_f32 as the canonical quiet NaN 0x7FC00000, so
+ * that it keeps propagating as a NaN and is never taken for the sentinel. */
 #define RG_EXCLUDED_BITS 0x7FD1CE5Du
 
 int rg_version(void);
@@ -79,7 +81,8 @@ int rg_antenna_to_cartesian_f32(const double* ranges_m, int32_t n_gates,
 
 /* ---------------------------------------------------------------------------------------------------
  * a3  GateFilter predicates (radar_grid/filters.py:114-258): mask_inout[g] |= pred(data[g]).
- * NaN compares false, so threshold filters never exclude NaN gates (filters.py:134).
+ * NaN compares false, so threshold filters never exclude NaN gates (filters.py:134).  Any non-zero byte of mask_inout
+ * counts as set; the kernel ORs 1 into the byte where the predicate holds and leaves the other bits as they are.
  * ------------------------------------------------------------------------------------------------- */
 typedef enum rg_gate_op {
   RG_GATE_BELOW = 0,   /* data <  a            filters.py:134 */
@@ -98,7 +101,9 @@ int rg_gate_mask_f32(const float* data, int64_t n_gates, int32_t op, float a, fl
  *   packed[g*stride + f] = (masks_host[f] && masks_host[f][g]) || (shared_mask && shared_mask[g])
  *                          ? EXCLUDED : fields_host[f][g]          for f <  n_fields
  *                          = EXCLUDED                               for f >= n_fields (padding slots)
- * fields_host / masks_host are HOST arrays of n_fields DEVICE pointers (mask entries may be NULL).
+ * fields_host / masks_host are HOST arrays of n_fields DEVICE pointers (mask entries may be NULL, and so may masks_host);
+ * any non-zero mask byte excludes.  An unmasked value keeps its bits, NaN payloads included -- except the one value whose
+ * bits are RG_EXCLUDED_BITS, which is stored as the canonical quiet NaN 0x7FC00000 (see RG_EXCLUDED_BITS).
  * ------------------------------------------------------------------------------------------------- */
 int rg_pack_fields_f32(int32_t n_fields, const float* const* fields_host, const uint8_t* const* masks_host,
                        const uint8_t* shared_mask, int64_t n_gates, int32_t stride, float* packed,
@@ -196,7 +201,8 @@ typedef struct rg_gate4 { float x, y, z; int32_t index; } rg_gate4; /* 16 bytes:
  * uses behind the 3-D grid cache; PyART is not in the reference tree, so this mode is parity-unpinned.  Its contract:
  * membership is the float64 `d2 < r2` of every mode; among the member gates the field does not exclude, the smallest float32
  * d2 = fmaf(dz,dz,fmaf(dy,dy,dx*dx)) wins and bit-equal d2 go to the LOWER gate index; the winner's value is stored bit for
- * bit, fill_value where there is none.  To float64 the winner is at most (1 + 5u)/(1 - 5u), u = 2^-24, farther (in d2) than
+ * bit (as packed: a value carrying the bits of RG_EXCLUDED_BITS arrives as the canonical quiet NaN, the one exception),
+ * fill_value where there is none.  To float64 the winner is at most (1 + 5u)/(1 - 5u), u = 2^-24, farther (in d2) than
  * the nearest member (oracle.closest_gate_choice derives it; tests/test_gpu_closest.py checks every voxel). */
 typedef enum rg_weighting { RG_W_BARNES2 = 0, RG_W_CRESSMAN = 1, RG_W_NEAREST = 2, RG_W_CLOSEST = 3 } rg_weighting;
 
@@ -210,12 +216,15 @@ int rg_geom_bin_gates_f32(const float* gate_x, const float* gate_y, const float*
                           rg_gate4* sorted_gates, int32_t* cell_start,
                           void* workspace, int64_t workspace_bytes, rg_stream_t stream);
 
-/* Per-level lists: gate g is listed under level iz iff |z_rel(g) - zc[iz]| <= R_g, R_g = max(min_radius, beam_factor * |g| /
- * (1 - beam_factor)) (slightly inflated) -- a bound on the radius of influence of ANY voxel the gate can be a neighbour of
- * (compute.py:46-47: r_v = max(min_radius, |v| * beam_factor) and |v| <= |g| + r_v), so no neighbour is lost; needs
- * 0 <= beam_factor < 1.  rg_geom_bin_levels_count writes the number of (gate, level) entries to *total (device memory);
+/* Per-level lists: a gate g that rg_geom_bin_gates_f32 would keep is listed under level iz when |z_rel(g) - zc[iz]| <= R_g,
+ * R_g = max(min_radius, beam_factor * |g| / (1 - beam_factor)), and under no level beyond the inflated bound
+ * (1 + 1e-6) * R_g + 1 mm (the inflation covers the rounding of this very computation) -- R_g bounds the radius of influence
+ * of ANY voxel the gate can be a neighbour of (compute.py:46-47: r_v = max(min_radius, |v| * beam_factor) and
+ * |v| <= |g| + r_v), so no neighbour is lost; needs 0 <= beam_factor < 0.5 and min_radius >= 0 (RG_EUNSUPPORTED otherwise:
+ * use the single list).  rg_geom_bin_levels_count writes the number of (gate, level) entries to *total (device memory);
  * rg_geom_bin_gates_levels_f32 then fills sorted_gates[n_entries] in (level, cell, gate index) order and
- * cell_start[nz*ncx*ncy + 1] (cells->levels must equal nz).  zc: the float32 level coordinates (device). */
+ * cell_start[nz*ncx*ncy + 1] (cells->levels must equal nz).  n_entries must be the total rg_geom_bin_levels_count returned
+ * for the same arguments: it sizes the buffers and is not re-checked.  zc: the float32 level coordinates (device). */
 int rg_geom_bin_levels_count(const float* gate_x, const float* gate_y, const float* gate_z, int64_t n_gates,
                              float radar_altitude, float toa, const rg_cellgrid* cells_host, const float* zc, int32_t nz,
                              double min_radius, double beam_factor, int64_t* total, rg_stream_t stream);

@@ -299,6 +299,52 @@ class TestNativeLibrary:
         assert lib.rg_geom_count_f32(1 << 12, 1 << 12, cells, 1 << 12, 1 << 12, 1 << 12, 3, 4, 4, 250.0, 0.01746, 1 << 12,
                                      None) == _native.RG_EINVAL and b"levels 3 .. 5" in lib.rg_last_error()
 
+    def test_prologue_entry_points_refuse_bad_arguments_before_any_launch(self):
+        """rg_gate_mask_f32, rg_pack_fields_f32, rg_scan_counts_i64 and the binning entry points: alignment, strides, field
+        counts, null entries, negative sizes, a short workspace and beam_factor 0.5 (fake pointers, never dereferenced)."""
+        lib = rg.load_library(require_device=False)
+        p = 1 << 12
+        EINVAL, EALIGN, EUNSUP, EWS = _native.RG_EINVAL, _native.RG_EALIGN, _native.RG_EUNSUPPORTED, _native.RG_EWORKSPACE
+        for off in (1, 2, 3):
+            assert lib.rg_gate_mask_f32(p, 8, 0, 0.0, 0.0, p + off, None) == EALIGN, off
+        assert lib.rg_gate_mask_f32(p + 4, 8, 0, 0.0, 0.0, p, None) == EALIGN
+        assert b"aligned" in lib.rg_last_error()
+        assert lib.rg_gate_mask_f32(p, -1, 0, 0.0, 0.0, p, None) == EINVAL
+        assert lib.rg_gate_mask_f32(p, 0, 0, 0.0, 0.0, p, None) == _native.RG_OK
+
+        def ptrs(*v):
+            return (ctypes.c_void_p * len(v))(*v)
+        assert lib.rg_pack_fields_f32(3, ptrs(p, p, p), None, None, 8, 2, p, None) == EINVAL           # stride < n_fields
+        assert lib.rg_pack_fields_f32(3, ptrs(p, p, p), None, None, 8, 3, p, None) == EINVAL           # stride 3
+        assert lib.rg_pack_fields_f32(1, ptrs(p), None, None, 8, 16, p, None) == EINVAL
+        assert lib.rg_pack_fields_f32(0, ptrs(p), None, None, 8, 1, p, None) == EUNSUP
+        assert lib.rg_pack_fields_f32(9, ptrs(*[p] * 9), None, None, 8, 8, p, None) == EUNSUP
+        assert lib.rg_pack_fields_f32(2, ptrs(p, None), None, None, 8, 2, p, None) == EINVAL and b"field 1 is null" in lib.rg_last_error()
+        assert lib.rg_pack_fields_f32(1, ptrs(p), None, None, 8, 1, p + 4, None) == EALIGN
+        assert lib.rg_pack_fields_f32(1, ptrs(p), None, None, -1, 1, p, None) == EINVAL
+        assert lib.rg_pack_fields_f32(1, ptrs(p), None, None, 8, 1, None, None) == EINVAL              # no output buffer
+        assert lib.rg_pack_fields_f32(2, ptrs(None, None), None, None, 0, 2, None, None) == _native.RG_OK   # nothing to pack
+
+        cells = _native.CellGrid(x0=0.0, y0=0.0, inv_cx=1.0, inv_cy=1.0, z_lo=0.0, z_hi=1.0, ncx=4, ncy=4, levels=5, level0=0)
+        args = (p, p, p, 10, 0.0, 1.0, cells, p)
+        assert lib.rg_geom_bin_levels_count(*args, 5, 250.0, 0.5, p, None) == EUNSUP
+        assert lib.rg_geom_bin_gates_levels_f32(*args, 5, 250.0, 0.5, 10, p, p, p, 1 << 20, None) == EUNSUP
+        assert lib.rg_geom_bin_levels_count(*args, 5, 250.0, -0.1, p, None) == EUNSUP
+        assert lib.rg_geom_bin_levels_count(p, p, p, -1, 0.0, 1.0, cells, p, 5, 250.0, 0.3, p, None) == EINVAL
+        assert lib.rg_geom_bin_gates_levels_f32(p, p, p, -1, 0.0, 1.0, cells, p, 5, 250.0, 0.3, 10, p, p, p, 1 << 20, None) == EINVAL
+        assert lib.rg_geom_bin_gates_levels_f32(*args, 5, 250.0, 0.3, -1, p, p, p, 1 << 20, None) == EINVAL
+        assert lib.rg_geom_bin_gates_f32(p, p, p, -1, 0.0, 1.0, cells, p, p, p, 1 << 20, None) == EINVAL
+        assert lib.rg_geom_bin_gates_f32(p, p, p, 10, 0.0, 1.0, cells, p + 4, p, p, 1 << 20, None) == EALIGN
+        need = lib.rg_geom_bin_workspace_bytes(10, 4, 4)
+        assert lib.rg_geom_bin_gates_f32(p, p, p, 10, 0.0, 1.0, cells, p, p, p, need - 1, None) == EWS
+
+        assert lib.rg_scan_workspace_bytes(-1) == EINVAL
+        need = lib.rg_scan_workspace_bytes(1000)
+        assert need >= 256 and need % 256 == 0
+        assert lib.rg_scan_counts_i64(p, 1000, p, p, need - 1, None) == EWS and b"workspace" in lib.rg_last_error()
+        assert lib.rg_scan_counts_i64(p, -1, p, p, need, None) == EINVAL
+        assert lib.rg_scan_counts_i64(p, 1000, None, p, need, None) == EINVAL
+
     def test_product_library_refuses_experiment_codes_and_has_no_knob_parameters(self):
         """Timing-only kernels (results wrong by construction) and tuning variants are not in the shipped library: their
         tile / variant codes are RG_EINVAL (validation only, nothing is launched), and the kernels have no template
