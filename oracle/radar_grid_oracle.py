@@ -338,7 +338,7 @@ def csr_apply_rowwise_order(indptr, gate_indices, weights, fields, masks, grid_s
                             weight_chains: int = 0) -> np.ndarray:
     """The masked weighted mean of :func:`csr_apply` (interpolate.py:69-104) with the float32 additions performed in
     exactly the order the row-wise kernel of ``rg_csr_compact_apply_packed_f32`` documents
-    (radar_processor_amd/csrc/rg_csr_compact.hip), so that the kernel can be checked BIT FOR BIT on small cases:
+    (radar_processor_amd/csrc/rg_csr_rowwise.hpp), so that the kernel can be checked BIT FOR BIT on small cases:
 
     * a grid line of nx rows is cut into ceil(nx / 64) balanced segments; a segment's pairs are numbered from 0 and
       grouped in records of three;

@@ -24,6 +24,9 @@ SOURCES = [
     ("rg_core.hip", []),
     ("rg_csr_apply.hip", []),
     ("rg_csr_compact.hip", []),
+    ("rg_csr_compact_build.hip", []),
+    ("rg_csr_pack.hip", []),
+    ("rg_csr_rowwise.hip", []),
     ("rg_csr_columns.hip", []),
     ("rg_products.hip", []),
     ("rg_geometry.hip", []),

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "radargrid_hip.h"
 
 namespace rg {
@@ -29,6 +31,26 @@ constexpr int kBlock = 256;      // 4 waves per workgroup
 // float32 slots per gate of the packed fields (rg_pack_fields_f32) for a pass of nf fields: the gather is one 4-, 8- or
 // 16-byte load, or two of 16
 constexpr int stride_for(int nf) { return nf == 1 ? 1 : nf == 2 ? 2 : nf <= 4 ? 4 : 8; }
+
+// ---- run-time value -> template argument: the launchers pass a generic lambda and read the constants off its parameters ----
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// n_fields (1 .. MAXF, checked by the caller) -> f(int_c<NF>, int_c<STRIDE>), STRIDE = stride_for(NF); only 1 .. MAXF are
+// instantiated
+template <int MAXF = RG_MAX_FIELDS, int NF = 1, class F>
+int dispatch_fields(int nf, F&& f) {
+  if constexpr (NF < MAXF) {
+    if (nf != NF) return dispatch_fields<MAXF, NF + 1>(nf, f);
+  }
+  return f(int_c<NF>{}, int_c<stride_for(NF)>{});
+}
+
+// width of the row pointers -> f(IndT{}), IndT = int64_t or int32_t
+template <class F>
+int dispatch_index(bool is_i64, F&& f) {
+  return is_i64 ? f(int64_t{}) : f(int32_t{});
+}
 
 __device__ __forceinline__ uint32_t f32_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
 __device__ __forceinline__ float bits_f32(uint32_t v) { return __builtin_bit_cast(float, v); }

@@ -1,7 +1,9 @@
-// Layout of the compact CSR copy shared by the K1c kernels (rg_csr_compact.hip: tile and row-wise kernels;
-// rg_csr_columns.hip: the column-persistent row-wise kernel): chunk grid, block -> chunk rotation, segments, buffer
-// resources, per-field-count tuning of the row-wise kernels.  Everything here has internal linkage on purpose (each
-// translation unit gets its own copy; nothing is exported).
+// Layout of the compact CSR copy shared by the K1c kernels (rg_csr_compact.hip: the tile kernels, and the description of the
+// layout at its head; rg_csr_rowwise.hpp: the row-wise kernel, with its grid mode in rg_csr_rowwise.hip and its column and planes
+// modes in rg_csr_columns.hip; rg_csr_pack.hip, rg_csr_compact_build.hip: what writes the copy): chunk grid, block -> chunk rotation, segments,
+// buffer resources, record codings, per-field-count tuning of the row-wise kernel, and the argument checks the entry points
+// over the packed records share.  Everything here has internal linkage on purpose (each translation unit gets its own copy;
+// nothing is exported) except the launcher declared at the end.
 #pragma once
 
 #include <type_traits>
@@ -19,8 +21,7 @@ __device__ rg_u32x4 rg_buffer_load_v4u32(__amdgpu_buffer_rsrc_t, int voffset, in
 // infinity included; any other product is the IEEE one.
 __device__ float rg_fmul_legacy(float, float) __asm("llvm.amdgcn.fmul.legacy");
 
-// Types that cross translation units (the launcher of the row-wise kernel's column mode is called from
-// rg_csr_columns.hip) live in a NAMED namespace: a function with a parameter of an anonymous-namespace type has no linkage.
+// Types that cross translation units (the launcher at the end of this file) live in a NAMED namespace: a function with a parameter of an anonymous-namespace type has no linkage.
 namespace rgl {
 
 // Where a chunk's wavefronts find their rows: the grid as planes x lines x rows (nz x ny x nx for a radar grid).
@@ -60,11 +61,38 @@ struct RowwisePlanes : RowwiseColumns {
   int n_sel = 0;
 };
 
+// ---- the arguments the three entry points over the packed records share: rg_csr_compact_apply_packed_f32, _columns_f32 and
+// _planes_f32 (their 17 leading ones, and what each passes on to its launcher) -- checked by check_stream_args ----
+struct StreamArgs {
+  const void* indptr;
+  bool is_i64;
+  const void* records;
+  const int64_t* rec_ptr;
+  int rec_order;
+  unsigned w_base;
+  const int64_t* dict_ptr;
+  const int32_t* dict;
+  long n_vox, n_pairs, line_len, lines_per_plane;
+  const float* packed;
+  int n_fields, stride;
+  long n_gates;
+  float fill;
+  float* out;
+  int window_cap;
+  int lanes_hint;          // 0 = from the segment's mean row length, a power of two up to 64, or 70 + records per lane and row
+  hipStream_t stream;
+  // where the entry points differ
+  int max_fields;          // 8 for rg_csr_compact_apply_packed_f32 (whose tile kernel refuses 5-8 itself); 4 for the other two
+  bool need_out;           // the grid is all rg_csr_compact_apply_packed_f32 produces; the other two may store planes only
+  bool need_packed;        // column / planes modes: packed fields present and 16-byte aligned even without a pair
+};
+
 }  // namespace rgl
 
 namespace {
 
 using rgl::ChunkGrid;
+using rgl::StreamArgs;
 using rgl::RowwiseColumns;
 using rgl::RowwisePlanes;
 using rg::f32x2;
@@ -211,8 +239,40 @@ bool make_chunk_grid(int64_t n_rows, int64_t line_len, int64_t lines_per_plane, 
   return true;
 }
 
+// Validates what `fn`, one of the three entry points over the packed records, shares with the other two, and builds the chunk
+// grid (left alone when n_vox == 0: nothing to launch).  RG_OK, or the status to return with the error text set.
+inline int check_stream_args(const char* fn, const StreamArgs& a, ChunkGrid* cg) {
+  RG_REQUIRE(a.rec_order == RG_REC_ORDER_SEGMENT || a.rec_order == RG_REC_ORDER_DISPATCH, RG_EINVAL,
+             "%s: rec_order=%d is neither RG_REC_ORDER_SEGMENT nor RG_REC_ORDER_DISPATCH", fn, a.rec_order);
+  RG_REQUIRE(a.n_fields >= 1 && a.n_fields <= a.max_fields, RG_EUNSUPPORTED, "%s: n_fields=%d not in 1..%d", fn, a.n_fields,
+             a.max_fields);
+  RG_REQUIRE(a.stride == stride_for(a.n_fields), RG_EINVAL, "%s: stride=%d, expected %d for %d fields", fn, a.stride,
+             stride_for(a.n_fields), a.n_fields);
+  RG_REQUIRE(a.indptr && a.dict_ptr && a.rec_ptr && (a.out || !a.need_out), RG_EINVAL, "%s: null indptr/dict_ptr/rec_ptr%s", fn,
+             a.need_out ? "/out" : "");
+  RG_REQUIRE(a.n_vox >= 0 && a.n_pairs >= 0, RG_EINVAL, "%s: negative size", fn);
+  RG_REQUIRE(a.n_pairs == 0 || (a.records && a.dict && a.packed && a.n_gates > 0), RG_EINVAL,
+             "%s: pairs present but records/dict/packed/n_gates missing", fn);
+  RG_REQUIRE(!a.need_packed || (a.packed && a.n_gates > 0), RG_EINVAL, "%s: packed fields missing", fn);
+  RG_REQUIRE(a.n_gates <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "%s: n_gates exceeds int32 gate indices", fn);
+  RG_REQUIRE(a.n_vox <= 0x3FFFFFFFFFL, RG_EUNSUPPORTED, "%s: n_vox too large for one launch", fn);
+  RG_REQUIRE(a.window_cap >= 0 && a.window_cap <= RG_COMPACT_MAX_WINDOW, RG_EINVAL, "%s: window_cap %d outside 0..%d", fn,
+             a.window_cap, RG_COMPACT_MAX_WINDOW);
+  RG_REQUIRE(rg::aligned16(a.records), RG_EALIGN, "%s: records must be 16-byte aligned", fn);
+  RG_REQUIRE(!a.need_packed || rg::aligned16(a.packed), RG_EALIGN, "%s: packed must be 16-byte aligned", fn);
+  RG_REQUIRE((a.w_base & 0x3FFFFFFu) == 0, RG_EINVAL,
+             "%s: w_base=0x%08x must have its low 26 bits clear (exponent a multiple of 8)", fn, a.w_base);
+  RG_REQUIRE(a.lanes_hint == 0 || (a.lanes_hint >= 1 && a.lanes_hint <= 64 && (a.lanes_hint & (a.lanes_hint - 1)) == 0) ||
+                 (a.lanes_hint > 70 && a.lanes_hint <= 99), RG_EINVAL,
+             "%s: the lane split must be 0, a power of two up to 64, or 71..99", fn);
+  if (a.n_vox == 0) return RG_OK;
+  RG_REQUIRE(make_chunk_grid(a.n_vox, a.line_len, a.lines_per_plane, cg), RG_EINVAL,
+             "%s: n_vox=%ld is not planes x lines_per_plane=%ld x line_len=%ld", fn, a.n_vox, a.lines_per_plane, a.line_len);
+  RG_REQUIRE(chunk_count(*cg) <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "%s: too many chunks for one launch", fn);
+  return RG_OK;
+}
 
-// ---- per-field-count configuration of the row-wise kernels (see rg_csr_compact.hip for what the knobs mean) ----
+// ---- per-field-count configuration of the row-wise kernels (see rg_csr_rowwise.hpp for what the knobs mean) ----
 template <int NF> struct RowwiseConfig;
 template <> struct RowwiseConfig<1> { static constexpr int kpre = 3, target = 4; static constexpr bool regs = false; };
 template <> struct RowwiseConfig<2> { static constexpr int kpre = 3, target = 4; static constexpr bool regs = false; };
@@ -268,12 +328,6 @@ __device__ __forceinline__ void column_min_step(float& acc, float v) {
 
 }  // namespace
 
-// defined in rg_csr_compact.hip (next to the kernel), called by rg_csr_columns.hip
-int rg_launch_rowwise_columns(int nf, bool i64, int window_cap, const void* indptr, const int64_t* dict_ptr, const int32_t* dict,
-                              const rgl::ChunkGrid& cg, long n_vox, const float* packed, long n_gates, float fill, float* out,
-                              hipStream_t s, const void* rec, const int64_t* rec_ptr, unsigned w_base, int rec_order,
-                              int lanes_hint, const rgl::RowwiseColumns& cols);
-int rg_launch_rowwise_planes(int nf, bool i64, int window_cap, const void* indptr, const int64_t* dict_ptr, const int32_t* dict,
-                             const rgl::ChunkGrid& cg, long n_vox, const float* packed, long n_gates, float fill, float* out,
-                             hipStream_t s, const void* rec, const int64_t* rec_ptr, unsigned w_base, int rec_order,
-                             int lanes_hint, const rgl::RowwisePlanes& cols);
+// Called across translation units: the tile kernel over the records, 1-4 fields (rg_csr_compact_apply_packed_f32 with tile = 384;
+// defined next to the kernel in rg_csr_compact.hip, called from rg_csr_rowwise.hip); `a` and `cg` have passed check_stream_args.
+int rg_launch_tile_packed(const rgl::StreamArgs& a, const rgl::ChunkGrid& cg);

@@ -225,54 +225,6 @@ int launch_dyn(const void* indptr, const int32_t* gidx, const float* wts, long n
   return rg::check_launch("rg_csr_apply_f32");
 }
 
-template <typename IndT>
-int dispatch(int nf, int variant, const void* indptr, const int32_t* gidx, const float* wts, long n_vox, long line_len,
-             const float* packed, long n_gates, float fill, float* out, hipStream_t s) {
-#define RG_KD(NF_, ST_, TILE_) \
-  launch_dyn<IndT, NF_, ST_, TILE_>(indptr, gidx, wts, n_vox, line_len, packed, n_gates, fill, out, s)
-  // `variant`: 0 = what ships.  128/256/384/512 select the pipeline tile explicitly (A/B timing, and the bit-identity
-  // tests of rg_csr_compact_apply_f32 with a non-default tile).
-  if (nf == 1) {
-    switch (variant) {
-      case 128: return RG_KD(1, 1, 128);     // pipeline tile (right answers; another order of the float32 adds)
-      case 256: return RG_KD(1, 1, 256);
-      case 512: return RG_KD(1, 1, 512);
-      default: return RG_KD(1, 1, 384);   // 384-pair tiles: same speed as 512 or slightly better, 72 VGPRs
-    }
-  }
-  switch (nf) {
-    case 2:
-      switch (variant) {
-        case 128: return RG_KD(2, 2, 128);
-        case 256: return RG_KD(2, 2, 256);
-        case 512: return RG_KD(2, 2, 512);
-        default: return RG_KD(2, 2, 384);
-      }
-    case 3:
-      switch (variant) {
-        case 128: return RG_KD(3, 4, 128);
-        case 192: return RG_KD(3, 4, 192);
-        case 256: return RG_KD(3, 4, 256);
-        case 320: return RG_KD(3, 4, 320);
-        // config 2 / bench grid, ms: 256 -> 2.48 / 17.5, 320 -> 2.37 / 16.9, 384 -> 2.39 / 17.1; 384 = 2 x 192 pairs is
-        // also what the packed stream of the compact kernel needs (same tile = same bits)
-        default: return RG_KD(3, 4, 384);
-      }
-    case 4:
-      switch (variant) {
-        case 128: return RG_KD(4, 4, 128);
-        case 256: return RG_KD(4, 4, 256);
-        case 320: return RG_KD(4, 4, 320);
-        default: return RG_KD(4, 4, 384);
-      }
-    case 5: return RG_KD(5, 8, 128);
-    case 6: return RG_KD(6, 8, 128);
-    case 7: return RG_KD(7, 8, 128);
-    default: return RG_KD(8, 8, 128);
-  }
-#undef RG_KD
-}
-
 using rg::stride_for;
 
 }  // namespace
@@ -303,11 +255,16 @@ extern "C" int rg_csr_apply_f32_ex(const void* indptr, int32_t indptr_is_i64, co
   RG_REQUIRE(n_vox % line_len == 0, RG_EINVAL, "rg_csr_apply_f32: n_vox=%ld is not a multiple of line_len=%ld",
              (long)n_vox, (long)line_len);
   hipStream_t s = (hipStream_t)stream;
-  if (indptr_is_i64)
-    return dispatch<int64_t>(n_fields, variant, indptr, gate_idx, weights, n_vox, line_len, packed, n_gates, fill_value,
-                             out, s);
-  return dispatch<int32_t>(n_fields, variant, indptr, gate_idx, weights, n_vox, line_len, packed, n_gates, fill_value, out,
-                           s);
+  // `variant`: 0 = what ships; a tile of rg_row_phase.hpp's table selects the pipeline tile explicitly (A/B timing, and the
+  // bit-identity tests of rg_csr_compact_apply_f32 with a non-default tile)
+  return rg::dispatch_index(indptr_is_i64 != 0, [&](auto ind) {
+    return rg::dispatch_fields(n_fields, [&](auto nf, auto st) {
+      return rg::dispatch_tile<decltype(nf)::value>(variant, [&](auto tile) {
+        return launch_dyn<decltype(ind), decltype(nf)::value, decltype(st)::value, decltype(tile)::value>(
+            indptr, gate_idx, weights, n_vox, line_len, packed, n_gates, fill_value, out, s);
+      });
+    });
+  });
 }
 
 extern "C" int rg_csr_apply_f32(const void* indptr, int32_t indptr_is_i64, const int32_t* gate_idx,

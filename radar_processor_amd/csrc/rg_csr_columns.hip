@@ -1,4 +1,4 @@
-// K1p  rg_csr_compact_apply_columns_f32: the row-wise kernel of rg_csr_compact.hip with workgroups that are PERSISTENT over a
+// K1p  rg_csr_compact_apply_columns_f32: the row-wise kernel of rg_csr_rowwise.hpp with workgroups that are PERSISTENT over a
 // COLUMN of chunks -- the same (line group, segment) patch through consecutive grid levels -- and an optional products
 // epilogue (COLMAX / first-argmax in registers, selected levels stored as planes) that removes the 3-D grid's round trip
 // through HBM.  radar_grid/interpolate.py:69-104 (the masked weighted mean), :137-140 (several fields, one pass);
@@ -8,8 +8,9 @@
 // back -- on this part writes mixed into a streaming read cost ten times their stand-alone price.
 //
 // The kernel is the COLUMN MODE of the row-wise kernel itself (csr_compact_rowwise_kernel<..., COLS = true> in
-// rg_csr_compact.hip): the same code from a chunk's row pointers to its row sums, one chunk after the other behind a barrier,
-// with 4-12 more VGPRs for the running maxima.  This file holds the entry point and the merge of level pieces.
+// rg_csr_rowwise.hpp): the same code from a chunk's row pointers to its row sums, one chunk after the other behind a barrier,
+// with 4-12 more VGPRs for the running maxima.  This file instantiates that mode and the planes mode, and holds their entry
+// points and the merge of level pieces.
 //
 // Measured (round 4, profiles/r04_columns_variants_*.json; ms per pass, bench grid / config 2, same process and arrays):
 // products only against row-wise kernel + separate COLMAX/argmax + CAPPI: one field 8.19 vs 8.07 / 1.16 vs 1.01, three
@@ -36,9 +37,26 @@
 //
 // Roofline: HBM.  Bytes per launch = the row-wise kernel's minus what is not stored: 16*R + 8*(S+1) + 4*D + 8*(C+1) +
 // ip*(V+1) + F*5*G + F*4*V [only if out] + F*4*Vxy*(n_keep [+ 2 if colmax]).
-#include "rg_compact_layout.hpp"
+#include "rg_csr_rowwise.hpp"
 
 namespace {
+
+// Column mode (Cols = RowwiseColumns) and planes mode (RowwisePlanes: the same launch with the wider epilogue) of the row-wise
+// kernel, 1-4 fields: one workgroup per column of chunks and level piece.
+template <typename Cols>
+int launch_rowwise_cols(const StreamArgs& a, const ChunkGrid& cg, const Cols& cols) {
+  constexpr bool PLANES = std::is_same_v<Cols, RowwisePlanes>;
+  constexpr int kRegsCols = -1;      // (four fields with the row sums in LDS: 108 instead of 111 VGPRs, the same 4 wavefronts)
+  return rg::dispatch_index(a.is_i64, [&](auto ind) {
+    return rg::dispatch_fields<4>(a.n_fields, [&](auto nf, auto) {
+      constexpr int NF = decltype(nf)::value;
+      constexpr long kStatic = RowwiseConfig<NF>::regs ? 16 : (long)kH * 64 * NF * 8;
+      return launch_rowwise<decltype(ind), NF, PLANES ? 2 : 1, kRegsCols>(
+          PLANES ? "rg_csr_compact_apply_planes_f32" : "rg_csr_compact_apply_columns_f32", a, cg, kStatic,
+          dim3(cols.n_cols * (unsigned)cols.pieces), 1, cols);
+    });
+  });
+}
 
 // (max, first arg) of a column from the partial results of its level pieces, merged in ascending level order: a later
 // piece wins only when strictly greater (rg_products.hip: merge<true> with b.idx > a.idx)
@@ -90,36 +108,14 @@ extern "C" int rg_csr_compact_apply_columns_f32(const void* indptr, int32_t indp
                                                 float* col_max, int32_t* col_arg, int32_t col_lo, int32_t col_hi,
                                                 int32_t window_cap, int32_t z_pieces, const int32_t* order, void* workspace,
                                                 int64_t workspace_bytes, int32_t lanes_hint, rg_stream_t stream) {
-  RG_REQUIRE(rec_order == RG_REC_ORDER_SEGMENT || rec_order == RG_REC_ORDER_DISPATCH, RG_EINVAL,
-             "rg_csr_compact_apply_columns_f32: rec_order=%d is neither RG_REC_ORDER_SEGMENT nor RG_REC_ORDER_DISPATCH", rec_order);
-  RG_REQUIRE(n_fields >= 1 && n_fields <= 4, RG_EUNSUPPORTED, "rg_csr_compact_apply_columns_f32: n_fields=%d not in 1..4",
-             n_fields);
-  RG_REQUIRE(stride == stride_for(n_fields), RG_EINVAL, "rg_csr_compact_apply_columns_f32: stride=%d, expected %d for %d fields",
-             stride, stride_for(n_fields), n_fields);
-  RG_REQUIRE(indptr && dict_ptr && rec_ptr, RG_EINVAL, "rg_csr_compact_apply_columns_f32: null indptr/dict_ptr/rec_ptr");
   RG_REQUIRE(out || level_planes || col_max, RG_EINVAL,
              "rg_csr_compact_apply_columns_f32: nothing to produce (out, level_planes and col_max are all null)");
-  RG_REQUIRE(n_vox >= 0 && n_pairs >= 0, RG_EINVAL, "rg_csr_compact_apply_columns_f32: negative size");
-  RG_REQUIRE(n_pairs == 0 || (records && dict && packed && n_gates > 0), RG_EINVAL,
-             "rg_csr_compact_apply_columns_f32: pairs present but records/dict/packed/n_gates missing");
-  RG_REQUIRE(packed && n_gates > 0, RG_EINVAL, "rg_csr_compact_apply_columns_f32: packed fields missing");
-  RG_REQUIRE(n_gates <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_columns_f32: n_gates exceeds int32 gate indices");
-  RG_REQUIRE(n_vox <= 0x3FFFFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_columns_f32: n_vox too large for one launch");
-  RG_REQUIRE(window_cap >= 0 && window_cap <= RG_COMPACT_MAX_WINDOW, RG_EINVAL,
-             "rg_csr_compact_apply_columns_f32: window_cap %d outside 0..%d", window_cap, RG_COMPACT_MAX_WINDOW);
-  RG_REQUIRE(rg::aligned16(records), RG_EALIGN, "rg_csr_compact_apply_columns_f32: records must be 16-byte aligned");
-  RG_REQUIRE(rg::aligned16(packed), RG_EALIGN, "rg_csr_compact_apply_columns_f32: packed must be 16-byte aligned");
-  RG_REQUIRE((w_base & 0x3FFFFFFu) == 0, RG_EINVAL,
-             "rg_csr_compact_apply_columns_f32: w_base=0x%08x must have its low 26 bits clear", w_base);
-  RG_REQUIRE(lanes_hint == 0 || (lanes_hint >= 1 && lanes_hint <= 64 && (lanes_hint & (lanes_hint - 1)) == 0) ||
-                 (lanes_hint > 70 && lanes_hint <= 99), RG_EINVAL,
-             "rg_csr_compact_apply_columns_f32: lanes_hint must be 0, a power of two up to 64, or 71..99");
-  if (n_vox == 0) return RG_OK;
+  const StreamArgs a{indptr, indptr_is_i64 != 0, records, rec_ptr, rec_order, w_base, dict_ptr, dict, n_vox, n_pairs, line_len,
+                     lines_per_plane, packed, n_fields, stride, n_gates, fill_value, out, window_cap, lanes_hint,
+                     (hipStream_t)stream, /*max_fields=*/4, /*need_out=*/false, /*need_packed=*/true};
   ChunkGrid cg;
-  RG_REQUIRE(make_chunk_grid(n_vox, line_len, lines_per_plane, &cg), RG_EINVAL,
-             "rg_csr_compact_apply_columns_f32: n_vox=%ld is not planes x lines_per_plane=%ld x line_len=%ld", (long)n_vox,
-             (long)lines_per_plane, (long)line_len);
-  RG_REQUIRE(chunk_count(cg) <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_columns_f32: too many chunks for one launch");
+  int st = check_stream_args("rg_csr_compact_apply_columns_f32", a, &cg);
+  if (st != RG_OK || n_vox == 0) return st;
   RG_REQUIRE(z_pieces >= 1 && z_pieces <= cg.n_planes, RG_EINVAL,
              "rg_csr_compact_apply_columns_f32: z_pieces=%d outside 1..planes=%ld", z_pieces, (long)cg.n_planes);
   RG_REQUIRE(!level_planes || (keep_lo >= 0 && n_keep >= 1 && keep_lo + (long)n_keep <= cg.n_planes), RG_EINVAL,
@@ -142,8 +138,7 @@ extern "C" int rg_csr_compact_apply_columns_f32(const void* indptr, int32_t indp
     part_val = static_cast<float*>(workspace);
     part_arg = reinterpret_cast<int32_t*>(part_val + (size_t)z_pieces * n_fields * n_xy);
   }
-  hipStream_t s = (hipStream_t)stream;
-  int st;
+  hipStream_t s = a.stream;
   {
     rgl::RowwiseColumns c;
     c.order = order;
@@ -157,8 +152,7 @@ extern "C" int rg_csr_compact_apply_columns_f32(const void* indptr, int32_t indp
     c.n_keep = level_planes ? n_keep : 0;
     c.col_lo = col_lo;
     c.col_hi = col_hi;
-    st = rg_launch_rowwise_columns(n_fields, indptr_is_i64 != 0, window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates,
-                                   fill_value, out, s, records, rec_ptr, w_base, rec_order, lanes_hint, c);
+    st = launch_rowwise_cols(a, cg, c);
   }
   if (st != RG_OK) return st;
   if (part_val) {
@@ -192,13 +186,6 @@ extern "C" int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indpt
                                                const int32_t* order, void* workspace, int64_t workspace_bytes,
                                                int32_t lanes_hint, rg_stream_t stream) {
   RG_REQUIRE(req, RG_EINVAL, "rg_csr_compact_apply_planes_f32: null request");
-  RG_REQUIRE(rec_order == RG_REC_ORDER_SEGMENT || rec_order == RG_REC_ORDER_DISPATCH, RG_EINVAL,
-             "rg_csr_compact_apply_planes_f32: rec_order=%d is neither RG_REC_ORDER_SEGMENT nor RG_REC_ORDER_DISPATCH", rec_order);
-  RG_REQUIRE(n_fields >= 1 && n_fields <= 4, RG_EUNSUPPORTED, "rg_csr_compact_apply_planes_f32: n_fields=%d not in 1..4",
-             n_fields);
-  RG_REQUIRE(stride == stride_for(n_fields), RG_EINVAL, "rg_csr_compact_apply_planes_f32: stride=%d, expected %d for %d fields",
-             stride, stride_for(n_fields), n_fields);
-  RG_REQUIRE(indptr && dict_ptr && rec_ptr, RG_EINVAL, "rg_csr_compact_apply_planes_f32: null indptr/dict_ptr/rec_ptr");
   RG_REQUIRE(req->n_sel >= 0 && req->n_sel <= RG_MAX_SEL_PLANES, RG_EINVAL,
              "rg_csr_compact_apply_planes_f32: n_sel=%d outside 0..%d", req->n_sel, RG_MAX_SEL_PLANES);
   for (int k = 0; k < req->n_sel; ++k)
@@ -207,31 +194,16 @@ extern "C" int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indpt
              req->n_sel);
   RG_REQUIRE(req->out || req->level_planes || req->col_max || req->col_min || req->col_mean || req->n_sel > 0, RG_EINVAL,
              "rg_csr_compact_apply_planes_f32: nothing to produce");
-  RG_REQUIRE(n_vox >= 0 && n_pairs >= 0, RG_EINVAL, "rg_csr_compact_apply_planes_f32: negative size");
-  RG_REQUIRE(n_pairs == 0 || (records && dict && packed && n_gates > 0), RG_EINVAL,
-             "rg_csr_compact_apply_planes_f32: pairs present but records/dict/packed/n_gates missing");
-  RG_REQUIRE(packed && n_gates > 0, RG_EINVAL, "rg_csr_compact_apply_planes_f32: packed fields missing");
-  RG_REQUIRE(n_gates <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_planes_f32: n_gates exceeds int32 gate indices");
-  RG_REQUIRE(n_vox <= 0x3FFFFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_planes_f32: n_vox too large for one launch");
-  RG_REQUIRE(window_cap >= 0 && window_cap <= RG_COMPACT_MAX_WINDOW, RG_EINVAL,
-             "rg_csr_compact_apply_planes_f32: window_cap %d outside 0..%d", window_cap, RG_COMPACT_MAX_WINDOW);
-  RG_REQUIRE(rg::aligned16(records), RG_EALIGN, "rg_csr_compact_apply_planes_f32: records must be 16-byte aligned");
-  RG_REQUIRE(rg::aligned16(packed), RG_EALIGN, "rg_csr_compact_apply_planes_f32: packed must be 16-byte aligned");
-  RG_REQUIRE((w_base & 0x3FFFFFFu) == 0, RG_EINVAL,
-             "rg_csr_compact_apply_planes_f32: w_base=0x%08x must have its low 26 bits clear", w_base);
-  RG_REQUIRE(lanes_hint == 0 || (lanes_hint >= 1 && lanes_hint <= 64 && (lanes_hint & (lanes_hint - 1)) == 0) ||
-                 (lanes_hint > 70 && lanes_hint <= 99), RG_EINVAL,
-             "rg_csr_compact_apply_planes_f32: lanes_hint must be 0, a power of two up to 64, or 71..99");
   RG_REQUIRE(!(req->col_mean && z_pieces != 1), RG_EINVAL,
              "rg_csr_compact_apply_planes_f32: col_mean needs z_pieces == 1 (the float32 running sum cannot be split), got %d",
              z_pieces);
   RG_REQUIRE(!req->col_arg || req->col_max, RG_EINVAL, "rg_csr_compact_apply_planes_f32: col_arg needs col_max");
-  if (n_vox == 0) return RG_OK;
+  const StreamArgs a{indptr, indptr_is_i64 != 0, records, rec_ptr, rec_order, w_base, dict_ptr, dict, n_vox, n_pairs, line_len,
+                     lines_per_plane, packed, n_fields, stride, n_gates, fill_value, req->out, window_cap, lanes_hint,
+                     (hipStream_t)stream, /*max_fields=*/4, /*need_out=*/false, /*need_packed=*/true};
   ChunkGrid cg;
-  RG_REQUIRE(make_chunk_grid(n_vox, line_len, lines_per_plane, &cg), RG_EINVAL,
-             "rg_csr_compact_apply_planes_f32: n_vox=%ld is not planes x lines_per_plane=%ld x line_len=%ld", (long)n_vox,
-             (long)lines_per_plane, (long)line_len);
-  RG_REQUIRE(chunk_count(cg) <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_compact_apply_planes_f32: too many chunks for one launch");
+  int st = check_stream_args("rg_csr_compact_apply_planes_f32", a, &cg);
+  if (st != RG_OK || n_vox == 0) return st;
   RG_REQUIRE(z_pieces >= 1 && z_pieces <= cg.n_planes, RG_EINVAL,
              "rg_csr_compact_apply_planes_f32: z_pieces=%d outside 1..planes=%ld", z_pieces, (long)cg.n_planes);
   RG_REQUIRE(req->n_sel == 0 || cg.n_planes < 0xFFFF, RG_EUNSUPPORTED,
@@ -255,8 +227,7 @@ extern "C" int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indpt
   float* part_val = split_max ? static_cast<float*>(workspace) : nullptr;
   int32_t* part_arg = split_max ? reinterpret_cast<int32_t*>(part_val + n_part) : nullptr;
   float* part_min = split_min ? static_cast<float*>(workspace) + (split_max ? 2 * n_part : 0) : nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  int st;
+  hipStream_t s = a.stream;
   {
     rgl::RowwisePlanes c;
     c.order = order;
@@ -275,8 +246,7 @@ extern "C" int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indpt
     for (int k = 0; k < RG_MAX_SEL_PLANES; ++k) c.sel[k] = k < req->n_sel ? req->sel_levels[k] : nullptr;
     c.samples = req->n_sel ? req->sel_samples : nullptr;
     c.n_sel = req->n_sel;
-    st = rg_launch_rowwise_planes(n_fields, indptr_is_i64 != 0, window_cap, indptr, dict_ptr, dict, cg, n_vox, packed, n_gates,
-                                  fill_value, req->out, s, records, rec_ptr, w_base, rec_order, lanes_hint, c);
+    st = launch_rowwise_cols(a, cg, c);
   }
   if (st != RG_OK) return st;
   const long n = (long)n_fields * n_xy;

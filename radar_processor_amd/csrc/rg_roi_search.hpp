@@ -408,24 +408,6 @@ inline SearchArgs make_args(const rg_gate4* sorted, const int32_t* cell_start, c
   return a;
 }
 
-template <int V>
-using int_c = std::integral_constant<int, V>;
-
-// n_fields (1 .. RG_MAX_FIELDS, checked by the caller) -> f(int_c<NF>, int_c<STRIDE>), STRIDE = stride_for(NF)
-template <class F>
-int dispatch_fields(int nf, F&& f) {
-  switch (nf) {
-    case 1: return f(int_c<1>{}, int_c<stride_for(1)>{});
-    case 2: return f(int_c<2>{}, int_c<stride_for(2)>{});
-    case 3: return f(int_c<3>{}, int_c<stride_for(3)>{});
-    case 4: return f(int_c<4>{}, int_c<stride_for(4)>{});
-    case 5: return f(int_c<5>{}, int_c<stride_for(5)>{});
-    case 6: return f(int_c<6>{}, int_c<stride_for(6)>{});
-    case 7: return f(int_c<7>{}, int_c<stride_for(7)>{});
-    default: return f(int_c<8>{}, int_c<stride_for(8)>{});
-  }
-}
-
 // weighting (checked by the caller) -> f(int_c<W>); the closest-gate mode only where the entry point has one
 template <bool WITH_CLOSEST = false, class F>
 int dispatch_weighting(int weighting, F&& f) {

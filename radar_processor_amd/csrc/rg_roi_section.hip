@@ -53,6 +53,7 @@
 namespace {
 
 using namespace rg::roi;
+using rg::dispatch_fields;
 
 constexpr int kRing = 128;   // survivor queue per wave (power of two): <= 63 waiting + 64 new records
 constexpr int kPts = 4;      // points per block

@@ -69,6 +69,33 @@ __device__ __forceinline__ void butterfly(float (&v)[N], int nsub) {
 // padding slot of a 3-field entry, otherwise in its own array behind the values)
 constexpr int tile_floats(int nf, int stride) { return nf == 1 ? 2 : nf == 3 ? 4 : stride + 1; }
 
+// Pairs per tile, per field count: the tiles a caller may ask for, and the default that any other value (0 included) selects.
+// ONE table for rg_csr_apply_f32 and the compact tile kernels: the same tile is the same partial sums, the same bits.
+//   fields   accepted            default
+//   1, 2     128 256 512         384     (384: same speed as 512 or slightly better, 72 VGPRs)
+//   3        128 192 256 320     384     (config 2 / bench grid, ms: 256 -> 2.48 / 17.5, 320 -> 2.37 / 16.9, 384 -> 2.39 / 17.1;
+//   4        128 256 320         384      384 = 2 x 192 pairs is also what the packed records of the compact kernel need)
+//   5-8      -                   128
+// A tile other than the default is for A/B timing and the bit-identity tests: right answers, another order of the float32 adds.
+template <int NF, class F>
+int dispatch_tile(int tile, F&& f) {
+  if constexpr (NF >= 5) {
+    return f(int_c<128>{});
+  } else {
+    if (tile == 128) return f(int_c<128>{});
+    if (tile == 256) return f(int_c<256>{});
+    if constexpr (NF <= 2) {
+      if (tile == 512) return f(int_c<512>{});
+    } else {
+      if (tile == 320) return f(int_c<320>{});
+      if constexpr (NF == 3) {
+        if (tile == 192) return f(int_c<192>{});
+      }
+    }
+    return f(int_c<384>{});
+  }
+}
+
 // ---- product side: one pair -> its LDS entry --------------------------------------------------------------------
 // One field: the masked products (w*v, w).  Several fields: the pair's RAW packed slots (EXCLUDED sentinel = masked)
 // and its weight -- 12 / 16 / 20 / 36 bytes instead of the 16 / 32 / 32 / 64 of F (w*v, w) pairs.  LDS stores are the

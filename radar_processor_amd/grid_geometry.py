@@ -156,7 +156,7 @@ class CompactCSR:
         """Slot (index into ``rec_ptr``) of segment ``sx`` of grid line ``line`` (int64 tensors, lines counted through all
         planes).  ``RG_REC_ORDER_SEGMENT``: the line-major segment number.  ``RG_REC_ORDER_DISPATCH``: ``block * H + w``
         for the wavefront ``w`` of the workgroup ``block`` that reads the segment -- the inverse of the kernels'
-        block -> chunk rotation (``block_chunk`` in csrc/rg_csr_compact.hip, 32-bit unsigned arithmetic).  ``plane0``: the
+        block -> chunk rotation (``block_chunk`` in csrc/rg_compact_layout.hpp, 32-bit unsigned arithmetic).  ``plane0``: the
         grid is a slab of whole planes of a larger one and this is its first plane there -- lines and slots stay the slab's
         own, the rotation counts the line groups in front of it."""
         nz, ny, nx = (int(v) for v in grid_shape)

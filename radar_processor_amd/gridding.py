@@ -161,11 +161,8 @@ class CsrGridder:
         nz, ny, nx = self.grid_shape
         if self.compact is not None and self.packed_stream and (self.tile in (0, 384) or self.tile >= 2000
                                                                 or csr.weights is None):
-            c = self.compact
             _native.check(self.lib.rg_csr_compact_apply_packed_f32(
-                _native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(c.rec), _native.ptr(c.rec_ptr), c.rec_order, c.w_base,
-                _native.ptr(c.dict_ptr), _native.ptr(c.dict), self.n_vox, csr.n_pairs, nx, ny, _native.ptr(self.packed),
-                self.n_fields, self.stride, self.n_gates, float(np.float32(fill_value)), _native.ptr(out), self.window,
+                *self._stream_args(fill_value), _native.ptr(out), self.window,
                 self.tile if (self.tile == 384 or self.tile >= 2000) else 0, _native.stream_ptr()),
                 "rg_csr_compact_apply_packed_f32")
             return
@@ -182,6 +179,22 @@ class CsrGridder:
             self.n_vox, csr.n_pairs, nx, _native.ptr(self.packed), self.n_fields, self.stride, self.n_gates,
             float(np.float32(fill_value)), _native.ptr(out), self.tile if self.tile in _PIPELINE_TILES else 0,
             _native.stream_ptr()), "rg_csr_apply_f32")
+
+    def _stream_args(self, fill_value):
+        """The 17 leading arguments ``rg_csr_compact_apply_packed_f32``, ``_columns_f32`` and ``_planes_f32`` share."""
+        csr, c = self.csr, self.compact
+        nz, ny, nx = self.grid_shape
+        return (_native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(c.rec), _native.ptr(c.rec_ptr), c.rec_order, c.w_base,
+                _native.ptr(c.dict_ptr), _native.ptr(c.dict), self.n_vox, csr.n_pairs, nx, ny, _native.ptr(self.packed),
+                self.n_fields, self.stride, self.n_gates, float(np.float32(fill_value)))
+
+    def _columns_workspace(self, nbytes: int):
+        """The grow-only device workspace of the column and planes modes (partial planes of the level pieces)."""
+        torch = _native.torch_mod()
+        ws = getattr(self, "_columns_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._columns_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        return ws
 
     # ---- column mode of the row-wise kernel (rg_csr_compact_apply_columns_f32) ----------------------------------------
     @property
@@ -228,10 +241,8 @@ class CsrGridder:
         row-wise kernel, or is ``None`` when only 2-D products are wanted -- ``level_planes`` ``[F, n_keep, ny, nx]``
         (planes ``keep_lo ..`` of every grid), ``col_max`` / ``col_arg`` ``[F, ny, nx]`` (``column_argmax`` over the level
         window ``col_window = (lo, hi)``, default all levels)."""
-        torch = _native.torch_mod()
         if not self.has_columns_kernel:
             raise _native.NativeError("the column mode needs the packed records (1-4 fields, codable weights)")
-        csr, c = self.csr, self.compact
         nz, ny, nx = self.grid_shape
         n_keep = 0 if level_planes is None else int(level_planes.shape[1])
         lo, hi = (0, nz - 1) if col_window is None else (int(col_window[0]), int(col_window[1]))
@@ -240,16 +251,10 @@ class CsrGridder:
             order = None
         ws = None
         if col_max is not None and pieces > 1:
-            nbytes = int(self.lib.rg_csr_columns_workspace_bytes(ny, nx, self.n_fields, pieces))
-            ws = getattr(self, "_columns_ws", None)
-            if ws is None or ws.numel() < nbytes:
-                ws = self._columns_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        window = self.window
+            ws = self._columns_workspace(int(self.lib.rg_csr_columns_workspace_bytes(ny, nx, self.n_fields, pieces)))
         _native.check(self.lib.rg_csr_compact_apply_columns_f32(
-            _native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(c.rec), _native.ptr(c.rec_ptr), c.rec_order, c.w_base,
-            _native.ptr(c.dict_ptr), _native.ptr(c.dict), self.n_vox, csr.n_pairs, nx, ny, _native.ptr(self.packed),
-            self.n_fields, self.stride, self.n_gates, float(np.float32(fill_value)), _native.ptr(out),
-            _native.ptr(level_planes), int(keep_lo), n_keep, _native.ptr(col_max), _native.ptr(col_arg), lo, hi, window,
+            *self._stream_args(fill_value), _native.ptr(out),
+            _native.ptr(level_planes), int(keep_lo), n_keep, _native.ptr(col_max), _native.ptr(col_arg), lo, hi, self.window,
             pieces, _native.ptr(order), _native.ptr(ws), 0 if ws is None else int(ws.numel()), int(lanes_hint),
             _native.stream_ptr()), "rg_csr_compact_apply_columns_f32")
 
@@ -272,10 +277,8 @@ class CsrGridder:
         (``sel_levels``: int32 ``[ny, nx]`` tensors from ``grid_products.ppi_plan``) whose levels land in ``sel_samples``
         ``[F, n_sel, 2, ny, nx]`` for ``grid_products.ppi_finish``.  ``col_mean`` takes one level piece (its float32 running
         sum cannot be split): ``z_pieces`` is then 1."""
-        torch = _native.torch_mod()
         if not self.has_columns_kernel:
             raise _native.NativeError("the planes mode needs the packed records (1-4 fields, codable weights)")
-        csr, c = self.csr, self.compact
         nz, ny, nx = self.grid_shape
         n_sel = len(sel_levels)
         if n_sel > _native.RG_MAX_SEL_PLANES:
@@ -286,11 +289,8 @@ class CsrGridder:
             order = None
         ws = None
         if (col_max is not None or col_min is not None) and pieces > 1:
-            nbytes = int(self.lib.rg_csr_planes_workspace_bytes(ny, nx, self.n_fields, pieces, int(col_max is not None),
-                                                                int(col_min is not None)))
-            ws = getattr(self, "_columns_ws", None)
-            if ws is None or ws.numel() < nbytes:
-                ws = self._columns_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+            ws = self._columns_workspace(int(self.lib.rg_csr_planes_workspace_bytes(
+                ny, nx, self.n_fields, pieces, int(col_max is not None), int(col_min is not None))))
         req = _native.PlaneRequest(out=_native.ptr(out), level_planes=_native.ptr(level_planes), keep_lo=int(keep_lo),
                                    n_keep=0 if level_planes is None else int(level_planes.shape[1]),
                                    col_max=_native.ptr(col_max), col_arg=_native.ptr(col_arg), col_min=_native.ptr(col_min),
@@ -299,9 +299,7 @@ class CsrGridder:
         for k, sel in enumerate(sel_levels):
             req.sel_levels[k] = _native.ptr(sel)
         _native.check(self.lib.rg_csr_compact_apply_planes_f32(
-            _native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(c.rec), _native.ptr(c.rec_ptr), c.rec_order, c.w_base,
-            _native.ptr(c.dict_ptr), _native.ptr(c.dict), self.n_vox, csr.n_pairs, nx, ny, _native.ptr(self.packed),
-            self.n_fields, self.stride, self.n_gates, float(np.float32(fill_value)), ctypes.byref(req), self.window, pieces,
+            *self._stream_args(fill_value), ctypes.byref(req), self.window, pieces,
             _native.ptr(order), _native.ptr(ws), 0 if ws is None else int(ws.numel()), int(lanes_hint), _native.stream_ptr()),
             "rg_csr_compact_apply_planes_f32")
 

@@ -614,7 +614,7 @@ class TestBenchLauncher:
 
 class TestCompactLayoutHostLogic:
     """Chunk / segment arithmetic of the compact CSR copy (grid_geometry.CompactCSR) -- the host side must cut lines and
-    number chunks exactly as csrc/rg_csr_compact.hip does (checked against rg_csr_compact_chunks, no GPU needed)."""
+    number chunks exactly as csrc/rg_compact_layout.hpp does (checked against rg_csr_compact_chunks, no GPU needed)."""
 
     def test_segments_are_balanced_and_cover_the_line(self):
         from radar_processor_amd.grid_geometry import CompactCSR
@@ -645,7 +645,7 @@ class TestCompactLayoutHostLogic:
 
     def test_dispatch_order_slots_invert_the_block_rotation(self):
         """RG_REC_ORDER_DISPATCH: slot = block * H + wavefront for the block -> chunk rotation of the apply kernels
-        (block_chunk in csrc/rg_csr_compact.hip), restated here in plain Python; every segment gets exactly one slot,
+        (block_chunk in csrc/rg_compact_layout.hpp), restated here in plain Python; every segment gets exactly one slot,
         the slots of one workgroup are neighbours, and record_pointers lays the records out in slot order."""
         import torch
         from radar_processor_amd.grid_geometry import CompactCSR
