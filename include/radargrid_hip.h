@@ -40,7 +40,7 @@ extern "C" {
  * (no signature changed: a 102 library answers RG_EUNSUPPORTED for 5-8); 104 rg_cellgrid.levels + the per-level gate lists
  * (rg_geom_bin_levels_count / rg_geom_bin_gates_levels_f32); still 104: the packed records' two codings -- no signature
  * changed, rg_csr_compact_pack_dense was ADDED (a library without it fails to bind by name) and rg_csr_compact_pack refuses work; the
- * mosaic combine rules -- rg_roi_grid_mosaic_combine_f32 and rg_roi_section_mosaic_combine_f32 were ADDED, no signature changed. */
+ * mosaic combine rules -- rg_roi_grid_mosaic_combine_f32 and rg_roi_section_mosaic_combine_f32 were ADDED, no signature changed; the column profile -- rg_column_profile_f32 was ADDED. */
 #define RG_VERSION 104
 #define RG_MAX_FIELDS 8
 
@@ -149,6 +149,44 @@ typedef enum rg_column_op { RG_COL_MAX = 0, RG_COL_MIN = 1, RG_COL_MEAN = 2 } rg
 
 int rg_column_reduce_f32(const float* grid, int32_t nz, int64_t n_xy, int32_t z_lo, int32_t z_hi, int32_t op,
                          float* out, int32_t* out_arg, rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K5  column profile: echo-top and echo-base heights at up to RG_MAX_PROFILE_THRESHOLDS thresholds and the vertically
+ * integrated liquid (VIL) of every column, in one bottom-to-top pass over a stored grid.  The reference has none of them:
+ * the contract is build-defined (as out_arg above) and stated here; tests/column_profile_oracle.py restates it in float64
+ * NumPy.
+ *   grid         any [nz][n_xy] stack of float32 planes: n_xy = ny * nx of a lattice grid, or the (nz, 1, n_points) output
+ *                of the section entry points;
+ *   z_levels     float64 [nz], DEVICE: the height of every level, strictly increasing (the caller checks);
+ *   thresholds_host / n_thresholds   0 .. RG_MAX_PROFILE_THRESHOLDS finite thresholds, read on the host and passed by value;
+ *   out_top / out_base   float32 [n_thresholds][n_xy] or NULL;  out_vil  float32 [n_xy] or NULL.
+ * RG_EINVAL: a null grid or z_levels; all three outputs null; n_thresholds outside 0 .. RG_MAX_PROFILE_THRESHOLDS;
+ * n_thresholds == 0 with an out_top or out_base; a non-finite threshold or vil_max_dbz; a window with z_lo < 0, z_hi >= nz
+ * or z_lo > z_hi.  n_xy == 0 returns RG_OK.  A launch without VIL reads and writes 16 bytes per lane when n_xy % 4 == 0 and
+ * every pointer is 16-byte aligned; otherwise, and with VIL, a lane owns one column -- the same bits either way.
+ *
+ * The contract, for one column g[] and the levels z_lo .. z_hi only (a level outside the window is never read and never
+ * interpolated against); z[] = z_levels, every operation an IEEE float64 operation on the float32 values, unfused:
+ *   Echo top at T    k = the highest level of the window with (double)g[k] >= T (a NaN never is); none: NaN.  When
+ *                    linear != 0, k < z_hi and g[k] and g[k+1] are both finite:
+ *                        z[k] + ((g[k] - T) / (g[k] - g[k+1])) * (z[k+1] - z[k])
+ *                    in this association, rounded to float32 once.  In every other case -- k the top of the window, a NaN
+ *                    or infinite neighbour, an infinite g[k], linear == 0 -- the result is (float)z[k].
+ *   Echo base at T   the mirror image: k = the lowest level with g[k] >= T, the neighbour is k-1 (k > z_lo, both finite):
+ *                        z[k] - ((g[k] - T) / (g[k] - g[k-1])) * (z[k] - z[k-1])
+ *   VIL (Greene & Clark)   q[k] = 0 where g[k] is NaN, else 10^(min(g[k], vil_max_dbz) / 10);
+ *                        VIL = 3.44e-6 * sum_{k = z_lo}^{z_hi - 1} ((q[k] + q[k+1]) / 2)^(4/7) * (z[k+1] - z[k])
+ *                    the sum in level order from 0.0, rounded to float32 once; NaN where no level of the window is
+ *                    non-NaN, 0.0 for a one-level window that holds a value.  Metres and mm^6 m^-3 in, kg m^-2 out.
+ *                    (10^x is the device's float64 exp10, x^(4/7) its exp2(4/7 * log2 x): ~1e-14 relative, so a plane
+ *                    agrees with a correctly rounded evaluation to one float32 ulp.)
+ * Thresholds are independent of each other: the plane of T is the same bits whether T is asked for alone or with others,
+ * on the vector and on the one-column path.
+ * ------------------------------------------------------------------------------------------------- */
+#define RG_MAX_PROFILE_THRESHOLDS 4
+int rg_column_profile_f32(const float* grid, int32_t nz, int64_t n_xy, int32_t z_lo, int32_t z_hi, const double* z_levels,
+                          const double* thresholds_host, int32_t n_thresholds, int32_t linear, float* out_top,
+                          float* out_base, double vil_max_dbz, float* out_vil, rg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * a10  K4 CAPPI lerp: radar_grid/products.py:406-412.  out = fl32(fl32(w_lo*lo) + fl32(w_hi*hi)), the

@@ -17,9 +17,9 @@ from .gate_filters import GateFilter, GridFilter, create_mask_from_filter, devic
 from .geometry_builder import RoiSearch, compute_grid_geometry
 from .grid_geometry import (DeviceCSR, GridGeometry, load_device_layout, load_geometry, save_device_layout, save_geometry)
 from .grid_products import (EARTH_RADIUS, EFFECTIVE_RADIUS_FACTOR, column_argmax, column_max, column_mean,
-                            column_min, compute_beam_height, compute_beam_height_flat, compute_beam_height_simple,
-                            constant_altitude_ppi, constant_elevation_ppi, get_beam_height_difference,
-                            get_elevation_from_z_level)
+                            column_min, column_profile, compute_beam_height, compute_beam_height_flat,
+                            compute_beam_height_simple, constant_altitude_ppi, constant_elevation_ppi, echo_base, echo_top,
+                            get_beam_height_difference, get_elevation_from_z_level, vertically_integrated_liquid)
 from .gridding import PlaneProducts, apply_geometry, apply_geometry_multi, grid_fields_device, grid_products_device
 from .roi_grid import roi_grid_fields_device
 from .mosaic import (MOSAIC_COMBINES, NO_RADAR, MosaicSearch, apply_mosaic, apply_mosaic_multi, compute_mosaic_geometry,
@@ -55,6 +55,7 @@ __all__ = [
     "mosaic_section_points", "path_reach", "mosaic_section_fields_device", "compute_mosaic_section_geometry",
     "mosaic_vertical_section",
     "section_path", "section_rectangle", "section_fields_device", "compute_section_geometry", "vertical_section",
+    "column_profile", "echo_top", "echo_base", "vertically_integrated_liquid",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

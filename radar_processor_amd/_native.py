@@ -28,6 +28,7 @@ GATE_OPS = {"below": 0, "above": 1, "between": 2, "outside": 3, "equal": 4, "inv
 COLUMN_OPS = {"max": 0, "min": 1, "mean": 2}
 WEIGHTINGS = {"barnes2": 0, "cressman": 1, "nearest": 2, "closest": 3}
 COMBINES = {"mean": 0, "max": 1, "nearest_radar": 2}     # rg_combine: how a mosaic launch combines its radars
+RG_MAX_PROFILE_THRESHOLDS = 4   # thresholds one rg_column_profile_f32 launch takes
 RG_MAX_PLANE_TESTS = 12
 RG_TEST_LO, RG_TEST_HI, RG_TEST_LO_INCLUSIVE, RG_TEST_NONFINITE = 1, 2, 4, 8
 RG_MINMAX_WORKSPACE_BYTES = 32768
@@ -99,6 +100,8 @@ SIGNATURES = {
                                       c_int32, c_int32, c_int64, c_float, c_void_p, c_int32, c_void_p]),
     "rg_column_reduce_f32": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                        c_void_p]),
+    "rg_column_profile_f32": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, POINTER(c_double), c_int32,
+                                        c_int32, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "rg_cappi_lerp_f32": (c_int32, [c_void_p, c_int64, c_int32, c_float, c_float, c_void_p, c_void_p]),
     "rg_elevation_ppi_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_double,
                                        c_double, c_double, c_double, c_double, c_double, c_double, c_int32, c_int32,

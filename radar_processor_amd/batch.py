@@ -198,17 +198,24 @@ class VolumeBatch:
         are neither written nor read back (``gridding.grid_products_device``).  ``volumes`` is indexed by the GLOBAL volume number; only this
         rank's entries (``shard_indices``) are touched, the others may be ``None``.  ``events``: optional list that
         receives one ``(start, end)`` pair of stream events per gridding pass (mask fold + gridding kernel), for
-        callers that time the kernel itself (``bench.py``)."""
+        callers that time the kernel itself (``bench.py``).
+
+        A ``PlaneProducts`` that includes a column profile product (``echo_top`` / ``echo_base`` / ``vil``) never takes the
+        fused launch: the epilogues do not compute those planes, so on a CSR geometry every group is gridded, then reduced
+        (``grid_products_device`` decides), as the CSR-free path always does."""
         import torch
-        from .gridding import PlaneProducts, grid_fields_device, grid_products_device, reduce_planes
+        from .gridding import PlaneProducts, grid_fields_device, grid_products_device, profile_planes, reduce_planes
         from .roi_grid import roi_grid_fields_device
         plane_spec = products if isinstance(products, PlaneProducts) else None
         if plane_spec is not None and self.fused:      # the CSR-free gridder has no epilogue: reduce its grids as usual
             from . import grid_products as gp
             geom_like = self.geometry
+            levels = {}
 
             def products(g, _spec=plane_spec):         # noqa: F811 -- the reducer form of the same request
                 recs = []
+                if _spec.profile and "zl" not in levels:       # the level heights: one upload per grid_shard call
+                    levels["zl"] = gp.profile_levels_device(geom_like, int(g.shape[1]), g.device)
                 for k in range(g.shape[0]):
                     rec = {}
                     lo, hi = gp._level_window(int(g.shape[1]), *_spec.window, geom_like)
@@ -224,7 +231,7 @@ class VolumeBatch:
                                         for alt in _spec.cappi}
                     if "ppi" in rec:
                         rec["ppi"] = rec.pop("ppi")                             # (key order of grid_products_device)
-                    recs.append(rec)
+                    recs.append(profile_planes(_spec, g[k], geom_like, lo, hi, rec, levels.get("zl")))   # echo top / base, VIL
                 return recs
             plane_spec = None
         mine = shard_indices(len(volumes), rank, world_size)

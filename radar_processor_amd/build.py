@@ -29,6 +29,7 @@ SOURCES = [
     ("rg_csr_rowwise.hip", []),
     ("rg_csr_columns.hip", []),
     ("rg_products.hip", []),
+    ("rg_column_profile.hip", []),
     ("rg_geometry.hip", []),
     ("rg_roi_grid.hip", []),
     ("rg_roi_section.hip", []),

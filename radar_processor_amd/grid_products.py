@@ -1,6 +1,7 @@
 """2-D products collapsed from a 3-D grid -- mirror of ``radar_grid/products.py``:
 ``constant_altitude_ppi`` (CAPPI, :317-415), ``column_max`` / ``column_min`` / ``column_mean`` (:420-580) and,
-new in this build, ``column_argmax``.
+new in this build, ``column_argmax`` and the column profile products ``echo_top`` / ``echo_base`` /
+``vertically_integrated_liquid`` (``column_profile``: all of them in one pass over the grid, ``rg_column_profile_f32``).
 
 The scalar control flow (level search, altitude -> index conversion, error handling) stays on the host exactly
 as in the reference; the per-pixel arithmetic runs in ``rg_cappi_lerp_f32`` / ``rg_column_reduce_f32``
@@ -9,8 +10,9 @@ tensors (result stays in HBM).
 """
 from __future__ import annotations
 
+import ctypes
 import logging
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -320,3 +322,164 @@ def column_argmax(grid, z_min_idx: Optional[int] = None, z_max_idx: Optional[int
     attains it, ``-1`` where the column is all NaN.  Not in the reference: ``np.nanargmax``
     semantics on the same 3-D grid define the contract."""
     return _column("max", grid, z_min_idx, z_max_idx, z_min_alt, z_max_alt, geometry, want_arg=True)
+
+
+# --------------------------------------------------------------------------------------------------
+# column profile: echo top / echo base / VIL (csrc/rg_column_profile.hip; not in the reference -- the contract is stated in
+# include/radargrid_hip.h and restated in float64 NumPy by tests/column_profile_oracle.py)
+# --------------------------------------------------------------------------------------------------
+def _thresholds(values, what: str) -> tuple:
+    """A threshold or a sequence of them as distinct finite floats, in the order given."""
+    values = (values,) if np.isscalar(values) else tuple(values)
+    out = tuple(dict.fromkeys(float(v) for v in values))
+    for v in out:
+        if not np.isfinite(v):
+            raise ValueError(f"{what} threshold must be finite, got {v}")
+    return out
+
+
+def check_profile_request(echo_top=(), echo_base=(), vil=False, max_dbz=56.0, interpolation="linear"):
+    """The argument checks of a column-profile request, none of which needs the device; returns the distinct thresholds
+    ``(tops, bases)``.  Whether anything has to be asked for is the caller's business (``column_profile`` insists,
+    ``PlaneProducts`` does not)."""
+    if interpolation not in ("linear", "nearest"):
+        raise ValueError(f"Unknown interpolation method: {interpolation}")
+    tops, bases = _thresholds(echo_top, "echo_top"), _thresholds(echo_base, "echo_base")
+    if not np.isfinite(float(max_dbz)):
+        raise ValueError(f"max_dbz must be finite, got {max_dbz}")
+    return tops, bases
+
+
+def profile_levels(geometry, nz: int) -> np.ndarray:
+    """The float64 height of every level, ``GridGeometry.z_levels()`` for anything with ``grid_limits``; strictly
+    increasing or ``ValueError`` (the kernel interpolates between neighbours)."""
+    z_min, z_max = geometry.grid_limits[0]
+    levels = np.linspace(z_min, z_max, nz)
+    if not np.all(np.isfinite(levels)) or (nz > 1 and not np.all(np.diff(levels) > 0)):
+        raise ValueError(f"the grid's levels [{z_min}, {z_max}] are not strictly increasing")
+    return levels
+
+
+def profile_levels_device(geometry, nz: int, device):
+    """``profile_levels`` as a float64 tensor on ``device``: what ``_profile_planes`` reads.  A caller that reduces several
+    grids of one geometry uploads it once and hands it down."""
+    torch = _native.torch_mod()
+    return torch.from_numpy(profile_levels(geometry, nz)).to(device)
+
+
+def _profile_planes(g, levels, lo: int, hi: int, tops, bases, vil: bool, max_dbz: float, interpolation: str) -> dict:
+    """The launches of one device grid ``[nz, ny, nx]``: the distinct thresholds of ``tops`` and ``bases`` merged into one
+    list, ``RG_MAX_PROFILE_THRESHOLDS`` per launch, VIL with the first.  ``levels``: the float64 level heights, a NumPy
+    array or a tensor already on the grid's device (``profile_levels_device``).  Returns device planes under the keys
+    asked for.
+
+    A launch produces the top plane of EVERY threshold it carries when any of them is wanted as a top, and likewise the
+    base planes: up to four distinct thresholds are one launch and one read of the grid whatever they are wanted for, at
+    the price of planes that are computed and dropped when the top and base lists differ (``echo_top=(18, 30, 45)`` with
+    ``echo_base=(18,)`` stores four base planes and keeps one: 16 MB each against the 640 MB read on the bench grid).  The
+    list is ordered thresholds wanted as both first, then top only, then base only, so that with more than four the
+    further launches tend to need one kind."""
+    torch = _native.torch_mod()
+    lib = _native.load_library()
+    nz, ny, nx = (int(s) for s in g.shape)
+    merged = tuple(dict.fromkeys([t for t in tops if t in bases] + list(tops) + list(bases)))
+    cap = _native.RG_MAX_PROFILE_THRESHOLDS
+    groups = [merged[i:i + cap] for i in range(0, len(merged), cap)] or [()]
+    got_top, got_base, got_vil = {}, {}, None
+    with torch.cuda.device(g.device):
+        zl = levels if _is_tensor(levels) else torch.from_numpy(levels).to(g.device)
+        for gi, group in enumerate(groups):
+            n = len(group)
+            want_top = any(t in tops for t in group)
+            want_base = any(t in bases for t in group)
+            p_top = torch.empty((n, ny, nx), dtype=torch.float32, device=g.device) if want_top else None
+            p_base = torch.empty((n, ny, nx), dtype=torch.float32, device=g.device) if want_base else None
+            p_vil = torch.empty((ny, nx), dtype=torch.float32, device=g.device) if vil and gi == 0 else None
+            thr = (ctypes.c_double * n)(*group) if n else None
+            _native.check(lib.rg_column_profile_f32(_native.ptr(g), nz, ny * nx, lo, hi, _native.ptr(zl), thr, n,
+                                                    int(interpolation == "linear"), _native.ptr(p_top), _native.ptr(p_base),
+                                                    float(max_dbz), _native.ptr(p_vil), _native.stream_ptr()),
+                          "rg_column_profile_f32")
+            for i, t in enumerate(group):
+                if t in tops:
+                    got_top[t] = p_top[i]
+                if t in bases:
+                    got_base[t] = p_base[i]
+            if p_vil is not None:
+                got_vil = p_vil
+    rec = {}
+    if tops:
+        rec["echo_top"] = {t: got_top[t] for t in tops}
+    if bases:
+        rec["echo_base"] = {t: got_base[t] for t in bases}
+    if vil:
+        rec["vil"] = got_vil
+    return rec
+
+
+def column_profile(grid, geometry, echo_top: Sequence[float] = (), echo_base: Sequence[float] = (), vil: bool = False,
+                   max_dbz: float = 56.0, interpolation: str = "linear", z_min_idx: Optional[int] = None,
+                   z_max_idx: Optional[int] = None, z_min_alt: Optional[float] = None, z_max_alt: Optional[float] = None):
+    """Echo-top heights, echo-base heights and the vertically integrated liquid of every column of ``grid`` in ONE pass
+    over it (``rg_column_profile_f32``): ``{"echo_top": {T: plane}, "echo_base": {T: plane}, "vil": plane}``, keys present
+    as asked for, float32 ``[ny, nx]`` planes.
+
+    ``echo_top`` / ``echo_base``: thresholds (dBZ for a reflectivity grid); the top is the height of the highest level of
+    the window that reaches ``T``, the base of the lowest, NaN where none does.  ``interpolation='linear'`` places the
+    crossing between that level and its finite neighbour beyond it, ``'nearest'`` returns the level's own height.
+    ``vil``: Greene & Clark's ``3.44e-6 * sum(((Z_k + Z_k+1) / 2)^(4/7) * dz)`` in kg m^-2 from dBZ and metres, every
+    level capped at ``max_dbz``; NaN levels count as no echo, an all-NaN column is NaN.  The exact rules -- ties,
+    infinities, the window's ends -- are in ``include/radargrid_hip.h``.  Not in the reference (it has no such product).
+
+    ``geometry``: anything with ``grid_shape`` / ``grid_limits`` (a ``GridGeometry``, ``RoiSearch``, ``MosaicSearch``, or
+    the section objects, whose grids are ``(nz, 1, n_points)``); heights are those of its level axis,
+    ``np.linspace(z_min, z_max, nz)``.  The window arguments are ``column_max``'s; an empty window is a ``ValueError``.
+    Up to ``RG_MAX_PROFILE_THRESHOLDS`` distinct thresholds share a launch, more take further launches.  NumPy in ->
+    NumPy out, cuda float32 tensor in -> tensors out.  Every argument is checked before the device is touched."""
+    tops, bases = check_profile_request(echo_top, echo_base, vil, max_dbz, interpolation)
+    if not (tops or bases or vil):
+        raise ValueError("column_profile: nothing requested (echo_top, echo_base or vil)")
+    if len(grid.shape) != 3:
+        raise ValueError("grid must have shape (nz, ny, nx)")
+    nz = int(grid.shape[0])
+    if int(geometry.grid_shape[0]) != nz:
+        raise ValueError(f"the grid has {nz} levels, the geometry {int(geometry.grid_shape[0])}")
+    levels = profile_levels(geometry, nz)
+    lo, hi = _level_window(nz, z_min_idx, z_max_idx, z_min_alt, z_max_alt, geometry)
+    if lo > hi:
+        raise ValueError(f"empty level window [{lo}, {hi}]")
+    g, as_numpy = _to_device_grid(grid)
+    rec = _profile_planes(g, levels, lo, hi, tops, bases, bool(vil), float(max_dbz), interpolation)
+    for key in ("echo_top", "echo_base"):
+        if key in rec:
+            rec[key] = {t: _finish(p, as_numpy) for t, p in rec[key].items()}
+    if "vil" in rec:
+        rec["vil"] = _finish(rec["vil"], as_numpy)
+    return rec
+
+
+def echo_top(grid, geometry, threshold: float = 18.0, interpolation: str = "linear", z_min_idx: Optional[int] = None,
+             z_max_idx: Optional[int] = None, z_min_alt: Optional[float] = None, z_max_alt: Optional[float] = None):
+    """Echo-top height at ``threshold``: float32 ``[ny, nx]``, NaN where no level of the window reaches it
+    (``column_profile``)."""
+    t = float(threshold)
+    return column_profile(grid, geometry, echo_top=(t,), interpolation=interpolation, z_min_idx=z_min_idx,
+                          z_max_idx=z_max_idx, z_min_alt=z_min_alt, z_max_alt=z_max_alt)["echo_top"][t]
+
+
+def echo_base(grid, geometry, threshold: float = 18.0, interpolation: str = "linear", z_min_idx: Optional[int] = None,
+              z_max_idx: Optional[int] = None, z_min_alt: Optional[float] = None, z_max_alt: Optional[float] = None):
+    """Echo-base height at ``threshold``: float32 ``[ny, nx]``, NaN where no level of the window reaches it
+    (``column_profile``)."""
+    t = float(threshold)
+    return column_profile(grid, geometry, echo_base=(t,), interpolation=interpolation, z_min_idx=z_min_idx,
+                          z_max_idx=z_max_idx, z_min_alt=z_min_alt, z_max_alt=z_max_alt)["echo_base"][t]
+
+
+def vertically_integrated_liquid(grid, geometry, max_dbz: float = 56.0, z_min_idx: Optional[int] = None,
+                                 z_max_idx: Optional[int] = None, z_min_alt: Optional[float] = None,
+                                 z_max_alt: Optional[float] = None):
+    """VIL in kg m^-2 over the level window: float32 ``[ny, nx]``, NaN where the column holds no value
+    (``column_profile``)."""
+    return column_profile(grid, geometry, vil=True, max_dbz=max_dbz, z_min_idx=z_min_idx, z_max_idx=z_max_idx,
+                          z_min_alt=z_min_alt, z_max_alt=z_max_alt)["vil"]

@@ -509,17 +509,26 @@ class PlaneProducts:
     CAPPIs at the given altitudes (``products.py:317-415``) and constant-elevation PPIs at the given angles (``ppi``,
     ``constant_elevation_ppi`` :168-314).  With these and nothing else wanted, the 3-D grid never has to exist in HBM: the
     gridding kernel, walking grid columns, keeps the running maximum / minimum / sum in registers and stores only the levels
-    the CAPPIs blend and the levels each PPI pixel reads."""
+    the CAPPIs blend and the levels each PPI pixel reads.
+
+    The column PROFILE products -- ``echo_top`` / ``echo_base`` heights at the given thresholds and ``vil``
+    (``grid_products.column_profile``, over the same level window) -- are computed from the stored grid by
+    ``rg_column_profile_f32``: the gridding kernels' epilogues do not produce them, so a request that holds one grids, then
+    reduces, and ``fused=True`` together with one is refused."""
 
     def __init__(self, colmax: bool = True, argmax: bool = True, cappi: Sequence[float] = (), interpolation: str = "linear",
                  z_min_idx: Optional[int] = None, z_max_idx: Optional[int] = None, z_min_alt: Optional[float] = None,
                  z_max_alt: Optional[float] = None, fused: Optional[bool] = None, colmin: bool = False, colmean: bool = False,
                  ppi: Sequence[float] = (), ppi_interpolation: str = "linear", earth_curvature: bool = True,
-                 ke: float = EFFECTIVE_RADIUS_FACTOR):
+                 ke: float = EFFECTIVE_RADIUS_FACTOR, echo_top: Sequence[float] = (), echo_base: Sequence[float] = (),
+                 vil: bool = False, vil_max_dbz: float = 56.0, profile_interpolation: str = "linear"):
         """``fused``: ``True`` = take the planes out of the gridding kernel (no 3-D grid in HBM: the memory-saving way),
         ``False`` = grid, then reduce with the separate kernels, ``None`` = whichever the build measured faster (the same
         planes either way, bit for bit).  ``ppi``: elevation angles (degrees); ``ppi_interpolation`` / ``earth_curvature`` /
-        ``ke`` as in ``constant_elevation_ppi`` ('linear' planes are float64, 'nearest' float32)."""
+        ``ke`` as in ``constant_elevation_ppi`` ('linear' planes are float64, 'nearest' float32).  ``echo_top`` /
+        ``echo_base``: thresholds; ``vil`` with ``vil_max_dbz``; ``profile_interpolation`` as ``column_profile``'s
+        ``interpolation``."""
+        from .grid_products import check_profile_request
         if interpolation not in ("linear", "nearest"):
             raise ValueError(f"Unknown interpolation method: {interpolation}")
         if ppi_interpolation not in ("linear", "nearest"):
@@ -536,11 +545,23 @@ class PlaneProducts:
         self.ppi_interpolation = ppi_interpolation
         self.earth_curvature = bool(earth_curvature)
         self.ke = float(ke)
+        self.echo_top, self.echo_base = check_profile_request(echo_top, echo_base, vil, vil_max_dbz, profile_interpolation)
+        self.vil = bool(vil)
+        self.vil_max_dbz = float(vil_max_dbz)
+        self.profile_interpolation = profile_interpolation
+        if fused and self.profile:
+            raise ValueError("fused=True cannot produce echo_top / echo_base / vil: the gridding kernels' epilogues do not "
+                             "compute them (leave fused unset: grid, then reduce)")
 
     @property
     def columns(self) -> bool:
         """Any product over the level window."""
         return self.colmax or self.colmin or self.colmean
+
+    @property
+    def profile(self) -> bool:
+        """Any column profile product (echo top / base, VIL): computed from the stored grid only."""
+        return bool(self.echo_top or self.echo_base or self.vil)
 
     @property
     def needs_planes_mode(self) -> bool:
@@ -578,12 +599,18 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
     separately (measured, see below).  COLMAX / argmax / CAPPI alone run ``rg_csr_compact_apply_columns_f32``; a request
     with a column minimum, mean or PPI runs ``rg_csr_compact_apply_planes_f32`` (a mean keeps each column in one workgroup;
     more than ``RG_MAX_SEL_PLANES`` PPIs take further launches of it, each gridding the fields again).  Default
-    (``fused=None``) and ``fused=False``: grid as usual, reduce with the separate kernels."""
+    (``fused=None``) and ``fused=False``: grid as usual, reduce with the separate kernels.
+
+    A request with a column profile product (``echo_top`` / ``echo_base`` / ``vil``) adds ``"echo_top": {T: plane}``,
+    ``"echo_base": {T: plane}``, ``"vil": plane`` -- what ``column_profile`` returns for the same grid -- and always grids,
+    then reduces; ``fused=True`` with one is a ``ValueError``."""
     from . import grid_products as gp
     torch = _native.torch_mod()
     products = products if products is not None else PlaneProducts()
     if fused is None:
         fused = products.fused
+    if fused and products.profile:
+        raise ValueError("fused=True cannot produce echo_top / echo_base / vil (grid, then reduce: leave fused unset)")
     n_fields = len(fields)
     if n_fields == 0:
         raise ValueError("no fields to grid")
@@ -594,8 +621,11 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
         masks = [None] * n_fields
     nz, ny, nx = (int(s) for s in geometry.grid_shape)
     lo, hi = gp._level_window(nz, *products.window, geometry)
-    if products.columns and lo > hi:
+    if (products.columns or products.profile) and lo > hi:
         raise ValueError(f"empty level window [{lo}, {hi}]")
+    if products.profile:
+        gp.profile_levels(geometry, nz)            # refused here, before any device work
+    levels = None                                  # the profile products' level heights: uploaded once, below
     plans = cappi_plans(products, geometry, nz)
     needed = sorted({k for plan in plans.values() if plan[0] != "outside" for k in ((plan[1], plan[1] + 1) if plan[0] == "blend"
                                                                                     else (plan[1],))})
@@ -616,7 +646,8 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
             # measured (profiles/r04_columns_variants_*.json, r04_nf4_lds_rowsums.json): walking columns costs what the store it
             # saves costs -- 8.2 vs 8.1 ms for one field, 10.7 vs 10.5 for three, 11.4 vs 11.2 for four on the bench grid --
             # so the epilogue is the MEMORY-saving choice (no F x 640 MB of grid) and is taken on request, not by default
-            run_fused = (gridder.has_columns_kernel and (nf >= _COLUMNS_FUSE_MIN_FIELDS if fused is None else bool(fused)))
+            run_fused = (gridder.has_columns_kernel and not products.profile      # the profile products need the stored grid
+                         and (nf >= _COLUMNS_FUSE_MIN_FIELDS if fused is None else bool(fused)))
             fused_planes = {}
             if run_fused:
                 cmax = torch.empty((nf, ny, nx), dtype=torch.float32, device=dev) if products.colmax else None
@@ -636,7 +667,9 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
                 gridder.apply(grids.view(nf, -1), fill_value)
             for k in range(nf):
                 if not run_fused:
-                    results.append(products_of_grid(products, grids[k], geometry, lo, hi, plans))
+                    if products.profile and levels is None:
+                        levels = gp.profile_levels_device(geometry, nz, dev)
+                    results.append(products_of_grid(products, grids[k], geometry, lo, hi, plans, levels))
                     continue
                 rec = {}
                 if products.colmax:
@@ -686,10 +719,12 @@ def _cappi_planes(plans: dict, level, ny: int, nx: int, dev) -> dict:
     return out
 
 
-def products_of_grid(products: PlaneProducts, grid, geometry, lo: int, hi: int, plans: dict) -> dict:
+def products_of_grid(products: PlaneProducts, grid, geometry, lo: int, hi: int, plans: dict, levels=None) -> dict:
     """The planes ``grid_products_device`` returns for one field, from its stored grid ``[nz, ny, nx]`` (device) through the
     separate kernels: ``column_argmax`` / ``column_max`` over levels ``lo .. hi``, ``reduce_planes``, the CAPPIs of ``plans``
-    (``cappi_plans``).  ``geometry``: anything with the grid's ``grid_shape`` / ``grid_limits``."""
+    (``cappi_plans``), and the column profile products over the same levels (``profile_planes``).  ``geometry``: anything
+    with the grid's ``grid_shape`` / ``grid_limits``.  ``levels``: ``profile_levels_device`` of the geometry, from a caller
+    that reduces several grids (``None``: uploaded here)."""
     from . import grid_products as gp
     _, ny, nx = (int(s) for s in grid.shape)
     rec = {}
@@ -704,6 +739,22 @@ def products_of_grid(products: PlaneProducts, grid, geometry, lo: int, hi: int, 
         rec["cappi"] = _cappi_planes(plans, lambda z: grid[z], ny, nx, grid.device)
     if products.ppi:
         rec["ppi"] = ppi_recs
+    return profile_planes(products, grid, geometry, lo, hi, rec, levels)
+
+
+def profile_planes(products: PlaneProducts, grid, geometry, lo: int, hi: int, rec: dict, levels=None) -> dict:
+    """The column profile products of a request for one stored grid ``[nz, ny, nx]`` (device), levels ``lo .. hi``:
+    ``echo_top`` / ``echo_base`` / ``vil`` as ``grid_products.column_profile`` returns them (one ``rg_column_profile_f32``
+    launch per four distinct thresholds) -- added to ``rec``; nothing when the request holds none.  ``levels``: the level
+    heights already on the grid's device (``grid_products.profile_levels_device``), or ``None`` to upload them here."""
+    from . import grid_products as gp
+    if products.profile:
+        if lo > hi:
+            raise ValueError(f"empty level window [{lo}, {hi}]")
+        if levels is None:
+            levels = gp.profile_levels_device(geometry, int(grid.shape[0]), grid.device)
+        rec.update(gp._profile_planes(grid, levels, lo, hi, products.echo_top,
+                                      products.echo_base, products.vil, products.vil_max_dbz, products.profile_interpolation))
     return rec
 
 

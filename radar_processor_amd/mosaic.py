@@ -648,11 +648,12 @@ def _products_of_grids(products, grids, spec) -> List[dict]:
     torch = _native.torch_mod()
     nz = int(spec.grid_shape[0])
     lo, hi = gp._level_window(nz, *products.window, spec)
-    if products.columns and lo > hi:
+    if (products.columns or products.profile) and lo > hi:
         raise ValueError(f"empty level window [{lo}, {hi}]")
     plans = cappi_plans(products, spec, nz)
     with torch.cuda.device(grids.device):
-        return [products_of_grid(products, grids[k], spec, lo, hi, plans) for k in range(grids.shape[0])]
+        levels = gp.profile_levels_device(spec, nz, grids.device) if products.profile else None     # one upload per call
+        return [products_of_grid(products, grids[k], spec, lo, hi, plans, levels) for k in range(grids.shape[0])]
 
 
 # ------------------------------------------------------------------------------------------------------------------------
