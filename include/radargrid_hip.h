@@ -612,6 +612,29 @@ int rg_csr_compact_apply_packed_f32(const void* indptr, int32_t indptr_is_i64, c
                                     int64_t n_gates, float fill_value, float* out, int32_t window_cap, int32_t tile,
                                     rg_stream_t stream);
 
+/* The ROW-END TABLE of a grid's row pointers, derived data built once per geometry: row_end16[v] = indptr[v + 1] -
+ * indptr[r0], the end of row v among the pairs of its segment (r0 = the segment's first row; segments as above: the balanced
+ * cuts of a line).  A segment of about 4 600 pairs needs no 8-byte row pointers to say where its rows begin: with the table
+ * the row-wise kernel reads 2 bytes per row instead of indptr[v] and indptr[v + 1], and no indptr at all.  A segment whose
+ * span exceeds RG_ROW_END16_MAX holds RG_ROW_END16_WIDE in every entry (the kernel tests the last one, once per wavefront)
+ * and keeps reading indptr.  rg_csr_row_ends16 writes the table of n_rows rows (int32 or int64 indptr; for a slab of whole
+ * planes pass the slab's indptr, n_rows and row_end16 + the slab's first row: an entry depends on its own segment alone).
+ * The _ex variants of the three entry points over the packed records take the table as their argument before `stream`;
+ * NULL = no table, every segment reads indptr -- which is exactly what the entry points without _ex do.  Same bits either
+ * way: the table hands the kernel the same integers.  All of them (with or without a table) leave a chunk without a record
+ * -- rec_ptr equal at both ends of the workgroup's RG_COMPACT_LINES slots, RG_REC_ORDER_DISPATCH, grid mode -- as soon as
+ * its rows hold fill_value. */
+#define RG_ROW_END16_MAX 65534
+#define RG_ROW_END16_WIDE 0xFFFFu
+int rg_csr_row_ends16(const void* indptr, int32_t indptr_is_i64, int64_t n_rows, int64_t line_len, int64_t lines_per_plane,
+                      uint16_t* row_end16, rg_stream_t stream);
+int rg_csr_compact_apply_packed_f32_ex(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                       const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base, const int64_t* dict_ptr,
+                                       const int32_t* dict, int64_t n_vox, int64_t n_pairs, int64_t line_len,
+                                       int64_t lines_per_plane, const float* packed, int32_t n_fields, int32_t stride,
+                                       int64_t n_gates, float fill_value, float* out, int32_t window_cap, int32_t tile,
+                                       const uint16_t* row_end16, rg_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * K1p  the row-wise kernel in COLUMN MODE, with an optional products epilogue.
  * Replaces, in one pass over the packed records: radar_grid/interpolate.py:69-104 (apply_geometry) / :137-140
@@ -648,6 +671,15 @@ int rg_csr_compact_apply_columns_f32(const void* indptr, int32_t indptr_is_i64, 
                                      int32_t n_keep, float* col_max, int32_t* col_arg, int32_t col_lo, int32_t col_hi,
                                      int32_t window_cap, int32_t z_pieces, const int32_t* order, void* workspace,
                                      int64_t workspace_bytes, int32_t lanes_hint, rg_stream_t stream);
+int rg_csr_compact_apply_columns_f32_ex(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                        const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base, const int64_t* dict_ptr,
+                                        const int32_t* dict, int64_t n_vox, int64_t n_pairs, int64_t line_len,
+                                        int64_t lines_per_plane, const float* packed, int32_t n_fields, int32_t stride,
+                                        int64_t n_gates, float fill_value, float* out, float* level_planes, int32_t keep_lo,
+                                        int32_t n_keep, float* col_max, int32_t* col_arg, int32_t col_lo, int32_t col_hi,
+                                        int32_t window_cap, int32_t z_pieces, const int32_t* order, void* workspace,
+                                        int64_t workspace_bytes, int32_t lanes_hint, const uint16_t* row_end16,
+                                        rg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * K1q  PLANES MODE: the column mode of K1p with a wider products epilogue, for callers that keep 2-D products only.
@@ -697,6 +729,13 @@ int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indptr_is_i64, c
                                     int64_t n_gates, float fill_value, const rg_plane_request* req, int32_t window_cap,
                                     int32_t z_pieces, const int32_t* order, void* workspace, int64_t workspace_bytes,
                                     int32_t lanes_hint, rg_stream_t stream);
+int rg_csr_compact_apply_planes_f32_ex(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                       const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base, const int64_t* dict_ptr,
+                                       const int32_t* dict, int64_t n_vox, int64_t n_pairs, int64_t line_len,
+                                       int64_t lines_per_plane, const float* packed, int32_t n_fields, int32_t stride,
+                                       int64_t n_gates, float fill_value, const rg_plane_request* req, int32_t window_cap,
+                                       int32_t z_pieces, const int32_t* order, void* workspace, int64_t workspace_bytes,
+                                       int32_t lanes_hint, const uint16_t* row_end16, rg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * a12p / a12f  constant-elevation PPI in two halves around K1q (radar_grid/products.py:168-314).  Scalars, xc / yc and

@@ -37,6 +37,8 @@ RG_COMPACT_LINES = 4          # grid lines (= wavefronts) per chunk of the compa
 RG_COMPACT_MAX_WINDOW = 8192
 RG_COMPACT_ROTATION = 5       # block -> chunk column rotation per line group (header: RG_COMPACT_ROTATION)
 RG_REC_ORDER_SEGMENT, RG_REC_ORDER_DISPATCH = 0, 1
+RG_ROW_END16_MAX = 65534      # largest segment span the row-end table holds (header: RG_ROW_END16_MAX)
+RG_ROW_END16_WIDE = 0xFFFF    # table entries of a segment beyond it, which reads the row pointers (header: RG_ROW_END16_WIDE)
 RG_DENSE_MAX_DICT = 2048      # chunks with at most this many dictionary entries keep 14-byte records (header: RG_DENSE_MAX_DICT)
 
 
@@ -127,6 +129,20 @@ SIGNATURES = {
     "rg_csr_compact_apply_packed_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, ctypes.c_uint32, c_void_p,
                                                   c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32,
                                                   c_int32, c_int64, c_float, c_void_p, c_int32, c_int32, c_void_p]),
+    "rg_csr_row_ends16": (c_int32, [c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "rg_csr_compact_apply_packed_f32_ex": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, ctypes.c_uint32, c_void_p,
+                                                     c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32,
+                                                     c_int32, c_int64, c_float, c_void_p, c_int32, c_int32, c_void_p,
+                                                     c_void_p]),
+    "rg_csr_compact_apply_columns_f32_ex": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, ctypes.c_uint32, c_void_p,
+                                                      c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32,
+                                                      c_int32, c_int64, c_float, c_void_p, c_void_p, c_int32, c_int32,
+                                                      c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                                      c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "rg_csr_compact_apply_planes_f32_ex": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, ctypes.c_uint32, c_void_p,
+                                                     c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32,
+                                                     c_int32, c_int64, c_float, POINTER(PlaneRequest), c_int32, c_int32,
+                                                     c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "rg_csr_columns_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
     "rg_csr_compact_apply_columns_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, ctypes.c_uint32, c_void_p,
                                                    c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32,

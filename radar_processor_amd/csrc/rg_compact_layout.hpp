@@ -85,6 +85,8 @@ struct StreamArgs {
   int max_fields;          // 8 for rg_csr_compact_apply_packed_f32 (whose tile kernel refuses 5-8 itself); 4 for the other two
   bool need_out;           // the grid is all rg_csr_compact_apply_packed_f32 produces; the other two may store planes only
   bool need_packed;        // column / planes modes: packed fields present and 16-byte aligned even without a pair
+  // the _ex variants of the three entry points
+  const uint16_t* row_end16 = nullptr;   // rg_csr_row_ends16's table of the same grid, or null: every segment reads indptr
 };
 
 }  // namespace rgl

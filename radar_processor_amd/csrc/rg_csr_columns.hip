@@ -99,20 +99,22 @@ extern "C" int64_t rg_csr_columns_workspace_bytes(int64_t lines_per_plane, int64
   return (int64_t)z_pieces * n_fields * lines_per_plane * line_len * 8;      // partial (max, arg) planes
 }
 
-extern "C" int rg_csr_compact_apply_columns_f32(const void* indptr, int32_t indptr_is_i64, const void* records,
-                                                const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
-                                                const int64_t* dict_ptr, const int32_t* dict, int64_t n_vox, int64_t n_pairs,
-                                                int64_t line_len, int64_t lines_per_plane, const float* packed,
-                                                int32_t n_fields, int32_t stride, int64_t n_gates, float fill_value,
-                                                float* out, float* level_planes, int32_t keep_lo, int32_t n_keep,
-                                                float* col_max, int32_t* col_arg, int32_t col_lo, int32_t col_hi,
-                                                int32_t window_cap, int32_t z_pieces, const int32_t* order, void* workspace,
-                                                int64_t workspace_bytes, int32_t lanes_hint, rg_stream_t stream) {
+// _ex: with the row-end table of the grid (rg_csr_row_ends16; null = none, what rg_csr_compact_apply_columns_f32 passes)
+extern "C" int rg_csr_compact_apply_columns_f32_ex(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                                   const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
+                                                   const int64_t* dict_ptr, const int32_t* dict, int64_t n_vox, int64_t n_pairs,
+                                                   int64_t line_len, int64_t lines_per_plane, const float* packed,
+                                                   int32_t n_fields, int32_t stride, int64_t n_gates, float fill_value,
+                                                   float* out, float* level_planes, int32_t keep_lo, int32_t n_keep,
+                                                   float* col_max, int32_t* col_arg, int32_t col_lo, int32_t col_hi,
+                                                   int32_t window_cap, int32_t z_pieces, const int32_t* order, void* workspace,
+                                                   int64_t workspace_bytes, int32_t lanes_hint, const uint16_t* row_end16,
+                                                   rg_stream_t stream) {
   RG_REQUIRE(out || level_planes || col_max, RG_EINVAL,
              "rg_csr_compact_apply_columns_f32: nothing to produce (out, level_planes and col_max are all null)");
   const StreamArgs a{indptr, indptr_is_i64 != 0, records, rec_ptr, rec_order, w_base, dict_ptr, dict, n_vox, n_pairs, line_len,
                      lines_per_plane, packed, n_fields, stride, n_gates, fill_value, out, window_cap, lanes_hint,
-                     (hipStream_t)stream, /*max_fields=*/4, /*need_out=*/false, /*need_packed=*/true};
+                     (hipStream_t)stream, /*max_fields=*/4, /*need_out=*/false, /*need_packed=*/true, row_end16};
   ChunkGrid cg;
   int st = check_stream_args("rg_csr_compact_apply_columns_f32", a, &cg);
   if (st != RG_OK || n_vox == 0) return st;
@@ -164,6 +166,21 @@ extern "C" int rg_csr_compact_apply_columns_f32(const void* indptr, int32_t indp
   return RG_OK;
 }
 
+extern "C" int rg_csr_compact_apply_columns_f32(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                                const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
+                                                const int64_t* dict_ptr, const int32_t* dict, int64_t n_vox, int64_t n_pairs,
+                                                int64_t line_len, int64_t lines_per_plane, const float* packed,
+                                                int32_t n_fields, int32_t stride, int64_t n_gates, float fill_value,
+                                                float* out, float* level_planes, int32_t keep_lo, int32_t n_keep,
+                                                float* col_max, int32_t* col_arg, int32_t col_lo, int32_t col_hi,
+                                                int32_t window_cap, int32_t z_pieces, const int32_t* order, void* workspace,
+                                                int64_t workspace_bytes, int32_t lanes_hint, rg_stream_t stream) {
+  return rg_csr_compact_apply_columns_f32_ex(indptr, indptr_is_i64, records, rec_ptr, rec_order, w_base, dict_ptr, dict, n_vox,
+                                             n_pairs, line_len, lines_per_plane, packed, n_fields, stride, n_gates, fill_value,
+                                             out, level_planes, keep_lo, n_keep, col_max, col_arg, col_lo, col_hi, window_cap,
+                                             z_pieces, order, workspace, workspace_bytes, lanes_hint, nullptr, stream);
+}
+
 // K1q  rg_csr_compact_apply_planes_f32: the column mode with the wider epilogue (csr_compact_rowwise_kernel<..., PLANES = true>):
 // COLMIN (radar_grid/products.py:493-535) and COLMEAN (:538-580) over the level window next to COLMAX, and the per-pixel
 // levels of constant-elevation PPIs (:168-314) stored as samples for rg_elevation_ppi_finish_f32.  The min merges over level
@@ -177,14 +194,15 @@ extern "C" int64_t rg_csr_planes_workspace_bytes(int64_t lines_per_plane, int64_
   return (int64_t)z_pieces * n_fields * lines_per_plane * line_len * ((want_max ? 8 : 0) + (want_min ? 4 : 0));
 }
 
-extern "C" int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indptr_is_i64, const void* records,
-                                               const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
-                                               const int64_t* dict_ptr, const int32_t* dict, int64_t n_vox, int64_t n_pairs,
-                                               int64_t line_len, int64_t lines_per_plane, const float* packed,
-                                               int32_t n_fields, int32_t stride, int64_t n_gates, float fill_value,
-                                               const rg_plane_request* req, int32_t window_cap, int32_t z_pieces,
-                                               const int32_t* order, void* workspace, int64_t workspace_bytes,
-                                               int32_t lanes_hint, rg_stream_t stream) {
+// _ex: with the row-end table of the grid (rg_csr_row_ends16; null = none, what rg_csr_compact_apply_planes_f32 passes)
+extern "C" int rg_csr_compact_apply_planes_f32_ex(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                                  const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
+                                                  const int64_t* dict_ptr, const int32_t* dict, int64_t n_vox, int64_t n_pairs,
+                                                  int64_t line_len, int64_t lines_per_plane, const float* packed,
+                                                  int32_t n_fields, int32_t stride, int64_t n_gates, float fill_value,
+                                                  const rg_plane_request* req, int32_t window_cap, int32_t z_pieces,
+                                                  const int32_t* order, void* workspace, int64_t workspace_bytes,
+                                                  int32_t lanes_hint, const uint16_t* row_end16, rg_stream_t stream) {
   RG_REQUIRE(req, RG_EINVAL, "rg_csr_compact_apply_planes_f32: null request");
   RG_REQUIRE(req->n_sel >= 0 && req->n_sel <= RG_MAX_SEL_PLANES, RG_EINVAL,
              "rg_csr_compact_apply_planes_f32: n_sel=%d outside 0..%d", req->n_sel, RG_MAX_SEL_PLANES);
@@ -200,7 +218,7 @@ extern "C" int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indpt
   RG_REQUIRE(!req->col_arg || req->col_max, RG_EINVAL, "rg_csr_compact_apply_planes_f32: col_arg needs col_max");
   const StreamArgs a{indptr, indptr_is_i64 != 0, records, rec_ptr, rec_order, w_base, dict_ptr, dict, n_vox, n_pairs, line_len,
                      lines_per_plane, packed, n_fields, stride, n_gates, fill_value, req->out, window_cap, lanes_hint,
-                     (hipStream_t)stream, /*max_fields=*/4, /*need_out=*/false, /*need_packed=*/true};
+                     (hipStream_t)stream, /*max_fields=*/4, /*need_out=*/false, /*need_packed=*/true, row_end16};
   ChunkGrid cg;
   int st = check_stream_args("rg_csr_compact_apply_planes_f32", a, &cg);
   if (st != RG_OK || n_vox == 0) return st;
@@ -261,4 +279,17 @@ extern "C" int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indpt
     return rg::check_launch("rg_csr_compact_apply_planes_f32 (min merge)");
   }
   return RG_OK;
+}
+
+extern "C" int rg_csr_compact_apply_planes_f32(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                               const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
+                                               const int64_t* dict_ptr, const int32_t* dict, int64_t n_vox, int64_t n_pairs,
+                                               int64_t line_len, int64_t lines_per_plane, const float* packed,
+                                               int32_t n_fields, int32_t stride, int64_t n_gates, float fill_value,
+                                               const rg_plane_request* req, int32_t window_cap, int32_t z_pieces,
+                                               const int32_t* order, void* workspace, int64_t workspace_bytes,
+                                               int32_t lanes_hint, rg_stream_t stream) {
+  return rg_csr_compact_apply_planes_f32_ex(indptr, indptr_is_i64, records, rec_ptr, rec_order, w_base, dict_ptr, dict, n_vox,
+                                            n_pairs, line_len, lines_per_plane, packed, n_fields, stride, n_gates, fill_value, req,
+                                            window_cap, z_pieces, order, workspace, workspace_bytes, lanes_hint, nullptr, stream);
 }

@@ -1,5 +1,5 @@
 // Building the compact CSR copy (layout: head of rg_csr_compact.hip): rg_csr_compact_count and rg_csr_compact_fill find the
-// distinct gates of every chunk and each pair's position among them.
+// distinct gates of every chunk and each pair's position among them; rg_csr_row_ends16 writes the row-end table.
 #include "rg_compact_layout.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -202,7 +202,48 @@ __global__ __launch_bounds__(kBuildThreads) void compact_fill_kernel(const IndT*
   if (threadIdx.x == 0 && base != expect) atomicOr(error_flag, 4);
 }
 
+// The row-end table the row-wise kernel reads instead of the row pointers (rg_csr_rowwise.hpp): one workgroup per grid line,
+// one thread per row.  row_end16[v] = indptr[v + 1] - indptr[first row of v's segment]; every row of a segment whose span
+// exceeds RG_ROW_END16_MAX gets RG_ROW_END16_WIDE (the kernel looks at the last one), so a table entry depends on the row
+// pointers of its own segment alone -- a slab of whole planes writes what the whole grid would.
+template <typename IndT>
+__global__ __launch_bounds__(kBuildThreads) void row_ends16_kernel(const IndT* __restrict__ indptr, ChunkGrid cg,
+                                                                   uint16_t* __restrict__ row_end16) {
+  const long row0 = (long)blockIdx.x * cg.line_len;
+  const unsigned split = cg.seg_extra * (cg.seg_base + 1);      // rows of a line that lie in the longer segments
+  for (unsigned x = threadIdx.x; x < (unsigned)cg.line_len; x += kBuildThreads) {
+    const unsigned sx = x < split ? x / (cg.seg_base + 1) : cg.seg_extra + (x - split) / cg.seg_base;
+    const unsigned x0 = sx * cg.seg_base + (sx < cg.seg_extra ? sx : cg.seg_extra);
+    const unsigned nrows = cg.seg_base + (sx < cg.seg_extra ? 1u : 0u);
+    const long seg_b = (long)indptr[row0 + x0];
+    const long span = (long)indptr[row0 + x0 + nrows] - seg_b;
+    const long end = (long)indptr[row0 + x + 1] - seg_b;
+    row_end16[row0 + x] = span <= RG_ROW_END16_MAX ? (uint16_t)end : (uint16_t)RG_ROW_END16_WIDE;
+  }
+}
+
 }  // namespace
+
+extern "C" int rg_csr_row_ends16(const void* indptr, int32_t indptr_is_i64, int64_t n_rows, int64_t line_len,
+                                 int64_t lines_per_plane, uint16_t* row_end16, rg_stream_t stream) {
+  RG_REQUIRE(n_rows >= 0, RG_EINVAL, "rg_csr_row_ends16: negative size");
+  if (n_rows == 0) return RG_OK;
+  RG_REQUIRE(indptr && row_end16, RG_EINVAL, "rg_csr_row_ends16: null pointer");
+  ChunkGrid cg;
+  RG_REQUIRE(make_chunk_grid(n_rows, line_len, lines_per_plane, &cg), RG_EINVAL,
+             "rg_csr_row_ends16: n_rows=%ld is not planes x lines_per_plane=%ld x line_len=%ld", (long)n_rows,
+             (long)lines_per_plane, (long)line_len);
+  const long n_lines = cg.n_planes * cg.lines_per_plane;
+  RG_REQUIRE(n_lines <= 0x7FFFFFFFL && cg.line_len <= 0x7FFFFFFFL, RG_EUNSUPPORTED, "rg_csr_row_ends16: too many lines for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  if (indptr_is_i64)
+    hipLaunchKernelGGL(row_ends16_kernel<int64_t>, dim3((unsigned)n_lines), dim3(kBuildThreads), 0, s,
+                       static_cast<const int64_t*>(indptr), cg, row_end16);
+  else
+    hipLaunchKernelGGL(row_ends16_kernel<int32_t>, dim3((unsigned)n_lines), dim3(kBuildThreads), 0, s,
+                       static_cast<const int32_t*>(indptr), cg, row_end16);
+  return rg::check_launch("rg_csr_row_ends16");
+}
 
 extern "C" int rg_csr_compact_count(const void* indptr, int32_t indptr_is_i64, const int32_t* gate_idx, int64_t n_rows,
                                     int64_t line_len, int64_t lines_per_plane, int32_t* chunk_counts,

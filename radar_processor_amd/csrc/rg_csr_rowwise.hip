@@ -37,13 +37,16 @@ int launch_rowwise_grid(const StreamArgs& a, const ChunkGrid& cg) {
 // tile = 384: the tile kernel over the same records (agrees with it bit for bit);
 // tile = 2000 + h: row-wise with a diagnostic lane split (h = 1..64: that many lanes per row; h = 70 + t: aim for t
 // records per lane and row) -- a different split is a different order of the float32 adds.
-extern "C" int rg_csr_compact_apply_packed_f32(const void* indptr, int32_t indptr_is_i64, const void* records,
-                                               const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
-                                               const int64_t* dict_ptr,
-                                               const int32_t* dict, int64_t n_vox, int64_t n_pairs, int64_t line_len,
-                                               int64_t lines_per_plane, const float* packed, int32_t n_fields,
-                                               int32_t stride, int64_t n_gates, float fill_value, float* out,
-                                               int32_t window_cap, int32_t tile, rg_stream_t stream) {
+// _ex: the same pass with the row-end table of the grid (rg_csr_row_ends16), which the row-wise kernel reads instead of the
+// row pointers wherever a segment's span fits it; null = no table, which is what rg_csr_compact_apply_packed_f32 passes.
+extern "C" int rg_csr_compact_apply_packed_f32_ex(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                                  const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
+                                                  const int64_t* dict_ptr,
+                                                  const int32_t* dict, int64_t n_vox, int64_t n_pairs, int64_t line_len,
+                                                  int64_t lines_per_plane, const float* packed, int32_t n_fields,
+                                                  int32_t stride, int64_t n_gates, float fill_value, float* out,
+                                                  int32_t window_cap, int32_t tile, const uint16_t* row_end16,
+                                                  rg_stream_t stream) {
   const bool rowwise = tile == 0 || tile >= 2000;
   const int lanes_hint = tile >= 2000 ? tile - 2000 : 0;
   RG_REQUIRE(tile == 0 || tile == 384 ||
@@ -56,9 +59,21 @@ extern "C" int rg_csr_compact_apply_packed_f32(const void* indptr, int32_t indpt
              "128-pair tiles, not a whole number of 64-record loads); the row-wise kernel takes 1-8", n_fields);
   const StreamArgs a{indptr, indptr_is_i64 != 0, records, rec_ptr, rec_order, w_base, dict_ptr, dict, n_vox, n_pairs, line_len,
                      lines_per_plane, packed, n_fields, stride, n_gates, fill_value, out, window_cap, lanes_hint,
-                     (hipStream_t)stream, /*max_fields=*/8, /*need_out=*/true, /*need_packed=*/false};
+                     (hipStream_t)stream, /*max_fields=*/8, /*need_out=*/true, /*need_packed=*/false, row_end16};
   ChunkGrid cg;
   const int st = check_stream_args("rg_csr_compact_apply_packed_f32", a, &cg);
   if (st != RG_OK || n_vox == 0) return st;
   return rowwise ? launch_rowwise_grid(a, cg) : rg_launch_tile_packed(a, cg);
+}
+
+extern "C" int rg_csr_compact_apply_packed_f32(const void* indptr, int32_t indptr_is_i64, const void* records,
+                                               const int64_t* rec_ptr, int32_t rec_order, uint32_t w_base,
+                                               const int64_t* dict_ptr,
+                                               const int32_t* dict, int64_t n_vox, int64_t n_pairs, int64_t line_len,
+                                               int64_t lines_per_plane, const float* packed, int32_t n_fields,
+                                               int32_t stride, int64_t n_gates, float fill_value, float* out,
+                                               int32_t window_cap, int32_t tile, rg_stream_t stream) {
+  return rg_csr_compact_apply_packed_f32_ex(indptr, indptr_is_i64, records, rec_ptr, rec_order, w_base, dict_ptr, dict, n_vox,
+                                            n_pairs, line_len, lines_per_plane, packed, n_fields, stride, n_gates, fill_value,
+                                            out, window_cap, tile, nullptr, stream);
 }

@@ -64,7 +64,8 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     const IndT* __restrict__ indptr, const int64_t* __restrict__ dict_ptr, const int32_t* __restrict__ dict, ChunkGrid cg,
     const float* __restrict__ packed, unsigned last_gate, float fill, int window_cap, long n_vox, float* __restrict__ out,
     const rg_u32x4* __restrict__ rec, const int64_t* __restrict__ rec_ptr, unsigned w_base, int lanes_hint,
-    int rec_order, unsigned n_chunks, int chunks_per_block, const std::conditional_t<COLS == 2, RowwisePlanes, RowwiseColumns> cols) {
+    int rec_order, unsigned n_chunks, int chunks_per_block, const std::conditional_t<COLS == 2, RowwisePlanes, RowwiseColumns> cols,
+    const uint16_t* __restrict__ row_end16) {
   static_assert(NF >= 1 && NF <= 8 && STRIDE == stride_for(NF), "passes of 1-8 fields");
   constexpr bool PLANES = COLS == 2;
   static_assert(!PLANES || NF <= 4, "the planes mode is the column mode of 1-4 fields");
@@ -154,6 +155,22 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     if (bid >= n_chunks) break;                       // workgroup-uniform
     chunk = block_chunk(cg, bid);
   }
+  // Grid mode, dispatch order: a chunk without a record.  The workgroup's kH segments occupy slots bid * kH .. bid * kH + kH - 1 of
+  // rec_ptr and a segment without pairs takes no unit, so equal ends mean that no row of the chunk has a neighbour (30 % of the
+  // bench grid's chunks: the corners beyond the range, the cone above the top sweep).  Every wavefront stores `fill` to its
+  // rows and is done: no dictionary, no row pointers or row ends, no window, no barrier -- the test reads two entries of
+  // rec_ptr at addresses that depend on the block alone, so it is WORKGROUP-UNIFORM: all four wavefronts skip the barrier
+  // below together, or none does.  (The column and planes modes keep their path: their epilogue runs on these values.)
+  if constexpr (!COLS) {
+    if (rec_order == RG_REC_ORDER_DISPATCH && rec_ptr[(long)bid * kH] == rec_ptr[((long)bid + 1) * kH]) {
+      const Segment se = chunk_segment(cg, chunk, wv);
+      if (lane < se.nrows) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f) out[(size_t)f * n_vox + se.r0 + lane] = fill;
+      }
+      continue;
+    }
+  }
   if (cb > 0) __syncthreads();                        // every wavefront is done with the previous chunk's window
   float mine_p[NF], mine_w[NF];                       // kRegs: lane == row
 #pragma unroll
@@ -172,11 +189,25 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   const Segment sg = chunk_segment(cg, chunk, wv);
   const int nrows = sg.nrows;
   const long r0 = sg.r0;
-  const long seg_b = nrows ? (long)indptr[r0] : 0;
-  const long seg_e = nrows ? (long)indptr[r0 + nrows] : 0;
-  const int span = (int)(seg_e - seg_b);
-  const int rs_o = nrows ? (int)((long)indptr[r0 + (lane < nrows ? lane : nrows)] - seg_b) : 0;
-  const int re_o = nrows ? (int)((long)indptr[r0 + (lane + 1 < nrows ? lane + 1 : nrows)] - seg_b) : 0;
+  // Where the rows of the segment begin and end among its pairs: rs_o / re_o of lane == row (a lane past the last row: both
+  // = span).  With the row-end table (rg_csr_row_ends16: row_end16[v] = indptr[v + 1] - indptr[r0], two bytes per row instead
+  // of indptr's two 8-byte reads) a row begins where the previous one ended, the first at 0, and the span is the last row's
+  // end; a segment whose span does not fit carries RG_ROW_END16_WIDE in its last entry and reads indptr as before.  Lanes
+  // past the last row read the last entry, so lane 63 holds it whatever nrows is: the choice is wave-uniform, and the 16-bit
+  // path reads no indptr.  Both paths hand on the same integers.
+  int span = 0, rs_o = 0, re_o = 0;
+  unsigned e16 = RG_ROW_END16_WIDE;
+  if (row_end16 && nrows) e16 = row_end16[r0 + (lane < nrows ? lane : nrows - 1)];
+  if (__builtin_amdgcn_readlane((int)e16, 63) != (int)RG_ROW_END16_WIDE) {
+    re_o = (int)e16;
+    rs_o = __builtin_amdgcn_update_dpp(0, (int)e16, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);   // lane 0 keeps the 0
+    span = __builtin_amdgcn_readlane((int)e16, 63);
+  } else if (nrows) {
+    const long seg_b = (long)indptr[r0];
+    span = (int)((long)indptr[r0 + nrows] - seg_b);
+    rs_o = (int)((long)indptr[r0 + (lane < nrows ? lane : nrows)] - seg_b);
+    re_o = (int)((long)indptr[r0 + (lane + 1 < nrows ? lane + 1 : nrows)] - seg_b);
+  }
   long rec_b = 0, rec_n = 0;
   if (nrows) {
     // dispatch order: the H segments of a workgroup's chunk are neighbours in the stream, and so are consecutive blocks
@@ -609,7 +640,11 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
 
   if constexpr (kStage) {
     if (span > 0 && lane < nrows) {                   // (the wave barrier above orders the rounds' LDS writes before these reads)
-      const f32x4 lo = reinterpret_cast<const f32x4*>(stage)[2 * lane], hi = reinterpret_cast<const f32x4*>(stage)[2 * lane + 1];
+      // the lane's staging address is formed here, behind a fence: as a loop invariant it lived in a register from before the
+      // first chunk to this read, and six fields, at the 96 registers five wavefronts allow, spilled it to scratch
+      int sl = lane;
+      asm volatile("" : "+v"(sl));
+      const f32x4 lo = reinterpret_cast<const f32x4*>(stage)[2 * sl], hi = reinterpret_cast<const f32x4*>(stage)[2 * sl + 1];
       const float vals[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
       for (int f = 0; f < NF; ++f) out[(size_t)f * n_vox + r0 + lane] = vals[f];
@@ -698,7 +733,7 @@ int launch_rowwise(const char* fn, const StreamArgs& a, const ChunkGrid& cg, lon
                      ((size_t)(window_cap + 1) * WS * sizeof(float) + 15) / 16 * 16, a.stream, static_cast<const IndT*>(a.indptr),
                      a.dict_ptr, a.dict, cg, a.packed, (unsigned)(a.n_gates - 1), a.fill, window_cap, a.n_vox, a.out,
                      static_cast<const rg_u32x4*>(a.records), a.rec_ptr, a.w_base, a.lanes_hint, a.rec_order,
-                     (unsigned)chunk_count(cg), chunks_per_block, cols);
+                     (unsigned)chunk_count(cg), chunks_per_block, cols, a.row_end16);
   return rg::check_launch(fn);
 }
 

@@ -395,6 +395,7 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
                 else:
                     rec = rec[:n_units]
             compact.rec, compact.rec_ptr, compact.rec_order, compact.w_base = rec, rec_ptr, rec_order, w_base
+            compact.build_row_ends(indptr)
             logger.info(f"Packed pair stream: {16 * n_units / 1e6:.1f} MB ({16 * n_units / max(n_pairs, 1):.2f} bytes per pair; "
                         f"{100 * compact.dense_fraction():.2f} % of the pairs in 14-byte records)")
         if n_pairs <= _INT32_MAX:

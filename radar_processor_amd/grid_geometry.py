@@ -61,7 +61,8 @@ class CompactCSR:
     above 65536.  ``indptr`` and ``weights`` are shared with the standard CSR."""
 
     __slots__ = ("local_idx", "dict_ptr", "dict", "n_dict", "max_dict", "window_cap", "grid_shape", "chunk_pairs",
-                 "chunk_counts", "rec", "rec_ptr", "rec_order", "w_base", "_pack_tried", "_column_orders")
+                 "chunk_counts", "rec", "rec_ptr", "rec_order", "w_base", "_pack_tried", "_column_orders", "row_end16",
+                 "_row_ptr_bytes")
 
     def __init__(self, local_idx, dict_ptr, dict_, max_dict: int, window_cap: int, grid_shape, chunk_pairs=None,
                  chunk_counts=None):
@@ -82,10 +83,94 @@ class CompactCSR:
         self.w_base = 0                     # weight code = float32 bits - w_base
         self._pack_tried = False
         self._column_orders = {}            # z_pieces -> workgroup order of the column kernel (gridding.CsrGridder)
+        # row-end table of the row-wise kernel (build_row_ends): derived data, never stored in a sidecar
+        self.row_end16 = None               # int16 storage of uint16 [n_vox]: indptr[v + 1] - indptr[first row of v's segment]
+        self._row_ptr_bytes = {}            # bytes per row pointer -> row_pointer_bytes
 
     def nbytes(self) -> int:
         return sum(int(t.numel()) * t.element_size()
-                   for t in (self.local_idx, self.dict_ptr, self.dict, self.rec, self.rec_ptr) if t is not None)
+                   for t in (self.local_idx, self.dict_ptr, self.dict, self.rec, self.rec_ptr, self.row_end16) if t is not None)
+
+    @staticmethod
+    def rows_fit16(span):
+        """THE rule of the row-end table (csrc/rg_csr_compact_build.hip writes by it, csrc/rg_csr_rowwise.hpp reads by it): a
+        segment whose ``span`` -- its pairs, ``indptr[r0 + nrows] - indptr[r0]`` -- is at most ``RG_ROW_END16_MAX`` = 65534
+        keeps its row ends in 16 bits; a longer one holds ``RG_ROW_END16_WIDE`` = 0xFFFF there (which is why 65535 itself
+        does not fit) and reads the row pointers.  ``span``: an int, an array or a tensor."""
+        return span <= _native.RG_ROW_END16_MAX
+
+    @classmethod
+    def segment_spans(cls, indptr, grid_shape):
+        """Pairs of every segment: int64 ``[lines, nsx]`` (lines counted through all planes)."""
+        torch = _native.torch_mod()
+        nz, ny, nx = (int(v) for v in grid_shape)
+        nsx = cls.layout(grid_shape)[0]
+        dev = indptr.device
+        starts = torch.tensor(cls.segment_starts(nx), device=dev, dtype=torch.int64)
+        line0 = torch.arange(nz * ny, device=dev, dtype=torch.int64) * nx
+        edges = indptr[(line0[:, None] + starts[None, :]).reshape(-1)].to(torch.int64).view(nz * ny, nsx + 1)
+        return edges[:, 1:] - edges[:, :-1]
+
+    def build_row_ends(self, indptr) -> None:
+        """Build (once) the row-end table ``rg_csr_row_ends16`` writes from the grid's row pointers: two bytes per row that
+        the row-wise kernel reads instead of ``indptr[v]`` and ``indptr[v + 1]`` in every segment :meth:`rows_fit16` admits."""
+        if self.row_end16 is not None:
+            return
+        torch = _native.torch_mod()
+        lib = _native.load_library()
+        nz, ny, nx = self.grid_shape
+        n_vox = nz * ny * nx
+        dev = indptr.device
+        table = torch.empty(max(n_vox, 1), dtype=torch.int16, device=dev)[:n_vox]
+        with torch.cuda.device(dev):
+            _native.check(lib.rg_csr_row_ends16(_native.ptr(indptr), int(indptr.dtype == torch.int64), n_vox, nx, ny,
+                                                _native.ptr(table), _native.stream_ptr()), "rg_csr_row_ends16")
+        self.row_end16 = table
+        self._row_ptr_bytes = {}
+        st = self.row_end_stats(indptr)
+        logger.info(f"Row-end table: {2 * n_vox / 1e6:.1f} MB; {100 * st['empty_chunks']:.2f} % of the chunks hold no pair, "
+                    f"{100 * st['segments16']:.3f} % of the segments and {100 * st['voxels16']:.3f} % of the voxels keep "
+                    "16-bit row ends")
+
+    def _segment_rows_and_chunks(self, dev):
+        """``(rows per segment [nsx], chunk of every segment [lines, nsx])`` as int64 tensors."""
+        torch = _native.torch_mod()
+        nz, ny, nx = self.grid_shape
+        nsx, nyg, _ = self.layout(self.grid_shape)
+        starts = torch.tensor(self.segment_starts(nx), device=dev, dtype=torch.int64)
+        line = torch.arange(nz * ny, device=dev, dtype=torch.int64)
+        grp = (line // ny) * nyg + (line % ny) // _native.RG_COMPACT_LINES
+        return starts[1:] - starts[:-1], grp[:, None] * nsx + torch.arange(nsx, device=dev, dtype=torch.int64)[None, :]
+
+    def row_end_stats(self, indptr) -> dict:
+        """Shares the row-end table and the early exit rest on: ``empty_chunks`` (chunks without a pair), ``segments16`` and
+        ``voxels16`` (segments / voxels whose row ends fit 16 bits, by :meth:`rows_fit16`)."""
+        nz, ny, nx = self.grid_shape
+        fit = self.rows_fit16(self.segment_spans(indptr, self.grid_shape))
+        nrows, _ = self._segment_rows_and_chunks(indptr.device)
+        n_chunks = max(int(self.chunk_pairs.numel()), 1)
+        return {"empty_chunks": float(int((self.chunk_pairs == 0).sum()) / n_chunks),
+                "segments16": float(int(fit.sum()) / max(fit.numel(), 1)),
+                "voxels16": float(int((fit * nrows[None, :]).sum()) / max(nz * ny * nx, 1))}
+
+    def row_pointer_bytes(self, indptr, grid_mode: bool = True) -> int:
+        """Bytes of row pointers / row ends one launch of the row-wise kernel reads: 2 per row of a segment on the 16-bit path,
+        one row pointer (``nrows + 1`` of them) per segment that reads ``indptr`` -- every segment without a table --, and
+        nothing for the chunks the grid mode leaves early (no pair, dispatch order)."""
+        torch = _native.torch_mod()
+        ip = 8 if indptr.dtype == torch.int64 else 4
+        key = (ip, bool(grid_mode))
+        if key not in self._row_ptr_bytes:
+            spans = self.segment_spans(indptr, self.grid_shape)
+            nrows, chunk = self._segment_rows_and_chunks(indptr.device)
+            fit = self.rows_fit16(spans) if self.row_end16 is not None else torch.zeros_like(spans, dtype=torch.bool)
+            live = torch.ones_like(fit)
+            if grid_mode and self.rec_order == _native.RG_REC_ORDER_DISPATCH:
+                live = self.chunk_pairs.to(indptr.device)[chunk] > 0
+            rows16 = int(((fit & live) * nrows[None, :]).sum())
+            ptrs = int(((~fit & live) * (nrows[None, :] + 1)).sum())
+            self._row_ptr_bytes[key] = 2 * rows16 + ip * ptrs
+        return self._row_ptr_bytes[key]
 
     def ensure_packed(self, csr: "DeviceCSR") -> bool:
         """Build (once) the packed pair stream ``rg_csr_compact_apply_packed_f32`` reads: positions and weights of three
@@ -136,6 +221,7 @@ class CompactCSR:
         if int(err.item()):
             raise _native.NativeError(f"rg_csr_compact_pack_dense reported flag {int(err.item())}")
         self.rec, self.rec_ptr, self.w_base = rec, rec_ptr, w_base
+        self.build_row_ends(csr.indptr)
         logger.info(f"Packed pair stream: {rec.numel() * 4 / 1e6:.1f} MB ({16 * n_rec / csr.n_pairs:.2f} bytes per pair; "
                     f"{100 * self.dense_fraction():.2f} % of the pairs in 14-byte records)")
         return True
@@ -759,6 +845,7 @@ def load_device_layout(geometry: GridGeometry, filepath: str, device=None) -> bo
             compact.rec, compact.rec_ptr = up("rec"), up("rec_ptr")
             compact.rec_order, compact.w_base = int(data["rec_order"][0]), int(data["w_base"][0])
             compact._pack_tried = True
+            compact.build_row_ends(csr.indptr)          # derived data: rebuilt, not stored
     geometry._compact = (csr, compact)
     logger.info(f"Device layout attached from {filepath}: {compact.nbytes() / 1e6:.1f} MB")
     return True

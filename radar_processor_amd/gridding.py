@@ -161,10 +161,10 @@ class CsrGridder:
         nz, ny, nx = self.grid_shape
         if self.compact is not None and self.packed_stream and (self.tile in (0, 384) or self.tile >= 2000
                                                                 or csr.weights is None):
-            _native.check(self.lib.rg_csr_compact_apply_packed_f32(
+            _native.check(self.lib.rg_csr_compact_apply_packed_f32_ex(
                 *self._stream_args(fill_value), _native.ptr(out), self.window,
-                self.tile if (self.tile == 384 or self.tile >= 2000) else 0, _native.stream_ptr()),
-                "rg_csr_compact_apply_packed_f32")
+                self.tile if (self.tile == 384 or self.tile >= 2000) else 0, _native.ptr(self.compact.row_end16),
+                _native.stream_ptr()), "rg_csr_compact_apply_packed_f32")
             return
         if self.compact is not None:
             c = self.compact
@@ -181,7 +181,9 @@ class CsrGridder:
             _native.stream_ptr()), "rg_csr_apply_f32")
 
     def _stream_args(self, fill_value):
-        """The 17 leading arguments ``rg_csr_compact_apply_packed_f32``, ``_columns_f32`` and ``_planes_f32`` share."""
+        """The 17 leading arguments ``rg_csr_compact_apply_packed_f32``, ``_columns_f32`` and ``_planes_f32`` share with their
+        ``_ex`` variants, which :meth:`apply`, :meth:`apply_columns` and :meth:`apply_planes` call with the compact copy's
+        row-end table (a null pointer where it has none: every segment then reads the row pointers)."""
         csr, c = self.csr, self.compact
         nz, ny, nx = self.grid_shape
         return (_native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(c.rec), _native.ptr(c.rec_ptr), c.rec_order, c.w_base,
@@ -252,16 +254,16 @@ class CsrGridder:
         ws = None
         if col_max is not None and pieces > 1:
             ws = self._columns_workspace(int(self.lib.rg_csr_columns_workspace_bytes(ny, nx, self.n_fields, pieces)))
-        _native.check(self.lib.rg_csr_compact_apply_columns_f32(
+        _native.check(self.lib.rg_csr_compact_apply_columns_f32_ex(
             *self._stream_args(fill_value), _native.ptr(out),
             _native.ptr(level_planes), int(keep_lo), n_keep, _native.ptr(col_max), _native.ptr(col_arg), lo, hi, self.window,
             pieces, _native.ptr(order), _native.ptr(ws), 0 if ws is None else int(ws.numel()), int(lanes_hint),
-            _native.stream_ptr()), "rg_csr_compact_apply_columns_f32")
+            _native.ptr(self.compact.row_end16), _native.stream_ptr()), "rg_csr_compact_apply_columns_f32")
 
     def columns_bytes(self, store_grid: bool, n_keep: int = 0, colmax: bool = False) -> Optional[int]:
         """Bytes one ``apply_columns`` launch must move: the compact kernel's, minus the grids that are not stored, plus the
         kept planes and the (max, arg) planes."""
-        base = self.compact_bytes()
+        base = self.compact_bytes(grid_mode=False)
         if base is None:
             return None
         nz, ny, nx = self.grid_shape
@@ -298,16 +300,16 @@ class CsrGridder:
                                    sel_samples=_native.ptr(sel_samples))
         for k, sel in enumerate(sel_levels):
             req.sel_levels[k] = _native.ptr(sel)
-        _native.check(self.lib.rg_csr_compact_apply_planes_f32(
+        _native.check(self.lib.rg_csr_compact_apply_planes_f32_ex(
             *self._stream_args(fill_value), ctypes.byref(req), self.window, pieces,
-            _native.ptr(order), _native.ptr(ws), 0 if ws is None else int(ws.numel()), int(lanes_hint), _native.stream_ptr()),
-            "rg_csr_compact_apply_planes_f32")
+            _native.ptr(order), _native.ptr(ws), 0 if ws is None else int(ws.numel()), int(lanes_hint),
+            _native.ptr(self.compact.row_end16), _native.stream_ptr()), "rg_csr_compact_apply_planes_f32")
 
     def planes_bytes(self, store_grid: bool, n_keep: int = 0, colmax: bool = False, argmax: bool = False,
                      colmin: bool = False, colmean: bool = False, n_sel: int = 0) -> Optional[int]:
         """Bytes one ``apply_planes`` launch must move: the compact kernel's, minus the grids that are not stored, plus the
         kept, max / arg / min / mean planes, the selection words read and (at most) two samples per selection written."""
-        base = self.compact_bytes()
+        base = self.compact_bytes(grid_mode=False)
         if base is None:
             return None
         nz, ny, nx = self.grid_shape
@@ -366,19 +368,22 @@ class CsrGridder:
         logger.info(f"Record placement settled: probe ms {probe_ms}, kept allocation {kept}")
         return {"tries": tries, "probe_ms": probe_ms, "kept": kept}
 
-    def compact_bytes(self) -> Optional[int]:
+    def compact_bytes(self, grid_mode: bool = True) -> Optional[int]:
         """Bytes one launch of the compact kernel must move: the packed records as stored (or 16-bit position + weight per
-        pair), the dictionaries and their offsets, the row pointers, every field once, every grid once (``None`` without a
-        compact copy)."""
+        pair), the dictionaries and their offsets, the row pointers -- through the records: what the row-wise kernel reads of
+        them, ``CompactCSR.row_pointer_bytes`` (2-byte row ends where a segment's span fits, nothing for a chunk without a
+        pair) --, every field once, every grid once (``None`` without a compact copy)."""
         if self.compact is None:
             return None
         csr, c = self.csr, self.compact
         ip = 8 if csr.is_i64 else 4
         if self.packed_stream:      # the records' 16-byte units (14-byte records where the chunk is dense) + one offset per segment
             stream = 16 * int(c.rec.shape[0]) + 8 * int(c.rec_ptr.numel())
+            rows = c.row_pointer_bytes(csr.indptr, grid_mode)      # the column and planes modes leave no chunk early
         else:
             stream = 6 * csr.n_pairs
-        return (stream + 4 * c.n_dict + 8 * int(c.dict_ptr.numel()) + ip * (self.n_vox + 1)
+            rows = ip * (self.n_vox + 1)
+        return (stream + 4 * c.n_dict + 8 * int(c.dict_ptr.numel()) + rows
                 + self.n_fields * (5 * self.n_gates + 4 * self.n_vox))
 
 
