@@ -144,6 +144,13 @@ int rg_csr_apply_f32_ex(const void* indptr, int32_t indptr_is_i64, const int32_t
  * over levels z_lo..z_hi (inclusive, already clipped by the caller as products.py:484-485 does).
  * out_arg (optional, MAX/MIN only): first level attaining the extremum, -1 for an all-NaN column
  * (np.nanargmax order; build-defined).
+ * In level order: MAX / MIN start from the first non-NaN level and keep the held value when held >= v (MAX) / held <= v (MIN)
+ * or v is NaN, so that the first of equal values -- the sign of a zero included -- is the one stored; MEAN adds the float32
+ * values from 0.0f, a NaN counting as 0.0f, and stores (float)((double)sum / (double)count), NaN where count is 0.  The same
+ * bits on every launch path (16-byte or one-column accesses, level range split over lanes or not).
+ * An EMPTY window (z_lo > z_hi, both inside 0 .. nz-1) is accepted: every value is NaN and every out_arg -1, for all three
+ * ops, and nothing of the grid is read.  RG_EINVAL: a null grid / out, nz < 1, n_xy < 0, z_lo < 0, z_hi >= nz, an unknown op,
+ * out_arg with RG_COL_MEAN.  n_xy == 0 returns RG_OK.
  * ------------------------------------------------------------------------------------------------- */
 typedef enum rg_column_op { RG_COL_MAX = 0, RG_COL_MIN = 1, RG_COL_MEAN = 2 } rg_column_op;
 
@@ -480,7 +487,9 @@ int rg_plane_filter_f32(const float* src, const uint8_t* src_mask, int64_t n, co
  * out[0] = min and out[1] = max ignoring NaN, out[2] = how many such non-NaN pixels there are, out[3] = how many
  * pixels are not no-data (geotiff.py:111-125: np.nanmin / np.nanmax of valid_data and len(valid_data)); +inf / -inf /
  * 0 when there are none.  `data` is float32 or float64 (data_is_f64), `workspace` needs RG_MINMAX_WORKSPACE_BYTES,
- * out is double[4] on the device.
+ * out is double[4] on the device.  The comparison with `fill` is made in the data's dtype (float32 data: against (float)fill),
+ * so a NaN pixel is no-data only without a fill value; with one it is kept (out[3]) and not counted (out[2]).  n == 0 (data may
+ * then be NULL) yields +inf, -inf, 0, 0.
  *
  * rg_colormap_rgba: per pixel v = minimum(maximum(x, vmin), vmax); v -= vmin; v /= (vmax - vmin); v *= n_lut;
  * v == n_lut -> n_lut - 1; index = trunc(v), or n_lut (under) when v < 0, n_lut + 1 (over) when v >= n_lut,

@@ -294,7 +294,7 @@ extern "C" int rg_column_reduce_f32(const float* grid, int32_t nz, int64_t n_xy,
   RG_REQUIRE(!(op == RG_COL_MEAN && out_arg), RG_EINVAL, "rg_column_reduce_f32: no arg index for the mean");
   if (n_xy == 0) return RG_OK;
   hipStream_t s = (hipStream_t)stream;
-  // an empty window (z_lo > z_hi) yields all-NaN / -1, like np.nanmax over an empty... (callers clip first)
+  // an empty window (z_lo > z_hi) runs the sequential kernel over no level: all-NaN / -1 (radargrid_hip.h)
   switch (op) {
     case RG_COL_MAX: return launch_column<RG_COL_MAX>(grid, n_xy, z_lo, z_hi, out, out_arg, s);
     case RG_COL_MIN: return launch_column<RG_COL_MIN>(grid, n_xy, z_lo, z_hi, out, out_arg, s);
