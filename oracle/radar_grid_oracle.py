@@ -432,6 +432,103 @@ def csr_apply_rowwise_order(indptr, gate_indices, weights, fields, masks, grid_s
     return out.reshape(nf, nz, ny, nx)
 
 
+TILE_ORDER_DEFAULT = {n: 384 if n <= 4 else 128 for n in range(1, 9)}     # pairs per tile, by field count (rg_row_phase.hpp)
+TILE_ORDER_ACCEPTED = {1: (128, 256, 384, 512), 2: (128, 256, 384, 512), 3: (128, 192, 256, 320, 384), 4: (128, 256, 320, 384),
+                       5: (128,), 6: (128,), 7: (128,), 8: (128,)}
+
+
+def csr_apply_tile_order(indptr, gate_indices, weights, fields, masks, grid_shape, tile: int = 0, fill_value=np.nan,
+                         used: Optional[set] = None) -> np.ndarray:
+    """The masked weighted mean of :func:`csr_apply` (interpolate.py:69-104) with the float32 additions performed in exactly
+    the order ``radar_processor_amd/csrc/rg_row_phase.hpp`` documents for ``rg_csr_apply_f32`` and the tile kernels of
+    ``rg_csr_compact_apply_f32`` / ``rg_csr_compact_apply_packed_f32`` (tile = 384), so that these kernels can be checked BIT
+    FOR BIT on small cases:
+
+    * a grid line of nx rows is cut into ceil(nx / 64) balanced segments (the first nx % nsx hold one row more); a segment's
+      pairs are numbered from 0 and walked in tiles of T pairs, [0, T), [T, 2T), ...; T = ``tile``, one of
+      TILE_ORDER_ACCEPTED[fields], or TILE_ORDER_DEFAULT[fields] for ``tile`` = 0 (anything else is a ValueError);
+    * per tile starting at t, a row [rs, re) is active when it is not empty, re > t and rs < t + T; ra / rb = the first / last
+      active row, nact = rb - ra + 1 (the empty rows between them count), L = 2^floor(log2(64 // nact)) lanes per row;
+    * lane k of a row adds the elements a + k, a + k + 2L, ... of the row's part [a, b) of the tile into one float32 running
+      sum and a + k + L, a + k + 3L, ... into a second one, both from +0, ascending; the lane's value is first + second;
+      the terms of a pair are (float32(w * v), w), or (+0, +0) where the field's mask excludes the gate;
+    * the L lane values are folded by an xor butterfly (x[i] += x[i ^ 1], then ^ 2, ... ^ L/2) and lane 0's result is added
+      to the row's running (sum w*v, sum w), which starts at +0: once per tile the row touches, in tile order;
+    * value = float32(float64(sum w*v) / float64(sum w)) where sum w > 0, else ``fill_value``; every field by the same rule
+      with its own mask.
+
+    ``fields`` / ``masks``: sequences of F arrays [G] (mask True = excluded, None = nothing excluded).  An unmasked value is data
+    whatever its bits: ``rg_pack_fields_f32`` stores the one that carries RG_EXCLUDED_BITS as the canonical quiet NaN, so it
+    propagates as a NaN like any other.  ``used``: a set that receives every ``(T, L, rounds)`` met, rounds = the trips of the
+    kernel's loop over groups of 64 / L rows (always 1: 64 / L >= nact).  Returns float32 [F, nz, ny, nx].  Test
+    infrastructure like the rest of this module; rows are looped in Python: small cases only."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    gate_indices = np.asarray(gate_indices)
+    w_all = np.asarray(weights, dtype=np.float32)
+    nz, ny, nx = (int(v) for v in grid_shape)
+    nf = len(fields)
+    if not 1 <= nf <= 8:
+        raise ValueError(f"1..8 fields per pass, got {nf}")
+    T = int(tile) if tile else TILE_ORDER_DEFAULT[nf]
+    if T not in TILE_ORDER_ACCEPTED[nf]:
+        raise ValueError(f"tile {tile} is not one of {TILE_ORDER_ACCEPTED[nf]} (or 0) for {nf} fields")
+    vals = np.stack([np.asarray(f, dtype=np.float32) for f in fields])
+    excl = np.stack([np.zeros(vals.shape[1], dtype=bool) if m is None else np.asarray(m, dtype=bool) for m in masks])
+    out = np.full((nf, nz * ny * nx), fill_value, dtype=np.float32)
+    nsx = (nx + 63) // 64
+    seg_base, seg_extra = nx // nsx, nx % nsx
+    zero = np.float32(0.0)
+    for line in range(nz * ny):
+        x0 = 0
+        for sx in range(nsx):
+            nrows = seg_base + (1 if sx < seg_extra else 0)
+            r0 = line * nx + x0
+            x0 += nrows
+            seg_b = int(indptr[r0])
+            span = int(indptr[r0 + nrows]) - seg_b
+            if span == 0:
+                continue
+            rs = indptr[r0:r0 + nrows] - seg_b
+            re = indptr[r0 + 1:r0 + nrows + 1] - seg_b
+            g = gate_indices[seg_b:seg_b + span]
+            w = w_all[seg_b:seg_b + span]
+            good = ~excl[:, g]
+            with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+                prod = np.where(good, w[None, :] * vals[:, g], zero).astype(np.float32)    # float32 product, then the adds
+                wgt = np.where(good, w[None, :], zero).astype(np.float32)
+                terms = np.stack([prod, wgt])                                                # [2, F, span]
+                acc = np.zeros((2, nf, nrows), dtype=np.float32)                             # running (sum w*v, sum w)
+                for t in range(0, span, T):
+                    act = np.nonzero((re > rs) & (re > t) & (rs < t + T))[0]
+                    if act.size == 0:
+                        continue
+                    ra, rb = int(act[0]), int(act[-1])
+                    nact = rb - ra + 1
+                    lanes = 1 << ((64 // nact).bit_length() - 1)
+                    if used is not None:
+                        rpr = 64 // lanes
+                        used.add((T, lanes, (nact + rpr - 1) // rpr))
+                    for r in act:                           # an empty row inside [ra, rb] adds +0 to its sums: no change
+                        a, b = max(int(rs[r]), t), min(int(re[r]), t + T)
+                        i = np.arange(b - a)
+                        lane, trip = i % lanes, i // lanes
+                        which, col = trip & 1, (trip >> 1) + 1                               # column 0: the +0 both sums start from
+                        m = np.zeros((2, nf, 2, lanes, int(col[-1]) + 1), dtype=np.float32)
+                        m[:, :, which, lane, col] = terms[:, :, a:b]
+                        part = np.add.accumulate(m, axis=4, dtype=np.float32)[..., -1]       # strictly sequential per running sum
+                        x = (part[:, :, 0] + part[:, :, 1]).astype(np.float32)               # [2, F, lanes]
+                        step = 1
+                        while step < lanes:
+                            x = (x + x[:, :, np.arange(lanes) ^ step]).astype(np.float32)
+                            step <<= 1
+                        acc[:, :, r] = (acc[:, :, r] + x[:, :, 0]).astype(np.float32)
+                ok = acc[1] > 0
+                rows = np.broadcast_to(np.arange(r0, r0 + nrows), ok.shape)
+                fidx = np.broadcast_to(np.arange(nf)[:, None], ok.shape)
+                out[fidx[ok], rows[ok]] = (acc[0][ok].astype(np.float64) / acc[1][ok].astype(np.float64)).astype(np.float32)
+    return out.reshape(nf, nz, ny, nx)
+
+
 def merge_masks(field_data, extra_masks: Sequence[np.ndarray] = ()) -> Tuple[np.ndarray, np.ndarray]:
     """interpolate.py:59-64 -- OR the field's own mask with every filter's ``gate_excluded``."""
     mask = np.ma.getmaskarray(field_data).copy()

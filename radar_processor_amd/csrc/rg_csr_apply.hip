@@ -49,10 +49,11 @@ using f32x2 = float __attribute__((ext_vector_type(2)));
 
 // The kernel: the phases above, with
 //   * a DYNAMIC row phase: per tile the rows that actually touch it (a contiguous range, found with one ballot) share
-//     the 64 lanes -- L = the largest power of two <= 64 / rows (at least `stride`) lanes per row, split into stride
-//     field slots x L/stride interleaved element streams -- and the per-row sums live in a small LDS array instead of
-//     per-pass registers, so lane utilisation does not depend on how many rows a tile holds and neither registers nor
-//     code grow with the field count;
+//     the 64 lanes -- L = the largest power of two <= 64 / rows lanes per row (rows = the span from the first to the last
+//     such row, empty rows in between included; no floor), every lane a "whole-entry" lane that sums its strided share of
+//     the row's pairs for ALL fields at once; lane split, order of the adds and fold are rg_row_phase.hpp's and are
+//     restated by oracle.csr_apply_tile_order -- and the per-row sums live in a small LDS array instead of per-pass
+//     registers, so lane utilisation does not depend on how many rows a tile holds;
 //   * BUFFER loads: the CSR tile and the packed fields are read through buffer resources, whose hardware range check
 //     returns 0 for anything past the end of the array.  That removes every address clamp and all 64-bit address
 //     arithmetic from the loop: a tile's resource is rebuilt in SGPRs (base + t, remaining bytes), the lane offset

@@ -13,13 +13,15 @@
 //                                                  pair's entry is one 8 / 16 / 32-byte vector access at a lane stride
 //                                                  of the same size (conflict-free); the row-phase lanes do the mask
 //                                                  test and the product
-// Lane split: L = 2^lg lanes per row, the largest power of two <= 64 / (rows touching the tile); lane k of a row sums
+// Lane split: L = 2^lg lanes per row, the largest power of two <= 64 / nact, nact = the span from the first to the last
+// row touching the tile (the empty rows between them count, they get lanes too); lane k of a row sums
 // pairs k, k+L, k+2L, ... of the row's part of the tile with two independent accumulators per value (elements k, k+2L,
 // ... and k+L, k+3L, ...), ALL F fields at once ("whole-entry" lanes: one vector read feeds 2F additions, where one
 // lane per field slot would spend a read and a loop trip per single addition pair).
 // Fold: xor-butterfly over the L lanes.  Steps 1..8 run on the DPP cross-lane path (quad_perm / row_half_mirror /
 // row_mirror: after the earlier steps all lanes of a quad / half row hold identical bits, so a mirror delivers exactly
 // the xor partner's value); 16 and 32 -- at most two rows in a tile -- go through ds_bpermute.
+// oracle.csr_apply_tile_order restates this order in NumPy; tests/test_gpu_tile_order.py holds both kernels to it bit for bit.
 #pragma once
 
 #include "rg_common.hpp"
