@@ -306,6 +306,42 @@ def rim_cloud(grid_shape, grid_limits, min_radius: float, beam_factor: float, se
                     np.array(lab, dtype="<U1"), misses)
 
 
+def point_cloud(xs, ys, zc, min_radius: float, beam_factor: float, seed: int,
+                per_sample: Sequence[int] = (0, 1, 1, 2, 2, 3, 3), cases: Sequence[str] = CASES, direction=None) -> RimCloud:
+    """Plant gates on the rims of the samples ``(xs[i], ys[i], zc[k])`` of a section: points anywhere, no lattice.
+
+    As :func:`rim_cloud` per sample: ``rng.choice(per_sample)`` gates, each of a case drawn from ``cases`` (a sample where
+    a case cannot be planted gets another one).  ``direction``: None, one ``'out:<signs>'`` spec for every point, or a
+    sequence with one spec (or None) per point.  ``voxel`` of the result is the sample's row ``k * len(xs) + i``, the row
+    order of a section."""
+    rng = np.random.default_rng(seed)
+    xs = np.asarray(xs, dtype=np.float32)
+    ys = np.asarray(ys, dtype=np.float32)
+    zc = np.asarray(zc, dtype=np.float32)
+    n = xs.shape[0]
+    per_point = [direction] * n if direction is None or isinstance(direction, str) else list(direction)
+    if len(per_point) != n:
+        raise ValueError(f"{len(per_point)} directions for {n} points")
+    pts, vox, lab = [], [], []
+    misses = 0
+    for k in range(zc.shape[0]):
+        for i in range(n):
+            rim = voxel_rim(xs[i], ys[i], zc[k], min_radius, beam_factor)
+            for _ in range(int(rng.choice(per_sample))):
+                want = [str(c) for c in rng.permutation(list(cases))]
+                for case in want:
+                    g = plant(rim, case, rng, direction=per_point[i])
+                    if g is not None:
+                        break
+                else:
+                    misses += 1
+                    continue
+                pts.append(g); vox.append(k * n + i); lab.append(case)
+    p = np.array(pts, dtype=np.float32).reshape(-1, 3)
+    return RimCloud(p[:, 0].copy(), p[:, 1].copy(), p[:, 2].copy(), np.array(vox, dtype=np.int64),
+                    np.array(lab, dtype="<U1"), misses)
+
+
 def vertical_cloud(grid_shape, grid_limits, min_radius: float, beam_factor: float, voxels: Sequence[int]) -> RimCloud:
     """For voxels on the radar's vertical (x = y = 0): the innermost gate inside and the outermost gate outside the rim,
     straight above and straight below (the tightest case of the per-level lists' reach bound)."""

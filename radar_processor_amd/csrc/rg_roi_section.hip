@@ -8,10 +8,12 @@
 //     no coordinate table has ends to read -- widened by the block's largest radius of influence.  Nothing assumes that
 //     consecutive points are close: a block of scattered points has a large box and streams many candidates, and still
 //     finds exactly its neighbours;
-//   * candidate stage (lanes = 64 candidates per step): a float32 lower bound of the distance to the nearest of four
-//     sub-boxes of kPts / 4 points each -- with 4 points per block, to the nearest POINT -- against the block's largest
-//     radius, inflated by 2e-6.  A path runs at any angle through the cells, so the block's box is mostly far from it; the
-//     sub-boxes follow it;
+//   * candidate stage (lanes = 64 candidates per step): the float32 distance to the nearest of four sub-boxes of kPts / 4
+//     points each -- with 4 points per block, to the nearest POINT -- against band_hi of the block's largest radius.  With
+//     one point per sub-box this is in_roi's float32 d2 with the squares added in another order, so it is no lower bound
+//     to the last bit: the band's 2e-6 (five times the error of either sum) is what keeps every gate the dense stage
+//     would admit.  A path runs at any angle through the cells, so the block's box is mostly far from it; the sub-boxes
+//     follow it;
 //   * dense stage: K2's, 16 queued records per step, through the same functions of rg_roi_search.hpp (in_roi: float32 d2
 //     where it is clear of the rim band, the reference's float64 `d2 < r2` inside it; grid_weight / accumulate: float32
 //     weights within K2's budgets; emit_hit: count and fill classify hits with the same code, fill writes the float64-exact
@@ -28,9 +30,13 @@
 // and 0.035 ms (four times fewer dense steps for the heavy rows, four times as many wavefronts, a prefilter that is exact
 // per point).  The lattice pass over the same structure (rg_roi_grid_f32) takes 10.9 ms.
 //
-// A point with a non-finite coordinate has no neighbours (its samples are filled, its rows empty): the cell of a NaN is
-// not defined.  Points outside the rectangle the search structure was built for read clamped cells: memory-safe, but their
-// neighbours are not guaranteed -- the Python surface refuses both before a launch.
+// A point with a non-finite coordinate -- NaN, +Inf or -Inf in x, in y or in both -- has no neighbours (its samples are
+// filled, its rows counted as 0 and never written): the cell of a NaN is not defined, and with beam_factor > 0 an infinite
+// coordinate alone would make the radius of influence infinite and every candidate a neighbour, so BOTH coordinates are
+// tested.  Such a point is a dead lane: it adds nothing to the block's radius, sub-boxes or cell box, and a block of dead
+// points only streams no cells at all.  Points outside the rectangle the search structure was built for read clamped cells:
+// memory-safe, but their neighbours are not guaranteed -- the Python surface refuses both before a launch.
+// (tests/test_gpu_section_rim.py calls the C entry points with dead points in every mix per block.)
 //
 // Several radars on one section (rg_roi_section_mosaic_f32, MOSAIC): the block visits the radars of the table in order.  For
 // each it rebuilds its samples from that radar's own xs / ys / zc (the points in that radar's frame: the distance to the
