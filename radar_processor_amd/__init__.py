@@ -20,7 +20,8 @@ from .grid_products import (EARTH_RADIUS, EFFECTIVE_RADIUS_FACTOR, column_argmax
                             column_min, column_profile, compute_beam_height, compute_beam_height_flat,
                             compute_beam_height_simple, constant_altitude_ppi, constant_elevation_ppi, echo_base, echo_top,
                             get_beam_height_difference, get_elevation_from_z_level, vertically_integrated_liquid)
-from .gridding import PlaneProducts, apply_geometry, apply_geometry_multi, grid_fields_device, grid_products_device
+from .gridding import PlaneProducts, apply_geometry, apply_geometry_multi, grid_fields_device
+from .plane_products import grid_products_device
 from .roi_grid import roi_grid_fields_device
 from .mosaic import (MOSAIC_COMBINES, NO_RADAR, MosaicSearch, apply_mosaic, apply_mosaic_multi, compute_mosaic_geometry,
                      compute_mosaic_section_geometry, mosaic_fields_device, mosaic_limits, mosaic_section_fields_device,

@@ -20,6 +20,10 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 
+from .gridding import PlaneProducts, grid_fields_device, volumes_per_pass_cap
+from .plane_products import ProductPlan, grid_products_device
+from .roi_grid import roi_grid_fields_device
+
 
 def _dist():
     import torch.distributed as dist
@@ -137,7 +141,6 @@ class VolumeBatch:
     def volumes_per_pass(self) -> int:
         """Volumes one pass fuses (decided on first use: the CSR path asks the geometry's device copy)."""
         if self._cap is None:
-            from .gridding import volumes_per_pass_cap
             self._cap = volumes_per_pass_cap(self.geometry, self.dev)
         return max(1, self._cap // len(self.field_names))
 
@@ -195,7 +198,8 @@ class VolumeBatch:
         given, so that only 2-D planes outlive the pass.  ``products`` may also be a :class:`gridding.PlaneProducts`
         (column maximum / argmax / minimum / mean, CAPPIs, constant-elevation PPIs): the result is then ``{index: [one dict of planes per field]}`` and, on the CSR
         path of a large geometry and on request, the pass runs the gridding kernel's column mode with its products epilogue -- the 3-D grids
-        are neither written nor read back (``gridding.grid_products_device``).  ``volumes`` is indexed by the GLOBAL volume number; only this
+        are neither written nor read back (``plane_products.grid_products_device``); the CSR-free path reduces its grids through
+        ``plane_products.ProductPlan``, resolved once per call.  ``volumes`` is indexed by the GLOBAL volume number; only this
         rank's entries (``shard_indices``) are touched, the others may be ``None``.  ``events``: optional list that
         receives one ``(start, end)`` pair of stream events per gridding pass (mask fold + gridding kernel), for
         callers that time the kernel itself (``bench.py``).
@@ -204,42 +208,16 @@ class VolumeBatch:
         fused launch: the epilogues do not compute those planes, so on a CSR geometry every group is gridded, then reduced
         (``grid_products_device`` decides), as the CSR-free path always does."""
         import torch
-        from .gridding import PlaneProducts, grid_fields_device, grid_products_device, profile_planes, reduce_planes
-        from .roi_grid import roi_grid_fields_device
-        plane_spec = products if isinstance(products, PlaneProducts) else None
-        if plane_spec is not None and self.fused:      # the CSR-free gridder has no epilogue: reduce its grids as usual
-            from . import grid_products as gp
-            geom_like = self.geometry
-            levels = {}
-
-            def products(g, _spec=plane_spec):         # noqa: F811 -- the reducer form of the same request
-                recs = []
-                if _spec.profile and "zl" not in levels:       # the level heights: one upload per grid_shard call
-                    levels["zl"] = gp.profile_levels_device(geom_like, int(g.shape[1]), g.device)
-                for k in range(g.shape[0]):
-                    rec = {}
-                    lo, hi = gp._level_window(int(g.shape[1]), *_spec.window, geom_like)
-                    if _spec.colmax:
-                        got = gp._column("max", g[k], lo, hi, None, None, None, want_arg=_spec.argmax)
-                        if _spec.argmax:
-                            rec["colmax"], rec["argmax"] = got
-                        else:
-                            rec["colmax"] = got
-                    reduce_planes(_spec, g[k], geom_like, lo, hi, rec)           # column min / mean, PPIs
-                    if _spec.cappi:
-                        rec["cappi"] = {alt: gp.constant_altitude_ppi(g[k], geom_like, alt, _spec.interpolation)
-                                        for alt in _spec.cappi}
-                    if "ppi" in rec:
-                        rec["ppi"] = rec.pop("ppi")                             # (key order of grid_products_device)
-                    recs.append(profile_planes(_spec, g[k], geom_like, lo, hi, rec, levels.get("zl")))   # echo top / base, VIL
-                return recs
-            plane_spec = None
         mine = shard_indices(len(volumes), rank, world_size)
         out: Dict[int, object] = {}
         n_f = len(self.field_names)
         groups = [mine[g0:g0 + self.volumes_per_pass] for g0 in range(0, len(mine), self.volumes_per_pass)]
         if not groups:
             return out
+        plane_spec = products if isinstance(products, PlaneProducts) else None
+        reduce = products
+        if plane_spec is not None:      # the CSR-free gridder has no epilogue: its grids are reduced; the CSR path returns planes
+            reduce = ProductPlan(plane_spec, self.geometry).planes_of_grids if self.fused else None
         with torch.cuda.device(self.dev):
             compute = torch.cuda.current_stream()
             copy_stream = self._copy_stream = getattr(self, "_copy_stream", None) or torch.cuda.Stream()
@@ -271,5 +249,5 @@ class VolumeBatch:
                     out[b] = planes[i * n_f:(i + 1) * n_f]
                     continue
                 g = grids[i * n_f:(i + 1) * n_f]
-                out[b] = products(g) if products is not None else g
+                out[b] = reduce(g) if reduce is not None else g
         return out

@@ -387,8 +387,6 @@ class CsrGridder:
                 + self.n_fields * (5 * self.n_gates + 4 * self.n_vox))
 
 
-_COLUMNS_FUSE_MIN_FIELDS = 5        # grid_products_device(fused=None): field-volumes per pass from which the products epilogue pays
-                                    # in TIME -- more than a pass can hold: never by default (see grid_products_device)
 _COLUMNS_MIN_WORKGROUPS = 8192      # column kernel: cut columns into level pieces until the launch has about this many workgroups
 _PIPELINE_TILES = (128, 192, 256, 320, 384, 512)   # pairs per pipeline step the tile kernels accept (0 = their default)
 _COMPACT_MIN_PAIRS = 50_000_000     # below this a pass takes well under a millisecond either way
@@ -573,232 +571,6 @@ class PlaneProducts:
         """Products the column mode's epilogue (``rg_csr_compact_apply_columns_f32``) does not compute: the fused pass runs
         ``rg_csr_compact_apply_planes_f32`` instead."""
         return self.colmin or self.colmean or bool(self.ppi)
-
-
-def reduce_planes(products: PlaneProducts, grid, geometry, lo: int, hi: int, rec: dict) -> dict:
-    """The separate-kernel route of the products ``rg_csr_compact_apply_columns_f32`` does not compute, for one stored grid
-    ``[nz, ny, nx]`` (device): ``colmin`` / ``colmean`` over levels ``lo .. hi`` and ``ppi`` -- added to ``rec``."""
-    from . import grid_products as gp
-    if products.colmin:
-        rec["colmin"] = gp._column("min", grid, lo, hi, None, None, None)
-    if products.colmean:
-        rec["colmean"] = gp._column("mean", grid, lo, hi, None, None, None)
-    if products.ppi:
-        rec["ppi"] = {e: gp.constant_elevation_ppi(grid, geometry, e, products.ppi_interpolation, products.earth_curvature,
-                                                   products.ke) for e in products.ppi}
-    return rec
-
-
-def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Optional[Sequence] = None, shared_mask=None,
-                         products: Optional[PlaneProducts] = None, fill_value: float = np.nan, fused: Optional[bool] = None):
-    """Grid device-resident fields and return ONLY 2-D products: a list with one ``dict`` per field --
-    ``{"colmax": [ny, nx] float32, "argmax": [ny, nx] int32, "colmin": [ny, nx] float32, "colmean": [ny, nx] float32,
-    "cappi": {altitude: [ny, nx] float32}, "ppi": {angle: [ny, nx] float64 / float32}}`` (keys present as requested by
-    ``products``).  The planes are bit-identical to ``column_argmax`` / ``column_min`` / ``column_mean`` /
-    ``constant_altitude_ppi`` / ``constant_elevation_ppi`` applied to the grid ``grid_fields_device`` returns for the same
-    pass.
-
-    ``fused=True``: on large geometries (packed records present) every group of up to four field-volumes runs as ONE launch
-    of the row-wise kernel in column mode with its products epilogue -- no 3-D grid is written or read back (640 MB each
-    way per field on the bench grid), so a pass needs no grid memory at all; it takes about as long as gridding + reducing
-    separately (measured, see below).  COLMAX / argmax / CAPPI alone run ``rg_csr_compact_apply_columns_f32``; a request
-    with a column minimum, mean or PPI runs ``rg_csr_compact_apply_planes_f32`` (a mean keeps each column in one workgroup;
-    more than ``RG_MAX_SEL_PLANES`` PPIs take further launches of it, each gridding the fields again).  Default
-    (``fused=None``) and ``fused=False``: grid as usual, reduce with the separate kernels.
-
-    A request with a column profile product (``echo_top`` / ``echo_base`` / ``vil``) adds ``"echo_top": {T: plane}``,
-    ``"echo_base": {T: plane}``, ``"vil": plane`` -- what ``column_profile`` returns for the same grid -- and always grids,
-    then reduces; ``fused=True`` with one is a ``ValueError``."""
-    from . import grid_products as gp
-    torch = _native.torch_mod()
-    products = products if products is not None else PlaneProducts()
-    if fused is None:
-        fused = products.fused
-    if fused and products.profile:
-        raise ValueError("fused=True cannot produce echo_top / echo_base / vil (grid, then reduce: leave fused unset)")
-    n_fields = len(fields)
-    if n_fields == 0:
-        raise ValueError("no fields to grid")
-    dev = fields[0].device
-    if dev.type != "cuda":
-        raise _native.NativeUnavailable("grid_products_device needs device-resident (cuda) tensors")
-    if masks is None:
-        masks = [None] * n_fields
-    nz, ny, nx = (int(s) for s in geometry.grid_shape)
-    lo, hi = gp._level_window(nz, *products.window, geometry)
-    if (products.columns or products.profile) and lo > hi:
-        raise ValueError(f"empty level window [{lo}, {hi}]")
-    if products.profile:
-        gp.profile_levels(geometry, nz)            # refused here, before any device work
-    levels = None                                  # the profile products' level heights: uploaded once, below
-    plans = cappi_plans(products, geometry, nz)
-    needed = sorted({k for plan in plans.values() if plan[0] != "outside" for k in ((plan[1], plan[1] + 1) if plan[0] == "blend"
-                                                                                    else (plan[1],))})
-    keep_lo, n_keep = (needed[0], needed[-1] - needed[0] + 1) if needed else (0, 0)
-    angles = list(dict.fromkeys(products.ppi))
-    n_gates = int(fields[0].numel())
-    results = []
-    with torch.cuda.device(dev):
-        use_compact = _use_compact(geometry, dev)
-        per_pass = _fields_per_pass(geometry, dev, use_compact)
-        if fused:                                # the products epilogue (column mode of the row-wise kernel) takes 1-4 fields
-            per_pass = min(per_pass, 4)
-        for f0 in range(0, n_fields, per_pass):
-            f1 = min(n_fields, f0 + per_pass)
-            nf = f1 - f0
-            gridder = _cached_gridder(geometry, n_gates, nf, dev, compact=use_compact)
-            gridder.pack(fields[f0:f1], masks[f0:f1], shared_mask)
-            # measured (profiles/r04_columns_variants_*.json, r04_nf4_lds_rowsums.json): walking columns costs what the store it
-            # saves costs -- 8.2 vs 8.1 ms for one field, 10.7 vs 10.5 for three, 11.4 vs 11.2 for four on the bench grid --
-            # so the epilogue is the MEMORY-saving choice (no F x 640 MB of grid) and is taken on request, not by default
-            run_fused = (gridder.has_columns_kernel and not products.profile      # the profile products need the stored grid
-                         and (nf >= _COLUMNS_FUSE_MIN_FIELDS if fused is None else bool(fused)))
-            fused_planes = {}
-            if run_fused:
-                cmax = torch.empty((nf, ny, nx), dtype=torch.float32, device=dev) if products.colmax else None
-                carg = torch.empty((nf, ny, nx), dtype=torch.int32, device=dev) if products.argmax else None
-                planes = torch.empty((nf, n_keep, ny, nx), dtype=torch.float32, device=dev) if n_keep else None
-                if products.needs_planes_mode:
-                    fused_planes = _fused_planes_pass(gridder, products, geometry, fill_value, planes, keep_lo, cmax, carg,
-                                                      (lo, hi), angles)
-                elif cmax is None and planes is None:      # nothing but out-of-range CAPPIs
-                    pass
-                else:
-                    gridder.apply_columns(out=None, fill_value=fill_value, level_planes=planes, keep_lo=keep_lo, col_max=cmax,
-                                          col_arg=carg, col_window=(lo, hi))
-                level = (lambda k, z: planes[k, z - keep_lo])
-            else:
-                grids = torch.empty((nf, nz, ny, nx), dtype=torch.float32, device=dev)
-                gridder.apply(grids.view(nf, -1), fill_value)
-            for k in range(nf):
-                if not run_fused:
-                    if products.profile and levels is None:
-                        levels = gp.profile_levels_device(geometry, nz, dev)
-                    results.append(products_of_grid(products, grids[k], geometry, lo, hi, plans, levels))
-                    continue
-                rec = {}
-                if products.colmax:
-                    rec["colmax"] = cmax[k]
-                    if products.argmax:
-                        rec["argmax"] = carg[k]
-                for key in ("colmin", "colmean"):
-                    if key in fused_planes:
-                        rec[key] = fused_planes[key][k]
-                if products.cappi:
-                    rec["cappi"] = _cappi_planes(plans, lambda z: level(k, z), ny, nx, dev)
-                if products.ppi:
-                    rec["ppi"] = fused_planes["ppi"][k]
-                results.append(rec)
-    return results
-
-
-def cappi_plans(products: PlaneProducts, geometry, nz: int) -> dict:
-    """``{altitude: cappi_plan}`` of a products request, warning about altitudes outside the grid as
-    ``constant_altitude_ppi`` does.  ``geometry``: anything with the grid's ``grid_limits``."""
-    from . import grid_products as gp
-    plans = {alt: gp.cappi_plan(geometry.grid_limits[0], nz, alt, products.interpolation) for alt in products.cappi}
-    for alt, plan in plans.items():
-        if plan[0] == "outside":
-            z_min, z_max = geometry.grid_limits[0]
-            gp.logger.warning(f"Altitude {alt}m is outside grid range [{z_min}, {z_max}]m")
-    return plans
-
-
-def _cappi_planes(plans: dict, level, ny: int, nx: int, dev) -> dict:
-    """The CAPPI planes of ``plans``; ``level(z)`` returns grid level ``z`` as a ``[ny, nx]`` plane (levels ``z`` and
-    ``z + 1`` adjacent in one buffer)."""
-    torch = _native.torch_mod()
-    lib = _native.load_library()
-    out = {}
-    for alt, plan in plans.items():
-        if plan[0] == "outside":
-            out[alt] = torch.full((ny, nx), float("nan"), dtype=torch.float32, device=dev)
-        elif plan[0] == "level":
-            out[alt] = level(plan[1])
-        else:
-            plane = torch.empty((ny, nx), dtype=torch.float32, device=dev)
-            _native.check(lib.rg_cappi_lerp_f32(_native.ptr(level(plan[1])), ny * nx, 0, float(np.float32(plan[2])),
-                                                float(np.float32(plan[3])), _native.ptr(plane), _native.stream_ptr()),
-                          "rg_cappi_lerp_f32")
-            out[alt] = plane
-    return out
-
-
-def products_of_grid(products: PlaneProducts, grid, geometry, lo: int, hi: int, plans: dict, levels=None) -> dict:
-    """The planes ``grid_products_device`` returns for one field, from its stored grid ``[nz, ny, nx]`` (device) through the
-    separate kernels: ``column_argmax`` / ``column_max`` over levels ``lo .. hi``, ``reduce_planes``, the CAPPIs of ``plans``
-    (``cappi_plans``), and the column profile products over the same levels (``profile_planes``).  ``geometry``: anything
-    with the grid's ``grid_shape`` / ``grid_limits``.  ``levels``: ``profile_levels_device`` of the geometry, from a caller
-    that reduces several grids (``None``: uploaded here)."""
-    from . import grid_products as gp
-    _, ny, nx = (int(s) for s in grid.shape)
-    rec = {}
-    if products.colmax:
-        got = gp._column("max", grid, lo, hi, None, None, None, want_arg=products.argmax)
-        rec["colmax"], rec["argmax"] = got if products.argmax else (got, None)
-        if not products.argmax:
-            del rec["argmax"]
-    reduce_planes(products, grid, geometry, lo, hi, rec)
-    ppi_recs = rec.pop("ppi", None)
-    if products.cappi:
-        rec["cappi"] = _cappi_planes(plans, lambda z: grid[z], ny, nx, grid.device)
-    if products.ppi:
-        rec["ppi"] = ppi_recs
-    return profile_planes(products, grid, geometry, lo, hi, rec, levels)
-
-
-def profile_planes(products: PlaneProducts, grid, geometry, lo: int, hi: int, rec: dict, levels=None) -> dict:
-    """The column profile products of a request for one stored grid ``[nz, ny, nx]`` (device), levels ``lo .. hi``:
-    ``echo_top`` / ``echo_base`` / ``vil`` as ``grid_products.column_profile`` returns them (one ``rg_column_profile_f32``
-    launch per four distinct thresholds) -- added to ``rec``; nothing when the request holds none.  ``levels``: the level
-    heights already on the grid's device (``grid_products.profile_levels_device``), or ``None`` to upload them here."""
-    from . import grid_products as gp
-    if products.profile:
-        if lo > hi:
-            raise ValueError(f"empty level window [{lo}, {hi}]")
-        if levels is None:
-            levels = gp.profile_levels_device(geometry, int(grid.shape[0]), grid.device)
-        rec.update(gp._profile_planes(grid, levels, lo, hi, products.echo_top,
-                                      products.echo_base, products.vil, products.vil_max_dbz, products.profile_interpolation))
-    return rec
-
-
-def _fused_planes_pass(gridder: CsrGridder, products: PlaneProducts, geometry: GridGeometry, fill_value, planes, keep_lo,
-                       cmax, carg, window, angles) -> dict:
-    """The planes-mode launches of one field group (``grid_products_device``): the first computes every column product, the
-    kept levels and the samples of the first ``RG_MAX_SEL_PLANES`` PPIs; any further PPIs take one more launch per
-    ``RG_MAX_SEL_PLANES``.  Returns ``{"colmin": [F, ny, nx], "colmean": [F, ny, nx], "ppi": [one {angle: plane} per field]}``
-    (keys as requested)."""
-    from . import grid_products as gp
-    torch = _native.torch_mod()
-    dev = gridder.dev
-    nf = gridder.n_fields
-    _, ny, nx = gridder.grid_shape
-    got = {}
-    cmin = torch.empty((nf, ny, nx), dtype=torch.float32, device=dev) if products.colmin else None
-    cmean = torch.empty((nf, ny, nx), dtype=torch.float32, device=dev) if products.colmean else None
-    ppi_plans = [gp.ppi_plan(geometry, e, products.ppi_interpolation, products.earth_curvature, products.ke, dev)
-                 for e in angles]
-    cap = _native.RG_MAX_SEL_PLANES
-    groups = [list(range(g0, min(len(angles), g0 + cap))) for g0 in range(0, len(angles), cap)] or [[]]
-    per_field = [{} for _ in range(nf)]
-    for gi, group in enumerate(groups):
-        first = gi == 0
-        samples = torch.empty((nf, len(group), 2, ny, nx), dtype=torch.float32, device=dev) if group else None
-        gridder.apply_planes(out=None, fill_value=fill_value, level_planes=planes if first else None, keep_lo=keep_lo,
-                             col_max=cmax if first else None, col_arg=carg if first else None,
-                             col_min=cmin if first else None, col_mean=cmean if first else None, col_window=window,
-                             sel_levels=[ppi_plans[i][0] for i in group], sel_samples=samples)
-        for j, i in enumerate(group):
-            for k in range(nf):
-                per_field[k][angles[i]] = gp.ppi_finish(ppi_plans[i], samples[k, j], products.ppi_interpolation)
-    if cmin is not None:
-        got["colmin"] = cmin
-    if cmean is not None:
-        got["colmean"] = cmean
-    if products.ppi:
-        got["ppi"] = per_field
-    return got
 
 
 def _to_host(t) -> np.ndarray:

@@ -40,7 +40,8 @@ import numpy as np
 from . import _native
 from .geometry_builder import _INT32_MAX, WEIGHTINGS, RoiSearch, csr_from_counts
 from .grid_geometry import GridGeometry
-from .gridding import _stride_for
+from .gridding import _coerce_filters, _host_field, _stride_for, _to_host, grid_fields_device
+from .plane_products import ProductPlan, grid_products_device
 from .roi_grid import pack_and_grid
 from .section import _check_points, _cumulative_distance, section_path, section_rectangle
 
@@ -254,7 +255,6 @@ def _mosaic_layout(geometry) -> np.ndarray:
 
 def _host_concat(offsets, fields, filters, what: str):
     """Per-radar masked fields (+ per-radar GateFilter lists) -> concatenated float32 values and uint8 exclusion mask."""
-    from .gridding import _coerce_filters, _host_field
     n_radars = len(offsets) - 1
     if len(fields) != n_radars:
         raise ValueError(f"{what}: expected one field per radar ({n_radars}), got {len(fields)}")
@@ -281,7 +281,6 @@ def apply_mosaic(geometry: GridGeometry, fields: Sequence, additional_filters: O
     offsets = _mosaic_layout(geometry)
     values, mask = _host_concat(offsets, list(fields), additional_filters, "apply_mosaic")
     _check_gather(int(offsets[-1]), 1)
-    from .gridding import _to_host, grid_fields_device
     torch = _native.torch_mod()
     dev = _native.device()
     f_t = torch.from_numpy(values).to(dev)
@@ -303,7 +302,6 @@ def apply_mosaic_multi(geometry: GridGeometry, fields: Dict[str, Sequence],
         return {}
     host = [_host_concat(offsets, list(fields[n]), additional_filters.get(n), f"apply_mosaic_multi[{n}]") for n in names]
     _check_gather(int(offsets[-1]), len(names))
-    from .gridding import _to_host, grid_fields_device
     torch = _native.torch_mod()
     dev = _native.device()
     f_ts = [torch.from_numpy(v).to(dev) for v, _ in host]
@@ -536,7 +534,6 @@ def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Seq
     with torch.cuda.device(dev):
         cat_fields, cat_field_masks, cat_shared = _concat_on_device(fields, masks, shared_masks, counts, n_fields, torch, dev)
         if is_geometry:
-            from .gridding import grid_fields_device, grid_products_device
             if products is not None:
                 return grid_products_device(target, cat_fields, cat_field_masks, cat_shared, products=products,
                                             fill_value=fill_value)
@@ -544,7 +541,7 @@ def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Seq
         grids, radar = _search_grid(target, sel, counts, cat_fields, cat_field_masks, cat_shared, weighting, fill_value,
                                     dev, combine, return_radar)
     if products is not None:
-        grids = _products_of_grids(products, grids, target)
+        grids = ProductPlan(products, target).planes_of_grids(grids)
     return (grids, radar) if return_radar else grids
 
 
@@ -638,22 +635,6 @@ def _search_grid(search: MosaicSearch, sel, counts, fields, masks, shared_mask, 
     if radar is not None:
         radar = _radar_indices(radar, sel, torch).view(len(fields), nz, ny, nx)
     return grids, radar
-
-
-def _products_of_grids(products, grids, spec) -> List[dict]:
-    """The planes ``grid_products_device`` returns, from stored grids ``[F, nz, ny, nx]`` through the separate kernels
-    (``gridding.products_of_grid``; ``spec``: anything with the shared ``grid_shape`` / ``grid_limits``)."""
-    from . import grid_products as gp
-    from .gridding import cappi_plans, products_of_grid
-    torch = _native.torch_mod()
-    nz = int(spec.grid_shape[0])
-    lo, hi = gp._level_window(nz, *products.window, spec)
-    if (products.columns or products.profile) and lo > hi:
-        raise ValueError(f"empty level window [{lo}, {hi}]")
-    plans = cappi_plans(products, spec, nz)
-    with torch.cuda.device(grids.device):
-        levels = gp.profile_levels_device(spec, nz, grids.device) if products.profile else None     # one upload per call
-        return [products_of_grid(products, grids[k], spec, lo, hi, plans, levels) for k in range(grids.shape[0])]
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -827,7 +808,6 @@ def mosaic_vertical_section(radars, fields: Sequence, vertices, spacing, z_limit
         additional_filters = [None] * len(radars)
     if len(fields) != len(radars) or len(additional_filters) != len(radars):
         raise ValueError(f"mosaic_vertical_section: expected one field and one filter list per radar ({len(radars)})")
-    from .gridding import _coerce_filters, _host_field, _to_host
     host = []
     for r, n in enumerate(counts):
         v, m = _host_field(fields[r], _coerce_filters(additional_filters[r]))

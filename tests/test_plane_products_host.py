@@ -144,3 +144,60 @@ def test_products_only_pass_refuses_host_tensors():
                            np.arange(8, dtype=np.int32), np.ones(8, dtype=np.float32), toa=17000.0)
     with pytest.raises(_native.NativeUnavailable):
         rg.grid_products_device(geom, [f], products=rg.PlaneProducts(colmin=True, colmean=True, ppi=(0.5,)), fused=True)
+
+
+# ---- ProductPlan: a request resolved against a grid spec, on the host ---------------------------------------------------------
+class _Spec:
+    grid_shape = (5, 3, 5)
+    grid_limits = ((1000, 5000), (-1, 1), (-1, 1))
+
+
+def test_product_plan_resolves_window_cappi_plans_kept_levels_and_angles_once(caplog):
+    from radar_processor_amd.plane_products import ProductPlan
+    spec = rg.PlaneProducts(cappi=(500.0, 3000.0, 3500.0, 3000.0), ppi=(1.5, 0.5, 1.5), z_min_idx=1, z_max_idx=3)
+    with caplog.at_level("WARNING", logger="radar_grid.products"):
+        plan = ProductPlan(spec, _Spec())
+    assert plan.window == (1, 3)
+    assert plan.cappi == {500.0: ("outside",), 3000.0: ("level", 2), 3500.0: ("blend", 2, 0.5, 0.5)}
+    assert list(plan.cappi) == [500.0, 3000.0, 3500.0]
+    assert (plan.keep_lo, plan.n_keep) == (2, 2)
+    assert plan.angles == [1.5, 0.5]
+    warnings = [r.getMessage() for r in caplog.records if r.levelname == "WARNING"]
+    assert warnings == ["Altitude 500.0m is outside grid range [1000, 5000]m"]
+
+
+def test_product_plan_refuses_an_empty_window_only_for_window_products():
+    from radar_processor_amd.plane_products import ProductPlan
+    empty = dict(z_min_idx=3, z_max_idx=1)
+    with pytest.raises(ValueError, match="empty level window"):
+        ProductPlan(rg.PlaneProducts(colmax=True, argmax=False, **empty), _Spec())
+    with pytest.raises(ValueError, match="empty level window"):
+        ProductPlan(rg.PlaneProducts(colmax=False, argmax=False, vil=True, **empty), _Spec())
+    plan = ProductPlan(rg.PlaneProducts(colmax=False, argmax=False, cappi=(3500.0,), **empty), _Spec())
+    assert plan.window == (3, 1) and (plan.keep_lo, plan.n_keep) == (2, 2)
+
+
+def test_product_plan_refuses_levels_that_do_not_increase_at_resolve_time():
+    from radar_processor_amd.plane_products import ProductPlan
+
+    class Flat(_Spec):
+        grid_limits = ((1000, 1000), (-1, 1), (-1, 1))
+    with pytest.raises(ValueError, match="strictly increasing"):
+        ProductPlan(rg.PlaneProducts(colmax=False, argmax=False, vil=True), Flat())
+    ProductPlan(rg.PlaneProducts(), Flat())                  # no profile product: the levels are nobody's business
+
+
+def test_ordered_record_fixes_the_key_order_of_every_subset():
+    import itertools
+    import random
+    from radar_processor_amd.plane_products import RECORD_KEYS, ordered_record
+    assert RECORD_KEYS == ("colmax", "argmax", "colmin", "colmean", "cappi", "ppi", "echo_top", "echo_base", "vil")
+    rng = random.Random(0)
+    for n in range(len(RECORD_KEYS) + 1):
+        for subset in itertools.combinations(RECORD_KEYS, n):
+            keys = list(subset)
+            rng.shuffle(keys)
+            planes = {k: object() for k in keys}
+            rec = ordered_record(planes)
+            assert list(rec) == list(subset)
+            assert all(rec[k] is planes[k] for k in subset)
