@@ -22,7 +22,9 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native
-from .grid_geometry import DeviceCSR, GridGeometry
+from . import grid_geometry
+from .compact_layout import ChunkLayout
+from .grid_geometry import CompactCSR, DeviceCSR, GridGeometry, scan_counts
 
 logger = logging.getLogger("radar_grid.compute")
 
@@ -247,20 +249,6 @@ class RoiSearch:
             weighting, _native.ptr(indptr), _native.ptr(gate_idx), _native.ptr(weights)))
 
 
-def scan_counts(counts, n_rows: int):
-    """Row lengths (int32 ``[n_rows + 1]``, on the device) -> row pointers int64 ``[n_rows + 1]`` (``rg_scan_counts_i64``)."""
-    torch = _native.torch_mod()
-    lib = _native.load_library()
-    dev = counts.device
-    with torch.cuda.device(dev):
-        indptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
-        ws_bytes = int(lib.rg_scan_workspace_bytes(n_rows))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _native.check(lib.rg_scan_counts_i64(_native.ptr(counts), n_rows, _native.ptr(indptr), _native.ptr(ws), ws_bytes,
-                                             _native.stream_ptr()), "rg_scan_counts_i64")
-    return indptr
-
-
 def csr_from_counts(counts, n_rows: int, fill) -> DeviceCSR:
     """count -> prefix sum -> fill: the CSR of ``n_rows`` rows whose lengths are ``counts``.  ``fill(indptr, gate_idx,
     weights)`` writes every row's pairs at ``indptr[row] ...`` (it is not called for an empty CSR).  ``indptr`` comes back
@@ -302,7 +290,6 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
 
     Returns ``(DeviceCSR without gate_indices [and without weights], CompactCSR)`` or ``None`` when a chunk holds more
     than 65536 distinct gates in a single segment (or packing was asked for and is not possible)."""
-    from .grid_geometry import CompactCSR
     torch = _native.torch_mod()
     lib = _native.load_library()
     nz, ny, nx = search.grid_shape
@@ -319,9 +306,8 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
         weights = local = rec = rec_ptr = None
         w_base = 0
         if packed:
-            from . import grid_geometry
-            rec_order = grid_geometry.DEFAULT_REC_ORDER
-            rec_ptr = CompactCSR.record_pointers(indptr, search.grid_shape, rec_order)      # all 16 bytes: the upper bound
+            rec_order = grid_geometry.DEFAULT_REC_ORDER        # read now: bench.py --rec-order assigns it before the build
+            rec_ptr = ChunkLayout(search.grid_shape).record_pointers(indptr, rec_order)      # all 16 bytes: the upper bound
             if rec_ptr is None:
                 return None
             slots_per_plane = (rec_ptr.numel() - 1) // nz      # chunks never cross a plane: neither do the slots
@@ -365,8 +351,8 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
                 # the slab's record pointers: its chunks' codings are known now (built[0]: their dictionary sizes)
                 dict_ptr_slab = torch.zeros(built[0].numel() + 1, dtype=torch.int64, device=dev)
                 dict_ptr_slab[1:] = torch.cumsum(built[0], 0)
-                rp = CompactCSR.record_pointers(indptr[iz0 * n_xy:iz1 * n_xy + 1], (iz1 - iz0, ny, nx), rec_order,
-                                                dict_ptr_slab, plane0=iz0)
+                rp = ChunkLayout((iz1 - iz0, ny, nx), plane0=iz0).record_pointers(indptr[iz0 * n_xy:iz1 * n_xy + 1], rec_order,
+                                                                                  dict_ptr_slab)
                 s0 = iz0 * slots_per_plane
                 rec_ptr[s0 + 1:s0 + rp.numel()] = rp[1:] + n_units
                 rec_ptr[s0] = n_units
@@ -394,10 +380,7 @@ def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int
                     rec = trimmed
                 else:
                     rec = rec[:n_units]
-            compact.rec, compact.rec_ptr, compact.rec_order, compact.w_base = rec, rec_ptr, rec_order, w_base
-            compact.build_row_ends(indptr)
-            logger.info(f"Packed pair stream: {16 * n_units / 1e6:.1f} MB ({16 * n_units / max(n_pairs, 1):.2f} bytes per pair; "
-                        f"{100 * compact.dense_fraction():.2f} % of the pairs in 14-byte records)")
+            compact.attach_records(rec, rec_ptr, rec_order, w_base, indptr)
         if n_pairs <= _INT32_MAX:
             indptr = indptr.to(torch.int32)
     return DeviceCSR(indptr, None, weights, max_gate, n_pairs=n_pairs), compact

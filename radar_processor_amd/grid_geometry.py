@@ -16,6 +16,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native
+from .compact_layout import ChunkLayout, check_sidecar, unpack_records
 
 logger = logging.getLogger("radar_grid.geometry")  # same logger name as the reference (docs/LOGGING.md:128-141)
 
@@ -51,6 +52,20 @@ class DeviceCSR:
                    if t is not None)
 
 
+def scan_counts(counts, n_rows: int):
+    """Row lengths (int32 ``[n_rows + 1]``, on the device) -> row pointers int64 ``[n_rows + 1]`` (``rg_scan_counts_i64``)."""
+    torch = _native.torch_mod()
+    lib = _native.load_library()
+    dev = counts.device
+    with torch.cuda.device(dev):
+        indptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        ws_bytes = int(lib.rg_scan_workspace_bytes(n_rows))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _native.check(lib.rg_scan_counts_i64(_native.ptr(counts), n_rows, _native.ptr(indptr), _native.ptr(ws), ws_bytes,
+                                             _native.stream_ptr()), "rg_scan_counts_i64")
+    return indptr
+
+
 class CompactCSR:
     """Compact device copy of a :class:`DeviceCSR` for ``rg_csr_compact_apply_f32``.  Rows are grouped in chunks that
     cover a 2-D patch of the grid -- segment ``sx`` (rows ``[64*sx, 64*sx+64)`` of a grid line) of
@@ -58,11 +73,16 @@ class CompactCSR:
     distinct gates are listed once (``dict`` / ``dict_ptr``) and every pair stores a 16-bit position in that list
     (``local_idx``).  A chunk with more than 65536 distinct gates (the patch around the radar on a dense scan) is
     *split*: one dictionary per wavefront behind a header of ``RG_COMPACT_LINES`` offsets, recognisable by an entry count
-    above 65536.  ``indptr`` and ``weights`` are shared with the standard CSR."""
+    above 65536.  ``indptr`` and ``weights`` are shared with the standard CSR.
+
+    This class holds the arrays, the LDS window policy and the build; the layout arithmetic and the record decoder live in
+    ``compact_layout`` (``chunks`` is the grid's :class:`~.compact_layout.ChunkLayout`), and the layout methods kept here
+    (``layout``, ``segment_starts``, ``chunk_of_rows``, ``slot_of_segments``, ``record_pointers``, ``segment_spans``,
+    ``_record_fields``) delegate to it."""
 
     __slots__ = ("local_idx", "dict_ptr", "dict", "n_dict", "max_dict", "window_cap", "grid_shape", "chunk_pairs",
                  "chunk_counts", "rec", "rec_ptr", "rec_order", "w_base", "_pack_tried", "_column_orders", "row_end16",
-                 "_row_ptr_bytes")
+                 "_row_ptr_bytes", "chunks")
 
     def __init__(self, local_idx, dict_ptr, dict_, max_dict: int, window_cap: int, grid_shape, chunk_pairs=None,
                  chunk_counts=None):
@@ -73,6 +93,7 @@ class CompactCSR:
         self.max_dict = int(max_dict)
         self.window_cap = int(window_cap)   # LDS window (entries) that covers 99.9 % of the pairs (speed only)
         self.grid_shape = tuple(int(v) for v in grid_shape)   # (planes, lines per plane, rows per line)
+        self.chunks = ChunkLayout(self.grid_shape)
         self.chunk_pairs = chunk_pairs      # int64 [chunks]: pairs per chunk    } kept to choose the window for a
         self.chunk_counts = chunk_counts    # int64 [chunks]: distinct gates     } given field count (window_for)
         # packed pair stream for passes of 1-8 fields (ensure_packed): records of three pairs -- 14 bytes each in the chunks
@@ -99,18 +120,6 @@ class CompactCSR:
         does not fit) and reads the row pointers.  ``span``: an int, an array or a tensor."""
         return span <= _native.RG_ROW_END16_MAX
 
-    @classmethod
-    def segment_spans(cls, indptr, grid_shape):
-        """Pairs of every segment: int64 ``[lines, nsx]`` (lines counted through all planes)."""
-        torch = _native.torch_mod()
-        nz, ny, nx = (int(v) for v in grid_shape)
-        nsx = cls.layout(grid_shape)[0]
-        dev = indptr.device
-        starts = torch.tensor(cls.segment_starts(nx), device=dev, dtype=torch.int64)
-        line0 = torch.arange(nz * ny, device=dev, dtype=torch.int64) * nx
-        edges = indptr[(line0[:, None] + starts[None, :]).reshape(-1)].to(torch.int64).view(nz * ny, nsx + 1)
-        return edges[:, 1:] - edges[:, :-1]
-
     def build_row_ends(self, indptr) -> None:
         """Build (once) the row-end table ``rg_csr_row_ends16`` writes from the grid's row pointers: two bytes per row that
         the row-wise kernel reads instead of ``indptr[v]`` and ``indptr[v + 1]`` in every segment :meth:`rows_fit16` admits."""
@@ -132,22 +141,12 @@ class CompactCSR:
                     f"{100 * st['segments16']:.3f} % of the segments and {100 * st['voxels16']:.3f} % of the voxels keep "
                     "16-bit row ends")
 
-    def _segment_rows_and_chunks(self, dev):
-        """``(rows per segment [nsx], chunk of every segment [lines, nsx])`` as int64 tensors."""
-        torch = _native.torch_mod()
-        nz, ny, nx = self.grid_shape
-        nsx, nyg, _ = self.layout(self.grid_shape)
-        starts = torch.tensor(self.segment_starts(nx), device=dev, dtype=torch.int64)
-        line = torch.arange(nz * ny, device=dev, dtype=torch.int64)
-        grp = (line // ny) * nyg + (line % ny) // _native.RG_COMPACT_LINES
-        return starts[1:] - starts[:-1], grp[:, None] * nsx + torch.arange(nsx, device=dev, dtype=torch.int64)[None, :]
-
     def row_end_stats(self, indptr) -> dict:
         """Shares the row-end table and the early exit rest on: ``empty_chunks`` (chunks without a pair), ``segments16`` and
         ``voxels16`` (segments / voxels whose row ends fit 16 bits, by :meth:`rows_fit16`)."""
         nz, ny, nx = self.grid_shape
-        fit = self.rows_fit16(self.segment_spans(indptr, self.grid_shape))
-        nrows, _ = self._segment_rows_and_chunks(indptr.device)
+        fit = self.rows_fit16(self.chunks.segment_spans(indptr))
+        nrows = self.chunks.segment_rows(indptr.device)
         n_chunks = max(int(self.chunk_pairs.numel()), 1)
         return {"empty_chunks": float(int((self.chunk_pairs == 0).sum()) / n_chunks),
                 "segments16": float(int(fit.sum()) / max(fit.numel(), 1)),
@@ -161,12 +160,12 @@ class CompactCSR:
         ip = 8 if indptr.dtype == torch.int64 else 4
         key = (ip, bool(grid_mode))
         if key not in self._row_ptr_bytes:
-            spans = self.segment_spans(indptr, self.grid_shape)
-            nrows, chunk = self._segment_rows_and_chunks(indptr.device)
+            spans = self.chunks.segment_spans(indptr)
+            nrows = self.chunks.segment_rows(indptr.device)
             fit = self.rows_fit16(spans) if self.row_end16 is not None else torch.zeros_like(spans, dtype=torch.bool)
             live = torch.ones_like(fit)
             if grid_mode and self.rec_order == _native.RG_REC_ORDER_DISPATCH:
-                live = self.chunk_pairs.to(indptr.device)[chunk] > 0
+                live = self.chunk_pairs.to(indptr.device)[self.chunks.segment_chunks(indptr.device)] > 0
             rows16 = int(((fit & live) * nrows[None, :]).sum())
             ptrs = int(((~fit & live) * (nrows[None, :] + 1)).sum())
             self._row_ptr_bytes[key] = 2 * rows16 + ip * ptrs
@@ -204,7 +203,7 @@ class CompactCSR:
                         "of 8, the compact copy keeps the plain arrays")
             return False
         nz, ny, nx = self.grid_shape
-        rec_ptr = self.record_pointers(csr.indptr, self.grid_shape, self.rec_order, self.dict_ptr)
+        rec_ptr = self.chunks.record_pointers(csr.indptr, self.rec_order, self.dict_ptr)
         if rec_ptr is None:                      # the kernels address a segment's records with 32-bit byte offsets
             logger.info("a segment holds more than 2^27 records: the compact copy keeps the plain arrays")
             return False
@@ -220,11 +219,18 @@ class CompactCSR:
                           "rg_csr_compact_pack_dense")
         if int(err.item()):
             raise _native.NativeError(f"rg_csr_compact_pack_dense reported flag {int(err.item())}")
-        self.rec, self.rec_ptr, self.w_base = rec, rec_ptr, w_base
-        self.build_row_ends(csr.indptr)
-        logger.info(f"Packed pair stream: {rec.numel() * 4 / 1e6:.1f} MB ({16 * n_rec / csr.n_pairs:.2f} bytes per pair; "
-                    f"{100 * self.dense_fraction():.2f} % of the pairs in 14-byte records)")
+        self.attach_records(rec, rec_ptr, self.rec_order, w_base, csr.indptr)
         return True
+
+    def attach_records(self, rec, rec_ptr, rec_order: int, w_base: int, indptr) -> None:
+        """Take ``rec`` / ``rec_ptr`` (in ``rec_order``, weights coded above ``w_base``) as the packed pair stream of the grid
+        whose row pointers are ``indptr``, and build the row-end table that goes with it."""
+        self.rec, self.rec_ptr, self.rec_order, self.w_base = rec, rec_ptr, int(rec_order), int(w_base)
+        self._pack_tried = True
+        self.build_row_ends(indptr)
+        n_pairs = max(int(indptr[-1]), 1)
+        logger.info(f"Packed pair stream: {rec.numel() * 4 / 1e6:.1f} MB ({rec.numel() * 4 / n_pairs:.2f} bytes per pair; "
+                    f"{100 * self.dense_fraction():.2f} % of the pairs in 14-byte records)")
 
     def dense_chunks(self):
         """bool ``[chunks]``: the chunks whose records are 14 bytes (at most ``RG_DENSE_MAX_DICT`` dictionary entries)."""
@@ -237,91 +243,37 @@ class CompactCSR:
         total = max(int(self.chunk_pairs.sum()), 1)
         return float(int(self.chunk_pairs[self.dense_chunks()].sum()) / total)
 
-    @classmethod
-    def slot_of_segments(cls, line, sx, grid_shape, rec_order: int, plane0: int = 0):
-        """Slot (index into ``rec_ptr``) of segment ``sx`` of grid line ``line`` (int64 tensors, lines counted through all
-        planes).  ``RG_REC_ORDER_SEGMENT``: the line-major segment number.  ``RG_REC_ORDER_DISPATCH``: ``block * H + w``
-        for the wavefront ``w`` of the workgroup ``block`` that reads the segment -- the inverse of the kernels'
-        block -> chunk rotation (``block_chunk`` in csrc/rg_compact_layout.hpp, 32-bit unsigned arithmetic).  ``plane0``: the
-        grid is a slab of whole planes of a larger one and this is its first plane there -- lines and slots stay the slab's
-        own, the rotation counts the line groups in front of it."""
-        nz, ny, nx = (int(v) for v in grid_shape)
-        nsx, nyg, _ = cls.layout(grid_shape)
-        if rec_order == _native.RG_REC_ORDER_SEGMENT:
-            return line * nsx + sx
-        lines = _native.RG_COMPACT_LINES
-        plane = line // ny
-        y = line - plane * ny
-        grp = plane * nyg + y // lines
-        shift = (((grp + int(plane0) * nyg) * _native.RG_COMPACT_ROTATION) & 0xFFFFFFFF) % nsx
-        col = (sx - shift) % nsx                     # the block column whose rotated column is sx
-        return (grp * nsx + col) * lines + y % lines
-
-    @classmethod
-    def record_pointers(cls, indptr, grid_shape, rec_order: int, dict_ptr=None, plane0: int = 0):
-        """``rec_ptr`` (int64 ``[slots + 1]``) for the row pointers of a whole grid (or of a slab of whole planes that starts
-        at plane ``plane0`` of a larger one), in 16-byte units laid out in slot order: a segment of ``n = ceil(pairs / 3)``
-        records takes ``ceil(14 * n / 16)`` units where its chunk's dictionary (``dict_ptr``, int64 ``[chunks + 1]``) has at
-        most ``RG_DENSE_MAX_DICT`` entries and ``n`` units elsewhere -- everywhere without ``dict_ptr``, which is also the
-        upper bound of any layout.  ``None`` when a segment would hold 2^27 records or more."""
-        torch = _native.torch_mod()
-        dev = indptr.device
-        nz, ny, nx = (int(v) for v in grid_shape)
-        nsx, nyg, n_chunks = cls.layout(grid_shape)
-        starts = torch.tensor(cls.segment_starts(nx), device=dev, dtype=torch.int64)
-        line0 = torch.arange(nz * ny, device=dev, dtype=torch.int64) * nx
-        edges = indptr[(line0[:, None] + starts[None, :]).reshape(-1)].to(torch.int64).view(nz * ny, nsx + 1)
-        n_rec_seg = ((edges[:, 1:] - edges[:, :-1]) + 2) // 3
-        if n_rec_seg.numel() and int(n_rec_seg.max()) >= 1 << 27:
-            return None
-        if dict_ptr is not None and n_rec_seg.numel():
-            lines = _native.RG_COMPACT_LINES
-            line_all = torch.arange(nz * ny, device=dev, dtype=torch.int64)
-            grp = (line_all // ny) * nyg + (line_all % ny) // lines                        # line group of every line
-            chunk = grp[:, None] * nsx + torch.arange(nsx, device=dev, dtype=torch.int64)[None, :]
-            dp = dict_ptr.to(dev)
-            dense = (dp[chunk + 1] - dp[chunk]) <= _native.RG_DENSE_MAX_DICT
-            n_rec_seg = torch.where(dense, (14 * n_rec_seg + 15) // 16, n_rec_seg)
-        if rec_order == _native.RG_REC_ORDER_SEGMENT:
-            per_slot = n_rec_seg.reshape(-1)
-        else:
-            line = torch.arange(nz * ny, device=dev, dtype=torch.int64)[:, None].expand(nz * ny, nsx)
-            sx = torch.arange(nsx, device=dev, dtype=torch.int64)[None, :].expand(nz * ny, nsx)
-            per_slot = torch.zeros(n_chunks * _native.RG_COMPACT_LINES, dtype=torch.int64, device=dev)
-            per_slot[cls.slot_of_segments(line, sx, grid_shape, rec_order, plane0).reshape(-1)] = n_rec_seg.reshape(-1)
-        rec_ptr = torch.zeros(per_slot.numel() + 1, dtype=torch.int64, device=dev)
-        rec_ptr[1:] = torch.cumsum(per_slot, 0)
-        return rec_ptr
-
+    # ---- the layout: one-line delegates to compact_layout.ChunkLayout, kept under the names callers know ---------------------
     @staticmethod
     def layout(grid_shape):
         """``(nsx, nyg, n_chunks)`` of a grid: segments per line, line groups per plane, chunks."""
-        nz, ny, nx = (int(v) for v in grid_shape)
-        nsx = (nx + 63) // 64
-        nyg = (ny + _native.RG_COMPACT_LINES - 1) // _native.RG_COMPACT_LINES
-        return nsx, nyg, nz * nyg * nsx
+        chunks = ChunkLayout(grid_shape)
+        return chunks.nsx, chunks.nyg, chunks.n_chunks
 
     @staticmethod
     def segment_starts(nx: int):
-        """First row of each of a line's ``ceil(nx / 64)`` segments (+ ``nx`` as the last entry).  The segments are
-        balanced -- the first ``nx % nsx`` hold one row more than the others -- exactly as the kernels cut them."""
-        nsx = (int(nx) + 63) // 64
-        base, extra = divmod(int(nx), nsx)
-        return [sx * base + min(sx, extra) for sx in range(nsx + 1)]
+        """``ChunkLayout.segment_starts`` of a line of ``nx`` rows."""
+        return ChunkLayout((1, 1, nx)).segment_starts()
 
     @staticmethod
     def chunk_of_rows(rows, grid_shape):
-        """Chunk number of every (flat, int64 tensor) row index."""
-        nz, ny, nx = (int(v) for v in grid_shape)
-        nsx, nyg, _ = CompactCSR.layout(grid_shape)
-        base, extra = divmod(nx, nsx)
-        line = rows // nx
-        x = rows - line * nx
-        plane = line // ny
-        y = line - plane * ny
-        split = extra * (base + 1)                  # rows covered by the longer segments
-        sx = (x // (base + 1)).where(x < split, extra + (x - split) // max(base, 1))
-        return (plane * nyg + y // _native.RG_COMPACT_LINES) * nsx + sx
+        """``ChunkLayout.chunk_of_rows``."""
+        return ChunkLayout(grid_shape).chunk_of_rows(rows)
+
+    @staticmethod
+    def slot_of_segments(line, sx, grid_shape, rec_order: int, plane0: int = 0):
+        """``ChunkLayout.slot_of_segments`` (the inverse of ``block_chunk`` in csrc/rg_compact_layout.hpp)."""
+        return ChunkLayout(grid_shape, plane0).slot_of_segments(line, sx, rec_order)
+
+    @staticmethod
+    def record_pointers(indptr, grid_shape, rec_order: int, dict_ptr=None, plane0: int = 0):
+        """``ChunkLayout.record_pointers`` of a whole grid, or of a slab of whole planes that starts at ``plane0``."""
+        return ChunkLayout(grid_shape, plane0).record_pointers(indptr, rec_order, dict_ptr)
+
+    @staticmethod
+    def segment_spans(indptr, grid_shape):
+        """``ChunkLayout.segment_spans``."""
+        return ChunkLayout(grid_shape).segment_spans(indptr)
 
     @staticmethod
     def entry_bytes(n_fields: int, rowwise: bool = False) -> int:
@@ -393,11 +345,7 @@ class CompactCSR:
                                                _native.ptr(counts), _native.ptr(rounds), stream), "rg_csr_compact_count")
         if int(counts.max()) >= _NOT_COMPACTABLE:      # a single 64-row segment references more than 65536 gates
             return None
-        dict_ptr = torch.empty(n_chunks + 1, dtype=torch.int64, device=dev)
-        ws_bytes = int(lib.rg_scan_workspace_bytes(n_chunks))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        _native.check(lib.rg_scan_counts_i64(_native.ptr(counts), n_chunks, _native.ptr(dict_ptr), _native.ptr(ws), ws_bytes,
-                                             stream), "rg_scan_counts_i64")
+        dict_ptr = scan_counts(counts, n_chunks)
         n_dict = int(dict_ptr[-1])
         dict_ = torch.empty(max(n_dict, 1), dtype=torch.int32, device=dev)[:n_dict]
         err = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -413,30 +361,18 @@ class CompactCSR:
     @classmethod
     def _finish(cls, indptr, grid_shape, local, counts, parts) -> "CompactCSR":
         torch = _native.torch_mod()
-        lines = _native.RG_COMPACT_LINES
         dev = counts.device
-        nz, ny, nx = (int(v) for v in grid_shape)
-        nsx, nyg, n_chunks = cls.layout(grid_shape)
+        chunks = ChunkLayout(grid_shape)
+        n_chunks = chunks.n_chunks
         assert n_chunks == int(counts.shape[0])
         dict_ptr = torch.zeros(n_chunks + 1, dtype=torch.int64, device=dev)
         dict_ptr[1:] = torch.cumsum(counts, 0)
         dict_ = torch.cat(parts) if parts else torch.zeros(1, dtype=torch.int32, device=dev)[:0]
-        # pairs per chunk: per (line, segment) from the row pointers, summed over the lines of a group
-        if n_chunks:
-            seg_x = torch.tensor(cls.segment_starts(nx), device=dev, dtype=torch.int64)
-            line0 = torch.arange(nz * ny, device=dev, dtype=torch.int64) * nx
-            edges = indptr[(line0[:, None] + seg_x[None, :]).reshape(-1)].to(torch.int64).view(nz * ny, nsx + 1)
-            seg_pairs = (edges[:, 1:] - edges[:, :-1]).view(nz, ny, nsx)
-            pad = nyg * lines - ny
-            if pad:
-                seg_pairs = torch.cat([seg_pairs, torch.zeros((nz, pad, nsx), dtype=torch.int64, device=dev)], dim=1)
-            chunk_pairs = seg_pairs.view(nz, nyg, lines, nsx).sum(dim=2).reshape(-1)
-        else:
-            chunk_pairs = torch.zeros(0, dtype=torch.int64, device=dev)
+        chunk_pairs = chunks.chunk_pairs(indptr)             # from the row pointers at the segment edges
         # LDS window: the smallest size (multiple of 256 entries) that leaves at most 0.1 % of the pairs to the
         # per-pair fallback
         window_cap = _native.RG_COMPACT_MAX_WINDOW
-        total = max(int(chunk_pairs.sum()), 1) if n_chunks else 1
+        total = max(int(chunk_pairs.sum()), 1)
         for cap in range(256, _native.RG_COMPACT_MAX_WINDOW + 1, 256):
             if int(chunk_pairs[counts > cap].sum()) <= total // 1000:
                 window_cap = cap
@@ -445,57 +381,9 @@ class CompactCSR:
                    chunk_pairs, counts)
 
     def _record_fields(self, csr: "DeviceCSR", r0: int, r1: int):
-        """Positions (int64) and weights (float32) of the pairs of rows ``[r0, r1)``, unpacked from the records (the inverse
-        of ``rg_csr_compact_pack_dense``, both codings: csrc/rg_compact_layout.hpp; used when the plain ``local_idx`` /
-        ``weights`` arrays do not exist)."""
-        torch = _native.torch_mod()
-        dev = csr.indptr.device
-        nz, ny, nx = self.grid_shape
-        nsx = (nx + 63) // 64
-        base, extra = divmod(nx, nsx)
-        ip = csr.indptr[r0:r1 + 1].to(torch.int64)
-        rows = torch.arange(r0, r1, device=dev, dtype=torch.int64)
-        line = rows // nx
-        x = rows - line * nx
-        split = extra * (base + 1)
-        sx = (x // (base + 1)).where(x < split, extra + (x - split) // max(base, 1))
-        seg = self.slot_of_segments(line, sx, self.grid_shape, self.rec_order)
-        x0 = (sx * base + torch.minimum(sx, torch.full_like(sx, extra)))
-        seg_first_pair = csr.indptr[line * nx + x0].to(torch.int64)            # pair offset where the row's segment starts
-        lens = ip[1:] - ip[:-1]
-        n = int(ip[-1] - ip[0])
-        row_of_pair = torch.repeat_interleave(torch.arange(r1 - r0, device=dev), lens, output_size=n)
-        pair = torch.arange(n, device=dev, dtype=torch.int64) + ip[0]
-        q = pair - seg_first_pair[row_of_pair]                                 # pair's offset inside its segment
-        unit0 = self.rec_ptr[seg[row_of_pair]]                                 # first 16-byte unit of the pair's segment
-        rq, j = q // 3, q % 3
-        chunk_of_row = self.chunk_of_rows(rows, self.grid_shape)
-        dense = ((self.dict_ptr[chunk_of_row + 1] - self.dict_ptr[chunk_of_row]) <= _native.RG_DENSE_MAX_DICT)[row_of_pair]
-        code = torch.empty(n, dtype=torch.int64, device=dev)
-        pos = torch.empty(n, dtype=torch.int64, device=dev)
-        wide = ~dense
-        if bool(wide.any()):
-            rec = self.rec[unit0[wide] + rq[wide]].to(torch.int64) & 0xFFFFFFFF      # [m, 4] as unsigned
-            jw = j[wide]
-            code[wide] = torch.where(jw == 0, rec[:, 0], torch.where(jw == 1, rec[:, 1], rec[:, 2])) & 0x3FFFFFF
-            p2 = (rec[:, 0] >> 26) | ((rec[:, 1] >> 26) << 6) | (((rec[:, 2] >> 26) & 0xF) << 12)
-            pos[wide] = torch.where(jw == 0, rec[:, 3] & 0xFFFF, torch.where(jw == 1, rec[:, 3] >> 16, p2))
-        if bool(dense.any()):
-            half = self.rec.view(torch.int16).reshape(-1)
-            rd, jd = rq[dense], j[dense]
-            h = half[(unit0[dense] * 8 + 7 * rd)[:, None] + torch.arange(7, device=dev)[None, :]].to(torch.int64) & 0xFFFF
-            odd = (rd & 1) == 1
-            pair_w = lambda lo, hi: h[:, lo] | (h[:, hi] << 16)                  # noqa: E731  two halfwords as one word
-            w2 = torch.where(odd, pair_w(0, 5), pair_w(0, 1))
-            m1 = torch.where(odd, pair_w(1, 2), pair_w(2, 3))
-            m2 = torch.where(odd, pair_w(3, 4), pair_w(4, 5))
-            pw = h[:, 6]
-            code[dense] = torch.where(jd == 0, m1, torch.where(jd == 1, m2, w2)) & 0x3FFFFFF
-            p1 = (m1 >> 26) | ((pw >> 11) << 6)
-            p2 = (m2 >> 26) | ((w2 >> 26) << 6)
-            pos[dense] = torch.where(jd == 0, pw & 0x7FF, torch.where(jd == 1, p1, p2))
-        weights = (code + self.w_base).to(torch.int32).view(torch.float32)
-        return pos, weights
+        """Positions (int64) and weights (float32) of the pairs of rows ``[r0, r1)``: ``compact_layout.unpack_records`` (used
+        when the plain ``local_idx`` / ``weights`` arrays do not exist)."""
+        return unpack_records(self.chunks, csr.indptr, self.rec, self.rec_ptr, self.rec_order, self.w_base, self.dict_ptr, r0, r1)
 
     def decode_weights(self, csr: "DeviceCSR", row0: int = 0, row1: Optional[int] = None, rows_per_slab: int = 500_000):
         """float32 weights of rows ``[row0, row1)``: a view of ``csr.weights`` when it exists, else unpacked from the
@@ -528,7 +416,7 @@ class CompactCSR:
             if p1 == p0:
                 continue
             rows = torch.arange(r0, r1, device=dev, dtype=torch.int64)
-            chunk_of_row = self.chunk_of_rows(rows, self.grid_shape)
+            chunk_of_row = self.chunks.chunk_of_rows(rows)
             start_of_row = self.dict_ptr[chunk_of_row]
             # split chunks (more than 65536 entries: one dictionary per wavefront behind a header of offsets)
             is_split = (self.dict_ptr[chunk_of_row + 1] - start_of_row) > 65536
@@ -816,7 +704,9 @@ def save_device_layout(geometry: GridGeometry, filepath: str, device=None) -> bo
     if compact.local_idx is not None:
         arrays["local_idx"] = compact.local_idx.cpu().numpy()
     np.savez(filepath, **arrays)
-    logger.info(f"Saved device layout to {filepath} ({os.path.getsize(filepath) / 1e6:.1f} MB)")
+    written = os.fspath(filepath)
+    written += "" if written.endswith(".npz") else ".npz"          # numpy.savez appends the suffix to a path without it
+    logger.info(f"Saved device layout to {written} ({os.path.getsize(written) / 1e6:.1f} MB)")
     return True
 
 
@@ -827,25 +717,28 @@ def load_device_layout(geometry: GridGeometry, filepath: str, device=None) -> bo
     torch = _native.torch_mod()
     if not os.path.exists(filepath):
         return False
-    with np.load(filepath, allow_pickle=False) as data:
-        if bytes(data["key"]).decode() != _reference_arrays_digest(geometry):
+    with np.load(filepath, allow_pickle=False) as npz:
+        if bytes(npz["key"]).decode() != _reference_arrays_digest(geometry):
             logger.warning(f"{filepath} was derived from another geometry: ignored")
             return False
-        if "rec" in data and ("rec_format" not in data or int(data["rec_format"][0]) != REC_FORMAT):
+        if "rec" in npz and ("rec_format" not in npz or int(npz["rec_format"][0]) != REC_FORMAT):
             logger.warning(f"{filepath} holds records in another coding than this build reads (no or another rec_format tag): "
                            "ignored, the device layout is derived again")
             return False
-        csr = geometry.device_csr(device)
-        dev = csr.indptr.device
-        up = lambda name: torch.from_numpy(np.ascontiguousarray(data[name])).to(dev)       # noqa: E731
-        compact = CompactCSR(up("local_idx") if "local_idx" in data else None, up("dict_ptr"), up("dict"), int(data["max_dict"][0]),
-                             int(data["window_cap"][0]), tuple(int(v) for v in data["grid_shape"]), up("chunk_pairs"),
-                             up("chunk_counts"))
-        if "rec" in data:
-            compact.rec, compact.rec_ptr = up("rec"), up("rec_ptr")
-            compact.rec_order, compact.w_base = int(data["rec_order"][0]), int(data["w_base"][0])
-            compact._pack_tried = True
-            compact.build_row_ends(csr.indptr)          # derived data: rebuilt, not stored
+        data = {name: npz[name] for name in npz.files}
+    reason = check_sidecar(ChunkLayout(geometry.grid_shape), data, geometry.n_pairs())     # before anything is uploaded
+    if reason is not None:
+        logger.warning(f"{filepath} does not hold the layout of this geometry ({reason}): ignored, the device layout is "
+                       "derived again")
+        return False
+    csr = geometry.device_csr(device)
+    dev = csr.indptr.device
+    up = lambda name: torch.from_numpy(np.ascontiguousarray(data[name])).to(dev)       # noqa: E731
+    compact = CompactCSR(up("local_idx") if "local_idx" in data else None, up("dict_ptr"), up("dict"), int(data["max_dict"][0]),
+                         int(data["window_cap"][0]), tuple(int(v) for v in data["grid_shape"]), up("chunk_pairs"),
+                         up("chunk_counts"))
+    if "rec" in data:                                   # the row-end table is derived data: rebuilt, not stored
+        compact.attach_records(up("rec"), up("rec_ptr"), int(data["rec_order"][0]), int(data["w_base"][0]), csr.indptr)
     geometry._compact = (csr, compact)
     logger.info(f"Device layout attached from {filepath}: {compact.nbytes() / 1e6:.1f} MB")
     return True

@@ -211,25 +211,16 @@ class CsrGridder:
         longest-processing-time scheduling).  Cached on the compact copy."""
         torch = _native.torch_mod()
         c = self.compact
-        nz, ny, nx = self.grid_shape
-        nsx, nyg, _ = c.layout(self.grid_shape)
-        n_cols = nsx * nyg
+        nz = self.grid_shape[0]
+        n_cols = c.chunks.nsx * c.chunks.nyg
         if z_pieces <= 0:
             z_pieces = max(1, min(nz, -(-_COLUMNS_MIN_WORKGROUPS // max(n_cols, 1))))
         z_pieces = max(1, min(int(z_pieces), nz))
         cache = c._column_orders
         order = cache.get(z_pieces)
         if order is None:
-            if c.chunk_pairs is not None and c.chunk_pairs.numel() == nz * nyg * nsx:
-                cp = c.chunk_pairs.view(nz, nyg, nsx)
-                yg = torch.arange(nyg, device=cp.device)[:, None]
-                col = torch.arange(nsx, device=cp.device)[None, :]
-                sx = (col + (yg * _native.RG_COMPACT_ROTATION) % nsx) % nsx            # the kernel's column -> segment map
-                parts = []
-                for p in range(z_pieces):
-                    z0, z1 = p * nz // z_pieces, (p + 1) * nz // z_pieces
-                    parts.append(torch.gather(cp[z0:z1].sum(dim=0), 1, sx).reshape(-1))
-                weight = torch.cat(parts)
+            if c.chunk_pairs is not None and c.chunk_pairs.numel() == c.chunks.n_chunks:
+                weight = c.chunks.column_weights(c.chunk_pairs, z_pieces)
                 order = torch.argsort(weight, descending=True, stable=True).to(torch.int32)
             else:
                 order = False                                        # no statistics: identity order
