@@ -21,7 +21,8 @@ Two routes:
   fill kernels, each radar over its reach window) and :func:`apply_mosaic` / :func:`mosaic_fields_device` grid through it
   like any geometry -- for repeated volumes;
 * :class:`MosaicSearch` keeps one search structure per radar and :func:`mosaic_fields_device` grids straight from the gates
-  (``rg_roi_grid_mosaic_f32``) -- no CSR, any subset of the radars per call.
+  (``rg_roi_grid_mosaic_combine_f32``; its joint mean is the kernel of ``rg_roi_grid_mosaic_f32``) -- no CSR, any subset
+  of the radars per call.
 
 A vertical section through a mosaic (``csrc/rg_roi_section.hip``: ``rg_roi_section_mosaic_f32``) has the same two routes:
 :func:`mosaic_section_fields_device` on a :class:`MosaicSearch` -- of a lattice, or of the path itself
@@ -33,7 +34,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -43,7 +44,8 @@ from .grid_geometry import GridGeometry
 from .gridding import _coerce_filters, _host_field, _stride_for, _to_host, grid_fields_device
 from .plane_products import ProductPlan, grid_products_device
 from .roi_grid import pack_and_grid
-from .section import _check_points, _cumulative_distance, section_path, section_rectangle
+from .section import (_PathRows, _check_points_in, _refuse_closest, _cumulative_distance, _grid_rectangle, _host,
+                      _length, _upload, section_path, section_rectangle)
 
 _GATHER_BYTES = 2 ** 32        # buffer-resource range of the packed-field gather in rg_csr_apply_f32
 MOSAIC_COMBINES = tuple(_native.COMBINES)      # "mean", "max", "nearest_radar": the combine rules of the CSR-free route
@@ -53,20 +55,6 @@ NO_RADAR = _native.RG_NO_RADAR                 # in a ``radar`` map: no radar ha
 def mosaic_limits(grid_limits, origin) -> Tuple[Tuple[float, float], ...]:
     """The shared grid's limits in the frame of a radar at ``origin = (oz, oy, ox)`` (Python floats)."""
     return tuple((float(lo) - float(o), float(hi) - float(o)) for (lo, hi), o in zip(grid_limits, origin))
-
-
-def _length(a) -> int:
-    """Element count of a NumPy array, torch tensor or sequence -- without touching a device."""
-    if hasattr(a, "numel"):
-        return int(a.numel())
-    if hasattr(a, "size") and not callable(a.size):
-        return int(a.size)
-    return len(a)
-
-
-def _host(a):
-    """A tensor (any device) -> NumPy; anything else as it is."""
-    return a.detach().cpu().numpy() if hasattr(a, "detach") else a
 
 
 def _check_radars(radars, max_radars: Optional[int] = None):
@@ -174,6 +162,19 @@ def _window_empty(w) -> bool:
     return w[0] >= w[1] or w[2] >= w[3]
 
 
+def _window_searches(radars, origins, grid_shape, grid_limits, min_radius, beam_factor, toa, dev):
+    """Per radar its reach window on the shared grid and its :class:`RoiSearch` over that window, in its own frame
+    (``None``: the window is empty): ``(windows, searches)``."""
+    windows, searches = [], []
+    for (gx, gy, gz, _), origin in zip(radars, origins):
+        w = reach_window(gx, gy, gz, grid_shape, grid_limits, origin, min_radius, beam_factor, toa)
+        windows.append(w)
+        searches.append(None if _window_empty(w) else RoiSearch(
+            gx, gy, gz, grid_shape, mosaic_limits(grid_limits, origin), radar_altitude=0.0, min_radius=min_radius,
+            beam_factor=beam_factor, toa=float(toa) - float(origin[0]), device=dev, window=w))
+    return windows, searches
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # geometry route
 # ------------------------------------------------------------------------------------------------------------------------
@@ -196,51 +197,56 @@ def compute_mosaic_geometry(radars, grid_shape, grid_limits, temp_dir: str, min_
         raise ValueError(f"Unknown weighting function: {weighting}")
     radars = list(radars)
     counts, origins = _check_radars(radars)
-    torch = _native.torch_mod()
     _native.load_library()
     dev = _native.device()
-    nz, ny, nx = (int(s) for s in grid_shape)
-    n_vox = nz * ny * nx
+    shape = nz, ny, nx = tuple(int(s) for s in grid_shape)
+
+    def part(r, search):
+        iy0, iy1, ix0, ix1 = search.window
+        return _RowsPart(r, search, lambda rows: rows.view(nz, ny, nx)[:, iy0:iy1, ix0:ix1],
+                         lambda: search.count_rows()[:-1].view(search.grid_shape),
+                         lambda base, gate_idx, weights: search.fill_rows(weighting, _native.ptr(base), _native.ptr(gate_idx),
+                                                                          _native.ptr(weights)))
+    # per radar that reaches a voxel: its search over its reach window, all of them built before the first count
+    searches = _window_searches(radars, origins, shape, grid_limits, min_radius, beam_factor, toa, dev)[1]
+    return _stacked_geometry(shape, grid_limits, toa, counts, origins,
+                             [part(r, search) for r, search in enumerate(searches) if search is not None], dev)
+
+
+class _RowsPart(NamedTuple):
+    """One radar's share of a stacked CSR (:func:`_stacked_geometry`)."""
+    radar: int              # its index: its gates are numbered from gate_offsets[radar]
+    search: RoiSearch       # this build's own: the index column of its sorted gates gets the offset
+    rows: Callable          # a tensor over the shared rows -> the view of the rows this radar serves, in its own order
+    count: Callable         # () -> int32 neighbour counts, shaped like that view
+    fill: Callable          # (base, gate_idx, weights): write its pairs of row v from position base[v] (contiguous) on
+
+
+def _stacked_geometry(grid_shape, grid_limits, toa, counts, origins, parts: Iterable[_RowsPart], dev) -> GridGeometry:
+    """The one row-stacking builder: the CSR whose row v is the first part's row v, then the second's, and so on, as a
+    mosaic geometry (``.gate_offsets``, ``.origins``).  ``parts`` may be a generator: a part is counted as it arrives."""
+    torch = _native.torch_mod()
+    n_rows = int(np.prod(grid_shape))
     offsets = _offsets(counts)
-    # per radar: its search over its reach window (None: reaches nothing)
-    parts = []
-    for r, (gx, gy, gz, origin) in enumerate(radars):
-        w = reach_window(gx, gy, gz, (nz, ny, nx), grid_limits, origins[r], min_radius, beam_factor, toa)
-        if _window_empty(w):
-            parts.append(None)
-            continue
-        search = RoiSearch(gx, gy, gz, (nz, ny, nx), mosaic_limits(grid_limits, origins[r]), radar_altitude=0.0,
-                           min_radius=min_radius, beam_factor=beam_factor, toa=float(toa) - float(origins[r][0]),
-                           device=dev, window=w)
-        parts.append(search)
     with torch.cuda.device(dev):
-        total = torch.zeros(n_vox + 1, dtype=torch.int32, device=dev)
-        grid_counts = total[:n_vox].view(nz, ny, nx)
-        win_counts = []
-        for search in parts:
-            if search is None:
-                win_counts.append(None)
-                continue
-            iy0, iy1, ix0, ix1 = search.window
-            win_counts.append(search.count_rows()[:-1].view(search.grid_shape))
-            grid_counts[:, iy0:iy1, ix0:ix1] += win_counts[-1]
+        total = torch.zeros(n_rows + 1, dtype=torch.int32, device=dev)
+        counted = []
+        for p in parts:
+            counted.append((p, p.count()))
+            p.rows(total[:n_rows]).add_(counted[-1][1])
 
         def fill(indptr, gate_idx, weights):
-            # running cursor: indptr plus the counts of the radars already filled.  The fill kernel reads only cursor[v] as
-            # the row base and writes at absolute positions, so every radar fills its segment of each row of its window.
-            cursor = indptr[:n_vox].view(nz, ny, nx).clone()
-            for r, search in enumerate(parts):
-                if search is None:
-                    continue
-                iy0, iy1, ix0, ix1 = search.window
-                cur_w = cursor[:, iy0:iy1, ix0:ix1].contiguous()
+            # running cursor: indptr plus the counts of the radars already filled.  The fill kernels read only cursor[v] as
+            # the row base and write at absolute positions, so every radar fills its segment of each of its rows.
+            cursor = indptr[:n_rows].clone()
+            for p, n in counted:
+                base = p.rows(cursor).contiguous()
                 # the radar's gate numbers carry its offset: shift the index column of this build's copy of its sorted gates
-                search.sorted_gates.view(torch.int32).view(-1, 4)[:, 3] += int(offsets[r])
-                search.fill_rows(weighting, _native.ptr(cur_w), _native.ptr(gate_idx), _native.ptr(weights))
-                cursor[:, iy0:iy1, ix0:ix1] += win_counts[r]
-        csr = csr_from_counts(total, n_vox, fill)
-        del parts
-    geom = GridGeometry.from_device((nz, ny, nx), grid_limits, csr, toa)
+                p.search.sorted_gates.view(torch.int32).view(-1, 4)[:, 3] += int(offsets[p.radar])
+                p.fill(base, gate_idx, weights)
+                p.rows(cursor).add_(n)
+        csr = csr_from_counts(total, n_rows, fill)
+    geom = GridGeometry.from_device(grid_shape, grid_limits, csr, toa)
     geom.gate_offsets = offsets
     geom.origins = origins
     return geom
@@ -253,24 +259,37 @@ def _mosaic_layout(geometry) -> np.ndarray:
     return np.asarray(offsets, dtype=np.int64)
 
 
-def _host_concat(offsets, fields, filters, what: str):
-    """Per-radar masked fields (+ per-radar GateFilter lists) -> concatenated float32 values and uint8 exclusion mask."""
+def _host_fields(counts, fields, filters, what: str):
+    """The one intake of host fields: radar r's masked field ``fields[r]`` and its list of ``GateFilter`` ``filters[r]``
+    (``filters`` ``None``: none) -> ``[(values float32, mask uint8), ...]``, each checked against the radar's gate count."""
+    host = []
+    for r, n in enumerate(counts):
+        size = _length(np.ma.getdata(fields[r]))
+        if size != int(n):
+            raise ValueError(f"{what}: radar {r} has {int(n)} gates, its field {size}")
+        host.append(_host_field(fields[r], _coerce_filters(None if filters is None else filters[r])))
+    return host
+
+
+def _apply_through(geometry, fields: Dict[str, Sequence], filters: Dict[str, Sequence], fill_value, what: str):
+    """``apply_mosaic_multi`` proper: every named field's radars laid end to end, uploaded, one pass through the geometry."""
+    offsets = _mosaic_layout(geometry)
+    if not fields:
+        return {}
     n_radars = len(offsets) - 1
-    if len(fields) != n_radars:
-        raise ValueError(f"{what}: expected one field per radar ({n_radars}), got {len(fields)}")
-    if filters is None:
-        filters = [None] * n_radars
-    if len(filters) != n_radars:
-        raise ValueError(f"{what}: expected one filter list per radar ({n_radars}), got {len(filters)}")
-    values, masks = [], []
-    for r in range(n_radars):
-        n = int(offsets[r + 1] - offsets[r])
-        if _length(np.ma.getdata(fields[r])) != n:
-            raise ValueError(f"{what}: radar {r} has {n} gates, its field {_length(np.ma.getdata(fields[r]))}")
-        v, m = _host_field(fields[r], _coerce_filters(filters[r]))
-        values.append(v)
-        masks.append(m)
-    return np.concatenate(values), np.concatenate(masks)
+    cat = []
+    for name, per_radar in fields.items():
+        label, per_radar, flt = what.format(name), list(per_radar), filters.get(name)
+        if len(per_radar) != n_radars:
+            raise ValueError(f"{label}: expected one field per radar ({n_radars}), got {len(per_radar)}")
+        if flt is not None and len(flt) != n_radars:
+            raise ValueError(f"{label}: expected one filter list per radar ({n_radars}), got {len(flt)}")
+        host = _host_fields(np.diff(offsets), per_radar, flt, label)
+        cat.append((np.concatenate([v for v, _ in host]), np.concatenate([m for _, m in host])))
+    _check_gather(int(offsets[-1]), len(cat))
+    on_device = [_upload(v, m, _native.device()) for v, m in cat]
+    grid = _to_host(grid_fields_device(geometry, [f for f, _ in on_device], [m for _, m in on_device], fill_value=fill_value))
+    return {name: grid[i].reshape(geometry.grid_shape) for i, name in enumerate(fields)}
 
 
 def apply_mosaic(geometry: GridGeometry, fields: Sequence, additional_filters: Optional[Sequence] = None,
@@ -278,15 +297,7 @@ def apply_mosaic(geometry: GridGeometry, fields: Sequence, additional_filters: O
     """Grid one field of every radar through a mosaic geometry: ``fields[r]`` is radar r's (masked) field in the reference
     format, ``additional_filters[r]`` a list of ``GateFilter`` of radar r.  Returns a float32 grid of
     ``geometry.grid_shape``."""
-    offsets = _mosaic_layout(geometry)
-    values, mask = _host_concat(offsets, list(fields), additional_filters, "apply_mosaic")
-    _check_gather(int(offsets[-1]), 1)
-    torch = _native.torch_mod()
-    dev = _native.device()
-    f_t = torch.from_numpy(values).to(dev)
-    m_t = torch.from_numpy(mask).to(dev) if mask.any() else None
-    grid = grid_fields_device(geometry, [f_t], [m_t], fill_value=fill_value)
-    return _to_host(grid[0]).reshape(geometry.grid_shape)
+    return _apply_through(geometry, {"": fields}, {"": additional_filters}, fill_value, "apply_mosaic")[""]
 
 
 def apply_mosaic_multi(geometry: GridGeometry, fields: Dict[str, Sequence],
@@ -294,20 +305,7 @@ def apply_mosaic_multi(geometry: GridGeometry, fields: Dict[str, Sequence],
                        fill_value: float = np.nan) -> Dict[str, np.ndarray]:
     """Several fields of every radar in one pass: ``fields[name][r]`` radar r's field, ``additional_filters[name][r]`` its
     filter list (a missing name: no filters)."""
-    offsets = _mosaic_layout(geometry)
-    if additional_filters is None:
-        additional_filters = {}
-    names = list(fields.keys())
-    if not names:
-        return {}
-    host = [_host_concat(offsets, list(fields[n]), additional_filters.get(n), f"apply_mosaic_multi[{n}]") for n in names]
-    _check_gather(int(offsets[-1]), len(names))
-    torch = _native.torch_mod()
-    dev = _native.device()
-    f_ts = [torch.from_numpy(v).to(dev) for v, _ in host]
-    m_ts = [torch.from_numpy(m).to(dev) if m.any() else None for _, m in host]
-    grid = _to_host(grid_fields_device(geometry, f_ts, m_ts, fill_value=fill_value))
-    return {name: grid[i].reshape(geometry.grid_shape) for i, name in enumerate(names)}
+    return _apply_through(geometry, fields, additional_filters or {}, fill_value, "apply_mosaic_multi[{}]")
 
 
 def _check_gather(n_gates_total: int, n_fields: int) -> None:
@@ -330,24 +328,24 @@ class MosaicSearch:
                  toa: float = 17000.0, device=None):
         radars = list(radars)
         counts, origins = _check_radars(radars, max_radars=_native.RG_MAX_RADARS)
-        self.grid_shape = tuple(int(s) for s in grid_shape)
-        if len(self.grid_shape) != 3 or min(self.grid_shape) < 1:
+        shape = tuple(int(s) for s in grid_shape)
+        if len(shape) != 3 or min(shape) < 1:
             raise ValueError(f"bad grid shape {grid_shape}")
+        dev = _native.canonical_device(device)
+        self._set(shape, grid_limits, min_radius, beam_factor, toa, origins, counts, dev,
+                  *_window_searches(radars, origins, shape, grid_limits, min_radius, beam_factor, toa, dev))
+
+    def _set(self, grid_shape, grid_limits, min_radius, beam_factor, toa, origins, counts, dev, windows, searches) -> None:
+        """The one place that sets a MosaicSearch's attributes, from values either constructor has prepared."""
+        self.grid_shape = grid_shape
         self.grid_limits = grid_limits
         self.min_radius = float(min_radius)
         self.beam_factor = float(beam_factor)
         self.toa = toa
         self.origins = origins
         self.n_gates = [int(c) for c in counts]
-        self.dev = _native.canonical_device(device)
-        self.windows, self.searches = [], []
-        for r, (gx, gy, gz, _) in enumerate(radars):
-            w = reach_window(gx, gy, gz, self.grid_shape, grid_limits, origins[r], min_radius, beam_factor, toa)
-            self.windows.append(w)
-            self.searches.append(None if _window_empty(w) else RoiSearch(
-                gx, gy, gz, self.grid_shape, mosaic_limits(grid_limits, origins[r]), radar_altitude=0.0,
-                min_radius=min_radius, beam_factor=beam_factor, toa=float(toa) - float(origins[r][0]), device=self.dev,
-                window=w))
+        self.dev = dev
+        self.windows, self.searches = windows, searches
 
     @classmethod
     def for_path(cls, radars, xs, ys, z_limits, nz, min_radius: float = 250.0, beam_factor: float = 0.01746,
@@ -361,20 +359,12 @@ class MosaicSearch:
         radars = list(radars)
         counts, origins = _check_radars(radars, max_radars=_native.RG_MAX_RADARS)
         xs, ys, limits = _path_limits(xs, ys, z_limits, nz)
+        dev = _native.canonical_device(device)
+        searches = [_path_search(gx, gy, gz, origins[r], xs, ys, nz, limits, min_radius, beam_factor, toa, dev)
+                    for r, (gx, gy, gz, _) in enumerate(radars)]
         self = cls.__new__(cls)
-        self.grid_shape = (int(nz), 2, 2)
-        self.grid_limits = limits
-        self.min_radius = float(min_radius)
-        self.beam_factor = float(beam_factor)
-        self.toa = toa
-        self.origins = origins
-        self.n_gates = [int(c) for c in counts]
-        self.dev = _native.canonical_device(device)
-        self.windows, self.searches = [], []
-        for r, (gx, gy, gz, _) in enumerate(radars):
-            search = _path_search(gx, gy, gz, origins[r], xs, ys, nz, limits, min_radius, beam_factor, toa, self.dev)
-            self.windows.append((0, 0, 0, 0) if search is None else (0, 2, 0, 2))
-            self.searches.append(search)
+        self._set((int(nz), 2, 2), limits, min_radius, beam_factor, toa, origins, counts, dev,
+                  [(0, 0, 0, 0) if s is None else (0, 2, 0, 2) for s in searches], searches)
         return self
 
     @property
@@ -417,15 +407,6 @@ def _radar_frame(v: np.ndarray, o: float) -> np.ndarray:
     return (v.astype(np.float64) - float(o)).astype(np.float32)
 
 
-class _Rectangle:
-    """What ``section._check_points`` / ``section_rectangle`` read of a search: the shared grid, unwindowed."""
-
-    def __init__(self, grid_shape, grid_limits):
-        self.full_shape = tuple(int(s) for s in grid_shape)
-        self.grid_limits = grid_limits
-        self.window = (0, self.full_shape[1], 0, self.full_shape[2])
-
-
 def _path_limits(xs, ys, z_limits, nz):
     """The points as float32 host arrays, validated, and the ``grid_limits`` of their bounding box."""
     if int(nz) < 1:
@@ -436,7 +417,7 @@ def _path_limits(xs, ys, z_limits, nz):
     if xs.ndim == 1 and xs.size > 0 and xs.shape == ys.shape and np.all(np.isfinite(xs)) and np.all(np.isfinite(ys)):
         box = ((float(ys.min()), float(ys.max())), (float(xs.min()), float(xs.max())))
     limits = (tuple(float(v) for v in z_limits),) + box
-    xs, ys = _check_points(_Rectangle((int(nz), 2, 2), limits), xs, ys, "barnes2")   # raises where the box was not formed
+    xs, ys = _check_points_in(_grid_rectangle((int(nz), 2, 2), limits), xs, ys)     # raises where the box was not formed
     return xs, ys, limits
 
 
@@ -473,13 +454,6 @@ def _check_combine(combine: str, return_radar: bool, is_geometry: bool = False) 
                          "mean by construction")
 
 
-def _radar_indices(radar, sel, torch):
-    """``out_radar`` of a combine launch (table positions, 255 = none) -> indices of the radars in the MosaicSearch."""
-    lut = torch.full((256,), _native.RG_NO_RADAR, dtype=torch.uint8, device=radar.device)
-    lut[:len(sel)] = torch.tensor(sel, dtype=torch.uint8, device=radar.device)
-    return lut[radar.long()]
-
-
 def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Sequence] = None,
                          shared_masks: Optional[Sequence] = None, weighting: str = "barnes2", fill_value: float = np.nan,
                          products=None, radars: Optional[Sequence[int]] = None, combine: str = "mean",
@@ -493,8 +467,8 @@ def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Seq
     order (its gate numbering is fixed).  ``weighting`` applies to the search route only (a geometry carries its weights).
 
     ``combine`` (search route only): ``"mean"`` -- the joint weighted mean over the union of every radar's neighbours
-    (``rg_roi_grid_mosaic_f32``); ``"max"`` -- per voxel and field the largest of the radars' own means; ``"nearest_radar"``
-    -- the mean of the radar whose antenna is closest to the voxel, among those that have one
+    (the kernel of ``rg_roi_grid_mosaic_f32``); ``"max"`` -- per voxel and field the largest of the radars' own means;
+    ``"nearest_radar"`` -- the mean of the radar whose antenna is closest to the voxel, among those that have one
     (``rg_roi_grid_mosaic_combine_f32``: one launch, no per-radar grids; the rules, ties included, are in
     ``include/radargrid_hip.h``).  A radar's own mean is, bit for bit, what ``radars=[r]`` returns.  ``return_radar=True``
     (not with ``"mean"``) returns ``(grids, radar)``: ``radar`` uint8 ``[F, nz, ny, nx]``, the index in the
@@ -507,39 +481,19 @@ def mosaic_fields_device(target, fields: Sequence[Sequence], masks: Optional[Seq
     if not is_geometry and not isinstance(target, MosaicSearch):
         raise TypeError("target must be a mosaic GridGeometry or a MosaicSearch")
     _check_combine(combine, return_radar, is_geometry)
+    if not is_geometry:
+        _refuse_closest(weighting, "a mosaic")
+    call = _prepare(target, fields, masks, shared_masks, radars, "mosaic_fields_device")
     if is_geometry:
-        offsets = _mosaic_layout(target)
-        n_all = len(offsets) - 1
-        all_counts = [int(offsets[r + 1] - offsets[r]) for r in range(n_all)]
-        if radars is not None and list(radars) != list(range(n_all)):
-            raise ValueError("a mosaic geometry grids all of its radars, in order (its gate numbering is fixed)")
-        sel = list(range(n_all))
-    else:
-        if weighting not in WEIGHTINGS:
-            raise ValueError(f"Unknown weighting function: {weighting} (the mosaic has no closest-gate mode)")
-        all_counts = target.n_gates
-        sel = _select(target.n_radars, radars)
-    counts, fields, n_fields, masks, shared_masks, n_total = _check_fields(sel, all_counts, fields, masks, shared_masks)
-    if is_geometry:
-        _check_gather(n_total, n_fields)
-
-    torch = _native.torch_mod()
-    dev = fields[0][0].device
-    if dev.type != "cuda":
-        raise _native.NativeUnavailable("mosaic_fields_device needs device-resident (cuda) tensors")
-    if not is_geometry and dev != target.dev:
-        raise ValueError(f"the fields are on {dev}, the MosaicSearch on {target.dev}")
-    _check_device_inputs(fields, masks, shared_masks, counts, n_fields, torch, dev)
-
-    with torch.cuda.device(dev):
-        cat_fields, cat_field_masks, cat_shared = _concat_on_device(fields, masks, shared_masks, counts, n_fields, torch, dev)
-        if is_geometry:
+        with _native.torch_mod().cuda.device(call.dev):
             if products is not None:
-                return grid_products_device(target, cat_fields, cat_field_masks, cat_shared, products=products,
+                return grid_products_device(target, call.fields, call.masks, call.shared_mask, products=products,
                                             fill_value=fill_value)
-            return grid_fields_device(target, cat_fields, cat_field_masks, cat_shared, fill_value=fill_value)
-        grids, radar = _search_grid(target, sel, counts, cat_fields, cat_field_masks, cat_shared, weighting, fill_value,
-                                    dev, combine, return_radar)
+            return grid_fields_device(target, call.fields, call.masks, call.shared_mask, fill_value=fill_value)
+    nz, ny, nx = target.grid_shape
+    head = (target.table(call.sel, call.offsets), len(call.sel), nz, ny, nx, target.min_radius, target.beam_factor)
+    grids, radar = _launch(call, "rg_roi_grid_mosaic_combine_f32", head, (nz, ny, nx), weighting, fill_value, combine,
+                           return_radar)
     if products is not None:
         grids = ProductPlan(products, target).planes_of_grids(grids)
     return (grids, radar) if return_radar else grids
@@ -599,42 +553,68 @@ def _concat_on_device(fields, masks, shared_masks, counts, n_fields, torch, dev)
     return cat_fields, cat_field_masks, cat_masks(lambda k: shared_masks[k])
 
 
-def _combine_launcher(entry, name: str, head, weighting, n_total, fill, combine, radar):
-    """``pack_and_grid``'s launch callback for a combine entry point: the groups of fields arrive in order, each writes
-    its rows of ``radar`` (uint8 ``[F, n_out]``, or ``None``)."""
+class _Call(NamedTuple):
+    """A validated CSR-free call (:func:`_prepare`): what a launch needs besides its table."""
+    sel: List[int]            # the radars of the call: indices into the MosaicSearch (or all of a geometry's)
+    counts: List[int]         # their gate counts
+    n_total: int
+    dev: object
+    fields: list              # [F] tensors, the call's radars laid end to end
+    masks: list               # [F] tensors or None
+    shared_mask: object
+    offsets: np.ndarray       # radar sel[k]'s first gate in those tensors
+
+
+def _prepare(target, fields, masks, shared_masks, radars, who: str) -> _Call:
+    """The one route from the arguments of a device call to its launches: the radars of the call (``radars`` of a
+    :class:`MosaicSearch`, all of a mosaic geometry), every length, the device, every tensor -- then the call's radars
+    concatenated on the device.  Nothing touches the device before every check has passed."""
+    if isinstance(target, MosaicSearch):
+        all_counts, sel = target.n_gates, _select(target.n_radars, radars)
+    else:
+        all_counts = np.diff(_mosaic_layout(target)).tolist()
+        sel = list(range(len(all_counts)))
+        if radars is not None and list(radars) != sel:
+            raise ValueError("a mosaic geometry grids all of its radars, in order (its gate numbering is fixed)")
+    counts, fields, n_fields, masks, shared_masks, n_total = _check_fields(sel, all_counts, fields, masks, shared_masks)
+    if not isinstance(target, MosaicSearch):
+        _check_gather(n_total, n_fields)
+    torch = _native.torch_mod()
+    dev = fields[0][0].device
+    if dev.type != "cuda":
+        raise _native.NativeUnavailable(f"{who} needs device-resident (cuda) tensors")
+    if isinstance(target, MosaicSearch) and dev != target.dev:
+        raise ValueError(f"the fields are on {dev}, the MosaicSearch on {target.dev}")
+    _check_device_inputs(fields, masks, shared_masks, counts, n_fields, torch, dev)
+    with torch.cuda.device(dev):
+        cat = _concat_on_device(fields, masks, shared_masks, counts, n_fields, torch, dev)
+    return _Call(sel, counts, n_total, dev, *cat, _offsets(counts)[:-1])
+
+
+def _launch(call: _Call, entry: str, head: tuple, out_shape: tuple, weighting, fill_value, combine, return_radar):
+    """The one launcher of the CSR-free mosaic calls: ``call`` through the combine entry point ``entry`` of the lattice or
+    of the section (``head``: its arguments up to the weighting, the table first) under any of the three rules -- the
+    joint mean is ``RG_COMBINE_MEAN`` with a null ``out_radar``, the kernel of the mean entry points.  Returns ``(out
+    [F, *out_shape], radar)``; ``radar`` (``return_radar``, else ``None``) uint8 of that shape: indices into the
+    MosaicSearch, ``pack_and_grid``'s groups of fields having written their rows of it one after the other."""
+    torch = _native.torch_mod()
+    launch_entry = getattr(_native.load_library(), entry)
+    fill = float(np.float32(fill_value))
+    n_fields = len(call.fields)
+    radar = torch.empty((n_fields, math.prod(out_shape)), dtype=torch.uint8, device=call.dev) if return_radar else None
     done = [0]
 
     def launch(packed, nf, stride, out_view, stream):
         who = None if radar is None else radar[done[0]:done[0] + nf]
         done[0] += nf
-        _native.check(entry(*head, _native.WEIGHTINGS[weighting], _native.ptr(packed), nf, stride, n_total, fill,
-                            _native.ptr(out_view), _native.COMBINES[combine], _native.ptr(who), stream), name)
-    return launch
-
-
-def _search_grid(search: MosaicSearch, sel, counts, fields, masks, shared_mask, weighting, fill_value, dev,
-                 combine="mean", return_radar=False):
-    """``(grids, radar)``; ``radar`` is ``None`` unless asked for."""
-    lib = _native.load_library()
-    nz, ny, nx = search.grid_shape
-    n_total = sum(counts)
-    table = search.table(sel, _offsets(counts)[:-1])
-    fill = float(np.float32(fill_value))
-    if combine == "mean":
-        def launch(packed, nf, stride, out_view, stream):
-            _native.check(lib.rg_roi_grid_mosaic_f32(
-                table, len(sel), nz, ny, nx, search.min_radius, search.beam_factor, _native.WEIGHTINGS[weighting],
-                _native.ptr(packed), nf, stride, n_total, fill, _native.ptr(out_view), stream), "rg_roi_grid_mosaic_f32")
-        return pack_and_grid(dev, n_total, fields, masks, shared_mask, None, (nz, ny, nx), launch), None
-    torch = _native.torch_mod()
-    radar = torch.empty((len(fields), nz * ny * nx), dtype=torch.uint8, device=dev) if return_radar else None
-    head = (table, len(sel), nz, ny, nx, search.min_radius, search.beam_factor)
-    launch = _combine_launcher(lib.rg_roi_grid_mosaic_combine_f32, "rg_roi_grid_mosaic_combine_f32", head, weighting,
-                               n_total, fill, combine, radar)
-    grids = pack_and_grid(dev, n_total, fields, masks, shared_mask, None, (nz, ny, nx), launch)
-    if radar is not None:
-        radar = _radar_indices(radar, sel, torch).view(len(fields), nz, ny, nx)
-    return grids, radar
+        _native.check(launch_entry(*head, _native.WEIGHTINGS[weighting], _native.ptr(packed), nf, stride, call.n_total,
+                                   fill, _native.ptr(out_view), _native.COMBINES[combine], _native.ptr(who), stream), entry)
+    out = pack_and_grid(call.dev, call.n_total, call.fields, call.masks, call.shared_mask, None, out_shape, launch)
+    if radar is not None:           # table positions (255 = none) -> indices of the radars in the MosaicSearch
+        lut = torch.full((256,), _native.RG_NO_RADAR, dtype=torch.uint8, device=call.dev)
+        lut[:len(call.sel)] = torch.tensor(call.sel, dtype=torch.uint8, device=call.dev)
+        radar = lut[radar.long()].view((n_fields,) + tuple(out_shape))
+    return out, radar
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -655,7 +635,7 @@ def mosaic_section_points(search: MosaicSearch, xs, ys) -> List[Tuple[np.ndarray
     The one limitation: a radar whose lattice window is empty takes no part, as in the lattice mosaic -- on a coarse
     lattice such a radar may still reach points between the columns; :meth:`MosaicSearch.for_path` has no lattice and
     no such case."""
-    xs, ys = _check_points(_Rectangle(search.grid_shape, search.grid_limits), xs, ys, "barnes2")
+    xs, ys = _check_points_in(_grid_rectangle(search.grid_shape, search.grid_limits), xs, ys)
     nan = np.full(xs.shape, np.nan, dtype=np.float32)
     points = []
     for r, s in enumerate(search.searches):
@@ -669,14 +649,6 @@ def mosaic_section_points(search: MosaicSearch, xs, ys) -> List[Tuple[np.ndarray
         y_r[outside] = np.nan
         points.append((x_r, y_r))
     return points
-
-
-def _no_closest(weighting: str) -> None:
-    if weighting == "closest":
-        raise ValueError("weighting 'closest' is a single-radar lattice mode; a mosaic section takes barnes2, cressman or "
-                         "nearest")
-    if weighting not in WEIGHTINGS:
-        raise ValueError(f"Unknown weighting function: {weighting}")
 
 
 def mosaic_section_fields_device(search: MosaicSearch, xs, ys, fields: Sequence[Sequence], masks: Optional[Sequence] = None,
@@ -693,43 +665,21 @@ def mosaic_section_fields_device(search: MosaicSearch, xs, ys, fields: Sequence[
     uint8 ``[F, nz, n_points]``).  Every argument is validated before the device is touched."""
     if not isinstance(search, MosaicSearch):
         raise TypeError("search must be a MosaicSearch")
-    _no_closest(weighting)
+    _refuse_closest(weighting, "a mosaic section")
     _check_combine(combine, return_radar)
     all_points = mosaic_section_points(search, xs, ys)
-    sel = _select(search.n_radars, radars)
-    counts, fields, n_fields, masks, shared_masks, n_total = _check_fields(sel, search.n_gates, fields, masks, shared_masks)
+    call = _prepare(search, fields, masks, shared_masks, radars, "mosaic_section_fields_device")
+    # the points of a radar that serves at least one of them, on the device
     torch = _native.torch_mod()
-    dev = fields[0][0].device
-    if dev.type != "cuda":
-        raise _native.NativeUnavailable("mosaic_section_fields_device needs device-resident (cuda) tensors")
-    if dev != search.dev:
-        raise ValueError(f"the fields are on {dev}, the MosaicSearch on {search.dev}")
-    _check_device_inputs(fields, masks, shared_masks, counts, n_fields, torch, dev)
-    lib = _native.load_library()
+    points = [None if np.isnan(all_points[r][0]).all() else
+              (torch.from_numpy(all_points[r][0]).to(call.dev), torch.from_numpy(all_points[r][1]).to(call.dev))
+              for r in call.sel]
     nz, n_points = search.grid_shape[0], int(all_points[0][0].size)
-    fill = float(np.float32(fill_value))
-    with torch.cuda.device(dev):
-        cat_fields, cat_field_masks, cat_shared = _concat_on_device(fields, masks, shared_masks, counts, n_fields, torch, dev)
-        # the points of a radar that serves at least one of them, on the device
-        points = [None if np.isnan(all_points[r][0]).all() else
-                  (torch.from_numpy(all_points[r][0]).to(dev), torch.from_numpy(all_points[r][1]).to(dev)) for r in sel]
-        table = search.section_table(sel, _offsets(counts)[:-1], points)
-
-        if combine == "mean":
-            def launch(packed, nf, stride, out_view, stream):
-                _native.check(lib.rg_roi_section_mosaic_f32(
-                    table, len(sel), nz, n_points, search.min_radius, search.beam_factor, _native.WEIGHTINGS[weighting],
-                    _native.ptr(packed), nf, stride, n_total, fill, _native.ptr(out_view), stream),
-                    "rg_roi_section_mosaic_f32")
-            return pack_and_grid(dev, n_total, cat_fields, cat_field_masks, cat_shared, None, (nz, n_points), launch)
-        radar = torch.empty((n_fields, nz * n_points), dtype=torch.uint8, device=dev) if return_radar else None
-        head = (table, len(sel), nz, n_points, search.min_radius, search.beam_factor)
-        launch = _combine_launcher(lib.rg_roi_section_mosaic_combine_f32, "rg_roi_section_mosaic_combine_f32", head,
-                                   weighting, n_total, fill, combine, radar)
-        out = pack_and_grid(dev, n_total, cat_fields, cat_field_masks, cat_shared, None, (nz, n_points), launch)
-        if radar is None:
-            return out
-        return out, _radar_indices(radar, sel, torch).view(n_fields, nz, n_points)
+    head = (search.section_table(call.sel, call.offsets, points), len(call.sel), nz, n_points, search.min_radius,
+            search.beam_factor)
+    out, radar = _launch(call, "rg_roi_section_mosaic_combine_f32", head, (nz, n_points), weighting, fill_value, combine,
+                         return_radar)
+    return (out, radar) if return_radar else out
 
 
 def compute_mosaic_section_geometry(radars, xs, ys, z_limits, nz, min_radius: float = 250.0, beam_factor: float = 0.01746,
@@ -742,49 +692,23 @@ def compute_mosaic_section_geometry(radars, xs, ys, z_limits, nz, min_radius: fl
     segment of every row.  The result carries ``.gate_offsets``, ``.origins``, ``.section_x``, ``.section_y`` and goes
     through :func:`apply_mosaic`, :func:`apply_mosaic_multi`, :func:`mosaic_fields_device` and ``save_geometry`` like a
     lattice mosaic geometry."""
-    _no_closest(weighting)
+    _refuse_closest(weighting, "a mosaic section")
     radars = list(radars)
     counts, origins = _check_radars(radars)
     xs, ys, limits = _path_limits(xs, ys, z_limits, nz)
-    nz, n_points = int(nz), int(xs.size)
-    n_rows = nz * n_points
-    offsets = _offsets(counts)
-    torch = _native.torch_mod()
-    lib = _native.load_library()
+    _native.load_library()
     dev = _native.device()
-    from .section import _section_args
-    with torch.cuda.device(dev):
-        stream = _native.stream_ptr()
-        parts = []        # per radar that reaches the path: (r, search, the ten leading arguments, its points, its row lengths)
-        total = torch.zeros(n_rows + 1, dtype=torch.int32, device=dev)
+
+    def parts():        # per radar that reaches the path: its search is built, then counted, before the next radar's
         for r, (gx, gy, gz, _) in enumerate(radars):
             search = _path_search(gx, gy, gz, origins[r], xs, ys, nz, limits, min_radius, beam_factor, toa, dev)
-            if search is None:
-                continue
-            pts = (torch.from_numpy(_radar_frame(xs, origins[r][2])).to(dev),
-                   torch.from_numpy(_radar_frame(ys, origins[r][1])).to(dev))
-            head = _section_args(search, *pts)
-            row_counts = torch.zeros(n_rows + 1, dtype=torch.int32, device=dev)
-            _native.check(lib.rg_section_count_f32(*head, _native.ptr(row_counts), stream), "rg_section_count_f32")
-            total += row_counts
-            parts.append((r, search, head, pts, row_counts))
-
-        def fill(indptr, gate_idx, weights):
-            # running cursor: the fill kernel reads only cursor[row] as the row base and writes at absolute positions
-            cursor = indptr[:n_rows].clone()
-            for r, search, head, _, row_counts in parts:
-                # the radar's gate numbers carry its offset: shift the index column of this build's copy of its sorted gates
-                search.sorted_gates.view(torch.int32).view(-1, 4)[:, 3] += int(offsets[r])
-                _native.check(lib.rg_section_fill_f32(*head, _native.WEIGHTINGS[weighting], _native.ptr(cursor),
-                                                      _native.ptr(gate_idx), _native.ptr(weights), stream),
-                              "rg_section_fill_f32")
-                cursor += row_counts[:n_rows]
-        csr = csr_from_counts(total, n_rows, fill)
-        del parts
+            if search is not None:
+                rows = _PathRows(search, _radar_frame(xs, origins[r][2]), _radar_frame(ys, origins[r][1]))
+                yield _RowsPart(r, search, lambda shared: shared, lambda rows=rows: rows.count()[:-1],
+                                lambda *csr_arrays, rows=rows: rows.fill(weighting, *csr_arrays))
     z_lim = tuple(float(v) for v in z_limits)
-    geom = GridGeometry.from_device((nz, 1, n_points), (z_lim, (0.0, 0.0), (0.0, _cumulative_distance(xs, ys))), csr, toa)
-    geom.gate_offsets = offsets
-    geom.origins = origins
+    geom = _stacked_geometry((int(nz), 1, int(xs.size)), (z_lim, (0.0, 0.0), (0.0, _cumulative_distance(xs, ys))), toa,
+                             counts, origins, parts(), dev)
     geom.section_x, geom.section_y = xs, ys
     return geom
 
@@ -799,25 +723,15 @@ def mosaic_vertical_section(radars, fields: Sequence, vertices, spacing, z_limit
     s float64 [n_points])`` -- :func:`mosaic_section_fields_device` on :meth:`MosaicSearch.for_path`, with its ``combine``
     rule (``"mean"``, ``"max"`` or ``"nearest_radar"``)."""
     xs, ys, s = section_path(vertices, spacing)
-    _no_closest(weighting)
+    _refuse_closest(weighting, "a mosaic section")
     _check_combine(combine, False)
-    radars = list(radars)
+    radars, fields = list(radars), list(fields)
     counts, _ = _check_radars(radars, max_radars=_native.RG_MAX_RADARS)
-    fields = list(fields)
-    if additional_filters is None:
-        additional_filters = [None] * len(radars)
-    if len(fields) != len(radars) or len(additional_filters) != len(radars):
+    if len(fields) != len(radars) or (additional_filters is not None and len(additional_filters) != len(radars)):
         raise ValueError(f"mosaic_vertical_section: expected one field and one filter list per radar ({len(radars)})")
-    host = []
-    for r, n in enumerate(counts):
-        v, m = _host_field(fields[r], _coerce_filters(additional_filters[r]))
-        if v.size != n:
-            raise ValueError(f"mosaic_vertical_section: radar {r} has {n} gates, its field {v.size}")
-        host.append((v, m))
+    host = _host_fields(counts, fields, additional_filters, "mosaic_vertical_section")
     search = MosaicSearch.for_path(radars, xs, ys, z_limits, nz, min_radius, beam_factor, toa)
-    torch = _native.torch_mod()
-    f_ts = [[torch.from_numpy(v).to(search.dev)] for v, _ in host]
-    m_ts = [[torch.from_numpy(m).to(search.dev) if m.any() else None] for _, m in host]
-    out = mosaic_section_fields_device(search, xs, ys, f_ts, m_ts, weighting=weighting, fill_value=fill_value,
-                                       combine=combine)
+    on_device = [_upload(v, m, search.dev) for v, m in host]
+    out = mosaic_section_fields_device(search, xs, ys, [[f] for f, _ in on_device], [[m] for _, m in on_device],
+                                       weighting=weighting, fill_value=fill_value, combine=combine)
     return _to_host(out[0]), s

@@ -51,43 +51,77 @@ def section_path(vertices, spacing: float) -> Tuple[np.ndarray, np.ndarray, np.n
     return xs.astype(np.float32), ys.astype(np.float32), s
 
 
+def _host(a):
+    """A tensor (any device) -> NumPy; anything else as it is."""
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else a
+
+
+def _length(a) -> int:
+    """Element count of a NumPy array, torch tensor or sequence -- without touching a device."""
+    if hasattr(a, "numel"):
+        return int(a.numel())
+    if hasattr(a, "size") and not callable(a.size):
+        return int(a.size)
+    return len(a)
+
+
+def _upload(values: np.ndarray, mask: np.ndarray, dev):
+    """A host field (``gridding._host_field``) on ``dev``: ``(values, mask)`` tensors, the mask only where it excludes a gate."""
+    torch = _native.torch_mod()
+    return torch.from_numpy(values).to(dev), torch.from_numpy(mask).to(dev) if mask.any() else None
+
+
+def _grid_rectangle(grid_shape, grid_limits, window=None) -> Tuple[float, float, float, float]:
+    """``(x_min, x_max, y_min, y_max)`` of the columns ``window = (iy0, iy1, ix0, ix1)`` (default: all) of a grid: the ends
+    of its float32 coordinate tables there.  Host arithmetic: the tables are NumPy's float32 ``linspace``
+    (``compute.py:185-186``), recomputed here rather than read back."""
+    _, ny, nx = grid_shape
+    iy0, iy1, ix0, ix1 = (0, ny, 0, nx) if window is None else window
+    yc = np.linspace(grid_limits[1][0], grid_limits[1][1], ny, dtype="float32")[iy0:iy1]
+    xc = np.linspace(grid_limits[2][0], grid_limits[2][1], nx, dtype="float32")[ix0:ix1]
+    return float(xc.min()), float(xc.max()), float(yc.min()), float(yc.max())
+
+
 def section_rectangle(search) -> Tuple[float, float, float, float]:
     """``(x_min, x_max, y_min, y_max)`` of the sample points a search structure serves: the xy rectangle of its
     ``grid_limits`` -- the ends of its float32 coordinate tables -- and for a windowed search the window's coordinate
     range.  The cell lattice and the padding by the largest radius of influence are proven only there.  Host arithmetic:
     the tables are NumPy's float32 ``linspace`` (``compute.py:185-186``), recomputed here rather than read back."""
-    _, ny, nx = search.full_shape
-    iy0, iy1, ix0, ix1 = search.window
-    yc = np.linspace(search.grid_limits[1][0], search.grid_limits[1][1], ny, dtype="float32")[iy0:iy1]
-    xc = np.linspace(search.grid_limits[2][0], search.grid_limits[2][1], nx, dtype="float32")[ix0:ix1]
-    return float(xc.min()), float(xc.max()), float(yc.min()), float(yc.max())
+    return _grid_rectangle(search.full_shape, search.grid_limits, search.window)
 
 
-def _check_points(search, xs, ys, weighting: str):
-    """The points as contiguous float32 host arrays, refused (``ValueError``) before anything touches the device."""
+def _refuse_closest(weighting: str, what: str = "a section") -> None:
+    """The weightings of a section (of ``what``): no closest-gate mode; raises ValueError, touches no device."""
     if weighting == "closest":
-        raise ValueError("weighting 'closest' is a single-radar lattice mode; a section takes barnes2, cressman or nearest")
+        raise ValueError(f"weighting 'closest' is a single-radar lattice mode; {what} takes barnes2, cressman or nearest")
     if weighting not in WEIGHTINGS:
         raise ValueError(f"Unknown weighting function: {weighting}")
-    if type(xs).__module__.startswith("torch"):
-        xs = xs.detach().cpu().numpy()
-    if type(ys).__module__.startswith("torch"):
-        ys = ys.detach().cpu().numpy()
-    xs = np.ascontiguousarray(xs, dtype=np.float32)
-    ys = np.ascontiguousarray(ys, dtype=np.float32)
+
+
+def _check_points_in(rectangle, xs, ys):
+    """The points as contiguous float32 host arrays, refused (``ValueError``) unless they are finite, one-dimensional, of
+    equal length, at least one, and inside ``rectangle = (x0, x1, y0, y1)`` (its rim included).  Touches no device."""
+    xs = np.ascontiguousarray(_host(xs), dtype=np.float32)
+    ys = np.ascontiguousarray(_host(ys), dtype=np.float32)
     if xs.ndim != 1 or ys.ndim != 1 or xs.shape != ys.shape:
         raise ValueError(f"xs and ys must be one-dimensional and of equal length, not {xs.shape} and {ys.shape}")
     if xs.size == 0:
         raise ValueError("a section needs at least one point (n_points == 0)")
     if not (np.all(np.isfinite(xs)) and np.all(np.isfinite(ys))):
         raise ValueError("xs and ys must be finite (NaN or infinite coordinate)")
-    x0, x1, y0, y1 = section_rectangle(search)
+    x0, x1, y0, y1 = rectangle
     bad = (xs < x0) | (xs > x1) | (ys < y0) | (ys > y1)
     if bad.any():
         i = int(np.argmax(bad))
         raise ValueError(f"point {i} = ({xs[i]}, {ys[i]}) lies outside the rectangle x [{x0}, {x1}], y [{y0}, {y1}] the "
                          f"search was built for ({int(bad.sum())} of {xs.size} points do)")
     return xs, ys
+
+
+def _check_points(search, xs, ys, weighting: str):
+    """The weighting and the points of a section on ``search``, refused before anything touches the device."""
+    _refuse_closest(weighting)
+    return _check_points_in(section_rectangle(search), xs, ys)
 
 
 def _cumulative_distance(xs: np.ndarray, ys: np.ndarray) -> float:
@@ -127,6 +161,33 @@ def _section_args(search: RoiSearch, xs_t, ys_t):
             search.beam_factor)
 
 
+class _PathRows:
+    """The count and fill pair of one path search (``rg_section_count_f32`` / ``rg_section_fill_f32``): the rows
+    ``k * n_points + i`` of the points ``(xs[i], ys[i])`` -- float32 host arrays in the frame of ``search`` -- times its
+    levels.  Keeps the points alive on the device; call it under ``torch.cuda.device(search.dev)``."""
+
+    def __init__(self, search: RoiSearch, xs: np.ndarray, ys: np.ndarray):
+        torch = _native.torch_mod()
+        self.points = torch.from_numpy(xs).to(search.dev), torch.from_numpy(ys).to(search.dev)
+        self.head = _section_args(search, *self.points)
+        self.n_rows = search.grid_shape[0] * int(xs.size)
+        self.dev = search.dev
+
+    def count(self):
+        """int32 ``[n_rows + 1]``: every row's number of neighbours and a trailing zero."""
+        torch = _native.torch_mod()
+        counts = torch.zeros(self.n_rows + 1, dtype=torch.int32, device=self.dev)
+        _native.check(_native.load_library().rg_section_count_f32(*self.head, _native.ptr(counts), _native.stream_ptr()),
+                      "rg_section_count_f32")
+        return counts
+
+    def fill(self, weighting: str, indptr, gate_idx, weights) -> None:
+        """Row v's pairs go to positions ``indptr[v] ...`` of the two arrays."""
+        _native.check(_native.load_library().rg_section_fill_f32(
+            *self.head, _native.WEIGHTINGS[weighting], _native.ptr(indptr), _native.ptr(gate_idx), _native.ptr(weights),
+            _native.stream_ptr()), "rg_section_fill_f32")
+
+
 def compute_section_geometry(search: RoiSearch, xs, ys, weighting: str = "barnes2") -> GridGeometry:
     """The section's CSR as an ordinary geometry: ``grid_shape (nz, 1, n_points)``, row ``k * n_points + i`` holding the
     gates within the radius of influence of ``(xs[i], ys[i], z_k)`` and their weights (float64-exact, rounded to float32,
@@ -135,20 +196,10 @@ def compute_section_geometry(search: RoiSearch, xs, ys, weighting: str = "barnes
     ``(z_limits, (0.0, 0.0), (0.0, s_last))`` with ``s_last`` the cumulative point-to-point distance; the points
     themselves are kept as ``.section_x`` / ``.section_y`` (``save_geometry`` writes the reference's nine keys only)."""
     xs, ys = _check_points(search, xs, ys, weighting)
-    torch = _native.torch_mod()
-    lib = _native.load_library()
-    dev = search.dev
     nz, n_points = search.grid_shape[0], int(xs.size)
-    n_rows = nz * n_points
-    with torch.cuda.device(dev):
-        stream = _native.stream_ptr()
-        xs_t, ys_t = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
-        head = _section_args(search, xs_t, ys_t)
-        counts = torch.zeros(n_rows + 1, dtype=torch.int32, device=dev)
-        _native.check(lib.rg_section_count_f32(*head, _native.ptr(counts), stream), "rg_section_count_f32")
-        csr = csr_from_counts(counts, n_rows, lambda indptr, gate_idx, weights: _native.check(lib.rg_section_fill_f32(
-            *head, _native.WEIGHTINGS[weighting], _native.ptr(indptr), _native.ptr(gate_idx), _native.ptr(weights), stream),
-            "rg_section_fill_f32"))
+    with _native.torch_mod().cuda.device(search.dev):
+        rows = _PathRows(search, xs, ys)
+        csr = csr_from_counts(rows.count(), rows.n_rows, lambda *csr_arrays: rows.fill(weighting, *csr_arrays))
     z_limits = tuple(float(v) for v in search.grid_limits[0])
     geom = GridGeometry.from_device((nz, 1, n_points), (z_limits, (0.0, 0.0), (0.0, _cumulative_distance(xs, ys))),
                                     csr, search.toa)
@@ -169,18 +220,13 @@ def vertical_section(gate_x, gate_y, gate_z, field_data, vertices, spacing, z_li
     nz = int(nz)
     if nz < 1:
         raise ValueError(f"nz must be at least 1, not {nz}")
-    if weighting == "closest":
-        raise ValueError("weighting 'closest' is a single-radar lattice mode; a section takes barnes2, cressman or nearest")
-    if weighting not in WEIGHTINGS:
-        raise ValueError(f"Unknown weighting function: {weighting}")
+    _refuse_closest(weighting)
     values, mask = _host_field(field_data, _coerce_filters(additional_filters))
     limits = (tuple(float(v) for v in z_limits), (float(ys.min()), float(ys.max())), (float(xs.min()), float(xs.max())))
     search = RoiSearch(gate_x, gate_y, gate_z, (nz, 2, 2), limits, radar_altitude=radar_altitude, min_radius=min_radius,
                        beam_factor=beam_factor, toa=toa)
     if values.size != search.n_gates:
         raise ValueError(f"field_data has {values.size} values for {search.n_gates} gates")
-    torch = _native.torch_mod()
-    f_t = torch.from_numpy(values).to(search.dev)
-    m_t = torch.from_numpy(mask).to(search.dev) if mask.any() else None
+    f_t, m_t = _upload(values, mask, search.dev)
     out = section_fields_device(search, xs, ys, [f_t], [m_t], weighting=weighting, fill_value=fill_value)
     return _to_host(out[0]), s
