@@ -40,7 +40,8 @@ extern "C" {
  * (no signature changed: a 102 library answers RG_EUNSUPPORTED for 5-8); 104 rg_cellgrid.levels + the per-level gate lists
  * (rg_geom_bin_levels_count / rg_geom_bin_gates_levels_f32); still 104: the packed records' two codings -- no signature
  * changed, rg_csr_compact_pack_dense was ADDED (a library without it fails to bind by name) and rg_csr_compact_pack refuses work; the
- * mosaic combine rules -- rg_roi_grid_mosaic_combine_f32 and rg_roi_section_mosaic_combine_f32 were ADDED, no signature changed; the column profile -- rg_column_profile_f32 was ADDED. */
+ * mosaic combine rules -- rg_roi_grid_mosaic_combine_f32 and rg_roi_section_mosaic_combine_f32 were ADDED, no signature changed; the column profile -- rg_column_profile_f32 was ADDED;
+ * georeferencing -- rg_gates_to_frame_f32 and rg_frame_to_lonlat_f64 were ADDED. */
 #define RG_VERSION 104
 #define RG_MAX_FIELDS 8
 
@@ -783,6 +784,50 @@ int rg_csr_compact_fill(const void* indptr, int32_t indptr_is_i64, const int32_t
                         int64_t line_len, int64_t lines_per_plane, const int64_t* dict_ptr,
                         const uint8_t* chunk_rounds, int32_t* dict, uint16_t* local_idx, int32_t* error_flag,
                         rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Georeferencing: a radar's gates into the plane of a shared grid, and a grid's nodes to longitude / latitude.  (No
+ * reference counterpart in radar_grid; the projection is PyART's `pyart_aeqd` -- azimuthal equidistant on a SPHERE of
+ * radius 6370997 m -- restated from its formulas.  PyART is not in the tree: parity with it is unpinned.)
+ *
+ * rg_georef is a HOST struct, filled once in float64 (radar_processor_amd/georef.py: make_georef) and passed by value to
+ * the kernels, which evaluate no trigonometry of its constants.  Angles in radians.
+ *   inverse, plane (x, y) about (lon_from, lat_from) -> (lon, lat):
+ *     rho = hypot(x, y); c = rho / radius; (sc, cc) = sincos(c)
+ *     lat = asin(clamp(cc * sin_lat_from + y * sc * cos_lat_from / rho, -1, 1))
+ *     lon = lon_from + atan2(x * sc, rho * cos_lat_from * cc - y * sin_lat_from * sc)
+ *     rho == 0: the centre (lon_from, lat_from).
+ *   forward, (lon, lat) -> plane about (lon_to, lat_to):
+ *     d = lon - lon_to; (sp, cp) = sincos(lat); (sd, cd) = sincos(d)
+ *     a = cp * sd;  b = cos_lat_to * sp - sin_lat_to * cp * cd;  q = sin_lat_to * sp + cos_lat_to * cp * cd
+ *     s = hypot(a, b); k = atan2(s, q) / s (1 where s == 0);  X = radius * k * a;  Y = radius * k * b
+ * Every step is float64, unfused, in the order written; results are rounded once.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rg_georef {
+  double radius;                               /* of the sphere, metres: finite, > 0 */
+  double lon_from, lat_from;                   /* centre of the plane the inputs lie in */
+  double sin_lat_from, cos_lat_from;
+  double lon_to, lat_to;                       /* centre of the plane of the outputs (rg_gates_to_frame_f32 only) */
+  double sin_lat_to, cos_lat_to;
+  double ox, oy;                               /* forward(lon_from, lat_from): the `from` centre in the `to` plane */
+  int32_t same_centre;                         /* 1: both centres are the same point (ox = oy = 0): copy, do not project */
+  int32_t reserved;
+} rg_georef;
+
+/* x_out[i] = (float)(X - ox), y_out[i] = (float)(Y - oy) with (X, Y) = forward(inverse(x[i], y[i])): gate i of a radar at
+ * the `from` centre, relative to its antenna's position (ox, oy) in the plane about the `to` centre.  A gate whose x or y
+ * is not finite gives NaN in both outputs; rho == 0 gives (0, 0).  same_centre: x and y are copied bit for bit, whatever
+ * they hold.  One thread per gate.  An input may BE an output (equal pointers: in place); arrays that overlap in any other
+ * way are refused (RG_EINVAL), as are null pointers, n < 0 and a radius or any other member that is not finite.  n == 0
+ * returns RG_OK without a launch. */
+int rg_gates_to_frame_f32(const float* x, const float* y, int64_t n, const rg_georef* radar_to_grid, float* x_out,
+                          float* y_out, rg_stream_t stream);
+/* lon[iy*nx + ix], lat[iy*nx + ix] (float64 degrees, lon in [-180, 180)) = inverse(xc[ix], yc[iy]) about the `from` centre
+ * of `grid`: the geographic position of every node of a grid's float32 coordinate tables.  One thread per node.  A table
+ * entry that is not finite gives NaN in both planes.  Refusals as above (every member of `grid` must be finite); ny == 0 or
+ * nx == 0 returns RG_OK without a launch. */
+int rg_frame_to_lonlat_f64(const float* xc, const float* yc, int32_t ny, int32_t nx, const rg_georef* grid, double* lon,
+                           double* lat, rg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,8 @@ from .mosaic import (MOSAIC_COMBINES, NO_RADAR, MosaicSearch, apply_mosaic, appl
                      mosaic_section_points, mosaic_vertical_section, path_reach, reach_window)
 from .section import (compute_section_geometry, section_fields_device, section_path, section_rectangle,
                       vertical_section)
+from .georef import (AEQD_EARTH_RADIUS, geographic_to_grid, grid_lonlat_device, grid_to_geographic, place_gates_device,
+                     place_radar, place_radars, section_path_lonlat)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -56,6 +58,8 @@ __all__ = [
     "mosaic_section_points", "path_reach", "mosaic_section_fields_device", "compute_mosaic_section_geometry",
     "mosaic_vertical_section",
     "section_path", "section_rectangle", "section_fields_device", "compute_section_geometry", "vertical_section",
+    "AEQD_EARTH_RADIUS", "geographic_to_grid", "grid_to_geographic", "place_gates_device", "place_radar", "place_radars",
+    "section_path_lonlat", "grid_lonlat_device",
     "column_profile", "echo_top", "echo_base", "vertically_integrated_liquid",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",

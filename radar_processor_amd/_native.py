@@ -73,6 +73,14 @@ class PlaneTest(Structure):
     _fields_ = [("plane", c_void_p), ("lo", c_float), ("hi", c_float), ("flags", c_int32)]
 
 
+class Georef(Structure):
+    """``rg_georef``: the float64 constants of a re-projection between two AEQD planes (``georef.make_georef`` fills it)."""
+    _fields_ = [("radius", c_double), ("lon_from", c_double), ("lat_from", c_double), ("sin_lat_from", c_double),
+                ("cos_lat_from", c_double), ("lon_to", c_double), ("lat_to", c_double), ("sin_lat_to", c_double),
+                ("cos_lat_to", c_double), ("ox", c_double), ("oy", c_double), ("same_centre", c_int32),
+                ("reserved", c_int32)]
+
+
 RG_MAX_SEL_PLANES = 4       # level selections (constant-elevation PPIs) one planes-mode launch samples
 RG_PPI_SEL_NONE = -1
 
@@ -197,6 +205,9 @@ SIGNATURES = {
     "rg_nan_minmax": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
     "rg_colormap_rgba": (c_int32, [c_void_p, c_int32, c_int64, c_double, c_double, c_int32, c_double, c_void_p,
                                    c_int32, c_void_p, c_void_p]),
+    "rg_gates_to_frame_f32": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(Georef), c_void_p, c_void_p, c_void_p]),
+    "rg_frame_to_lonlat_f64": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, POINTER(Georef), c_void_p, c_void_p,
+                                         c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -34,6 +34,7 @@ SOURCES = [
     ("rg_roi_grid.hip", []),
     ("rg_roi_section.hip", []),
     ("rg_raster.hip", []),
+    ("rg_georef.hip", []),
 ]
 
 # Every translation unit is built with FP contraction OFF: the parity contract is NumPy's arithmetic, which

@@ -2,7 +2,8 @@
 
 Each radar gives float32 gate coordinates relative to its antenna (what ``get_gate_coordinates`` returns) and its
 ``origin = (oz, oy, ox)``: the antenna position in the grid frame, in metres, in the axis order of ``grid_limits``.  Gates
-are translated into the grid frame, not rotated or re-projected.
+are translated into the grid frame, not rotated or re-projected.  Radars that stand apart need the re-projection first:
+``georef.place_radar`` / ``place_radars`` make the tuple from each radar's longitude, latitude and altitude.
 
 Radar r's contribution to voxel v is row v of ``compute_grid_geometry(gx_r, gy_r, gz_r, grid_shape,
 mosaic_limits(grid_limits, o_r), ..., radar_altitude=0.0, toa=toa - oz_r)`` -- the reference's neighbour set and weights
