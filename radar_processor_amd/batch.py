@@ -131,10 +131,8 @@ class VolumeBatch:
         self.dev = geometry.dev if self.fused else _native.canonical_device(device)
         if not 1 <= len(self.field_names) <= _native.RG_MAX_FIELDS:
             raise ValueError("1..8 fields per volume")
-        # measured on the bench grid (ms per fused pass): row-wise kernel over the packed records 7.9 / 8.7 / 10.1 / 10.5 / 15.5
-        # for 1 / 2 / 3 / 4 / 8 field-volumes (1.9 ms each at eight, where the geometry's LDS window admits eight: decided per
-        # geometry by gridding.fields_per_pass, on first use), rg_csr_apply_f32 13.1 / 14.9 / 18.8 / 20.7 and 55.1 for eight;
-        # the CSR-free gridder keeps gaining up to 8 because it shares the whole neighbour search
+        # volumes per pass: the CSR path is decided per geometry, on first use (pass_policy.volumes_per_pass_cap, with the
+        # measurements); the CSR-free gridder keeps gaining up to 8 because it shares the whole neighbour search
         self._cap = _native.RG_MAX_FIELDS if self.fused else None
 
     @property

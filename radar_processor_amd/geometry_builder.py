@@ -21,7 +21,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _native
+from . import _native, pass_policy
 from . import grid_geometry
 from .compact_layout import ChunkLayout
 from .grid_geometry import CompactCSR, DeviceCSR, GridGeometry, scan_counts
@@ -272,7 +272,6 @@ def csr_from_counts(counts, n_rows: int, fill) -> DeviceCSR:
 # multiple of 8 (the kernels OR it back in) and at most 7 below the largest exponent a weight can have.  barnes2:
 # exp(-4)+1e-5 = 2^-6 * 1.17 (exponent 121) .. 1+1e-5 (127); nearest: 1.0 (127)
 _PACK_BASE_EXPONENT = {"barnes2": 120, "nearest": 120}
-_AUTO_PACKED_MIN_PAIRS = 50_000_000      # layout="auto": from here on the packed layout alone (gridding._COMPACT_MIN_PAIRS)
 
 
 def _build_compact_only(search: "RoiSearch", weighting: str, pairs_per_slab: int = 1_200_000_000, packed: bool = False):
@@ -437,19 +436,11 @@ def compute_grid_geometry(
     if layout not in ("csr", "compact", "packed", "auto"):
         raise ValueError("layout must be 'csr', 'compact', 'packed' or 'auto'")
     if layout == "auto":
-        # Large geometries whose weights fit the 26-bit code (Barnes, uniform) are built in the packed layout ALONE: row
-        # pointers + dictionaries + 16-byte records, 5.4 bytes per pair -- it is what every gridding pass of 1-8 fields reads
-        # anyway, the reference's index and weight arrays are rebuilt from it on demand, bit for bit (CompactCSR.decode /
-        # decode_weights: save_geometry, the CPU baseline, the bench's post-check), and a process touches 47 GB instead of
-        # 115 GB for the bench geometry (first-touch allocation is what a build's wall time consists of).  Geometries below
-        # 50 M pairs grid in well under a millisecond either way and keep the reference's arrays; non-codable weights
-        # (Cressman) keep them too when they and their compact copy fit, and fall to the compact layout otherwise.
+        # pass_policy.choose_layout; the reference's arrays are rebuilt from a packed layout on demand (CompactCSR.decode /
+        # decode_weights: save_geometry, the CPU baseline, the bench's post-check)
         n_pairs = search.count_pairs()
         free_b, _ = _native.torch_mod().cuda.mem_get_info(search.dev)
-        if n_pairs >= _AUTO_PACKED_MIN_PAIRS and weighting in _PACK_BASE_EXPONENT:
-            layout = "packed"
-        else:
-            layout = "csr" if 10.4 * n_pairs + (10 << 30) <= free_b else "compact"
+        layout = pass_policy.choose_layout(n_pairs, free_b, weighting in _PACK_BASE_EXPONENT)
         logger.info(f"{n_pairs:,} pairs, {free_b / 1e9:.0f} GB free -> layout '{layout}'")
     if layout == "packed":
         built = _build_compact_only(search, weighting, packed=True)

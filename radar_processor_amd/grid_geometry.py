@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _native
+from . import _native, pass_policy
 from .compact_layout import ChunkLayout, check_sidecar, unpack_records
 
 logger = logging.getLogger("radar_grid.geometry")  # same logger name as the reference (docs/LOGGING.md:128-141)
@@ -188,7 +188,7 @@ class CompactCSR:
         if csr.n_pairs == 0 or self.local_idx is None or csr.weights is None:
             return False
         free_b, _ = torch.cuda.mem_get_info(dev)
-        if free_b < 5.6 * csr.n_pairs + (6 << 30):
+        if not pass_policy.packed_records_fit(csr.n_pairs, free_b):
             return False
         # codable?  exponent range of the weights (float32 bits >> 23; a sign bit would show up as an exponent >= 256)
         lo, hi = None, None
@@ -197,8 +197,8 @@ class CompactCSR:
             e = csr.weights[p0:p0 + step].view(torch.int32) >> 23
             a, b = int(e.min()), int(e.max())
             lo, hi = (a if lo is None else min(lo, a)), (b if hi is None else max(hi, b))
-        base = lo & ~7          # the code's base exponent: a multiple of 8, so that the kernels can OR it back in
-        if lo <= 0 or hi - base > 7 or hi >= 255:
+        base = pass_policy.weight_code_base(lo, hi)
+        if base is None:
             logger.info(f"weights span exponents {lo}..{hi}: not codable in 26 bits above a base exponent that is a multiple "
                         "of 8, the compact copy keeps the plain arrays")
             return False
@@ -277,24 +277,12 @@ class CompactCSR:
 
     @staticmethod
     def entry_bytes(n_fields: int, rowwise: bool = False) -> int:
-        """Bytes of one LDS window entry of the compact kernels.  Tile kernels: the packed slots of a gate (1, 2, 4 or 8
-        floats; a 3-field entry without its padding slot).  Row-wise kernel (``rowwise``): one field the value and a 0/1
-        factor, two fields the two values, three and more the values (v' = value or +0) plus one mask byte per field -- 16,
-        20 and 40 bytes for 3, 4 and 5-8 fields (``csrc/rg_compact_layout.hpp``: rowwise_entry_words)."""
-        if rowwise and n_fields >= 3:
-            return 16 if n_fields == 3 else 20 if n_fields == 4 else 40
-        if n_fields > 4:
-            return 32
-        return 4 * (2 if n_fields <= 2 else 3 if n_fields == 3 else 4)
+        """``pass_policy.entry_bytes``: bytes of one LDS window entry of the compact kernels."""
+        return pass_policy.entry_bytes(n_fields, rowwise)
 
     def window_for(self, n_fields: int, lds_budget_bytes: Optional[int] = None, rowwise: bool = False) -> int:
-        """LDS window (entries) for a pass of ``n_fields`` fields: the geometry's 99.9 % window if its entries fit
-        ``lds_budget_bytes`` (default 32 KiB; 48 KiB for the row-wise kernel's 3-8 field entries, which carry mask bytes and
-        have no tile next to them), else the largest that does."""
-        if lds_budget_bytes is None:
-            lds_budget_bytes = 49152 if (rowwise and n_fields >= 3) else 32768
-        room = max(0, lds_budget_bytes // self.entry_bytes(n_fields, rowwise)) // 64 * 64
-        return int(min(self.window_cap, room))
+        """``pass_policy.window_for`` of this geometry's 99.9 % window: the LDS window (entries) of a pass of ``n_fields``."""
+        return pass_policy.window_for(self.window_cap, n_fields, rowwise, lds_budget_bytes)
 
     def fallback_fraction(self, window: int) -> float:
         """Share of the pairs whose chunk holds more distinct gates than ``window`` (they gather per pair)."""

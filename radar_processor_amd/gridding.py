@@ -26,7 +26,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import _native
+from . import _native, pass_policy
 from .gate_filters import GateFilter
 from .grid_geometry import GridGeometry
 from .grid_products import EFFECTIVE_RADIUS_FACTOR
@@ -99,34 +99,14 @@ class CsrGridder:
             # the reference's fancy index (interpolate.py:74) raises the same way
             raise IndexError(f"index {self.csr.max_gate} is out of bounds for axis 0 with size {self.n_gates}")
         self.packed = torch.empty(max(self.n_gates, 1) * self.stride, dtype=torch.float32, device=self.dev)
-        compact_only = self.csr.gate_indices is None
-        packed_only = self.csr.weights is None           # only the packed pair stream exists (layout="packed")
-        # Which kernel (ms per pass on config 2 / the bench grid, MI355X):
-        #                              1 field        2 fields       3 fields       4 fields       8 fields
-        #   rg_csr_apply_f32           1.9 / 13.1     2.1 / 14.7     2.3 / 16.5     3.0 / 20.5     7.3 / 49.8
-        #   compact, tile kernel       1.11 / 8.4     1.69 / 11.6    2.2 / 14.6     3.3 / 19.5     9.6 / 65
-        #   compact, row-wise kernel   1.02 / 7.9     1.13 / 8.7     1.29 / 10.1    1.47 / 10.3    3.9 / 14.4
-        # The row-wise kernel reads the packed records (weights codable in 26 bits: Barnes, nearest) and has no tile in
-        # LDS, so it wins at every window it can hold.  The tile kernel (weights not codable) wins while its
-        # window stays <= 24 KiB next to its tiles and loses beyond; a compact-only geometry has no choice.
-        want = compact or compact_only
-        self.compact = geometry.device_compact(self.dev) if (want and self.csr.n_pairs) else None
-        self.window = 0
-        self.packed_stream = False
-        if self.compact is not None:
-            self.window = self.compact.window_for(self.n_fields)
-            if not compact_only and self.compact.fallback_fraction(self.window) > _COMPACT_MAX_FALLBACK:
-                # too many chunks would gather per pair (dense scans next to many fields): the standard kernel is faster
-                self.compact, self.window = None, 0
-        if self.compact is not None:
-            # passes of 1-8 fields stream the packed records (positions + weights, 5.33 bytes per pair) when the geometry's
-            # weights allow the lossless 26-bit code and the memory is there
-            self.packed_stream = bool((packed or packed_only) and self.compact.ensure_packed(self.csr))
-            if self.packed_stream:
-                self.window = self.compact.window_for(self.n_fields, rowwise=True)
-            if (not self.packed_stream and not compact_only
-                    and self.window * self.compact.entry_bytes(self.n_fields) > _COMPACT_MAX_WINDOW_BYTES):
-                self.compact, self.window = None, 0
+        self._columns_ws = None
+        # which kernel, with which window: pass_policy.choose_pass.  The attributes stay plain: apply() dispatches from them
+        csr, copy_of = _policy_facts(geometry, self.dev)
+        choice = pass_policy.choose_pass(self.n_fields, csr.n_pairs, csr.gate_indices is not None, csr.weights is not None,
+                                         compact, packed, copy_of)
+        self.compact = choice.copy.compact if choice.use_compact else None
+        self.window = choice.window
+        self.packed_stream = choice.packed_stream
 
     def _check_fields(self, fields, masks, shared_mask):
         torch = _native.torch_mod()
@@ -159,26 +139,24 @@ class CsrGridder:
         ``rg_csr_compact_apply_f32`` through the compact copy, ``rg_csr_apply_f32`` otherwise)."""
         csr = self.csr
         nz, ny, nx = self.grid_shape
-        if self.compact is not None and self.packed_stream and (self.tile in (0, 384) or self.tile >= 2000
-                                                                or csr.weights is None):
+        kernel, tile = pass_policy.tile_override(self.tile, self.packed_stream, self.compact is not None,
+                                                 csr.weights is not None)
+        if kernel == pass_policy.KERNEL_ROWWISE:
             _native.check(self.lib.rg_csr_compact_apply_packed_f32_ex(
-                *self._stream_args(fill_value), _native.ptr(out), self.window,
-                self.tile if (self.tile == 384 or self.tile >= 2000) else 0, _native.ptr(self.compact.row_end16),
-                _native.stream_ptr()), "rg_csr_compact_apply_packed_f32")
-            return
-        if self.compact is not None:
+                *self._stream_args(fill_value), _native.ptr(out), self.window, tile, _native.ptr(self.compact.row_end16),
+                _native.stream_ptr()), kernel)
+        elif kernel == pass_policy.KERNEL_TILE:
             c = self.compact
             _native.check(self.lib.rg_csr_compact_apply_f32(
                 _native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(c.local_idx), _native.ptr(csr.weights),
                 _native.ptr(c.dict_ptr), _native.ptr(c.dict), self.n_vox, csr.n_pairs, nx, ny, _native.ptr(self.packed),
                 self.n_fields, self.stride, self.n_gates, float(np.float32(fill_value)), _native.ptr(out), self.window,
-                self.tile if self.tile in _PIPELINE_TILES else 0, _native.stream_ptr()), "rg_csr_compact_apply_f32")
-            return
-        _native.check(self.lib.rg_csr_apply_f32_ex(
-            _native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(csr.gate_indices), _native.ptr(csr.weights),
-            self.n_vox, csr.n_pairs, nx, _native.ptr(self.packed), self.n_fields, self.stride, self.n_gates,
-            float(np.float32(fill_value)), _native.ptr(out), self.tile if self.tile in _PIPELINE_TILES else 0,
-            _native.stream_ptr()), "rg_csr_apply_f32")
+                tile, _native.stream_ptr()), kernel)
+        else:
+            _native.check(self.lib.rg_csr_apply_f32_ex(
+                _native.ptr(csr.indptr), int(csr.is_i64), _native.ptr(csr.gate_indices), _native.ptr(csr.weights),
+                self.n_vox, csr.n_pairs, nx, _native.ptr(self.packed), self.n_fields, self.stride, self.n_gates,
+                float(np.float32(fill_value)), _native.ptr(out), tile, _native.stream_ptr()), kernel)
 
     def _stream_args(self, fill_value):
         """The 17 leading arguments ``rg_csr_compact_apply_packed_f32``, ``_columns_f32`` and ``_planes_f32`` share with their
@@ -193,7 +171,7 @@ class CsrGridder:
     def _columns_workspace(self, nbytes: int):
         """The grow-only device workspace of the column and planes modes (partial planes of the level pieces)."""
         torch = _native.torch_mod()
-        ws = getattr(self, "_columns_ws", None)
+        ws = self._columns_ws
         if ws is None or ws.numel() < nbytes:
             ws = self._columns_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         return ws
@@ -202,7 +180,7 @@ class CsrGridder:
     @property
     def has_columns_kernel(self) -> bool:
         """The column mode of the row-wise kernel reads the packed records: 1-4 fields, codable weights."""
-        return self.compact is not None and self.packed_stream and self.n_fields <= 4
+        return pass_policy.has_columns_kernel(self.compact is not None, self.packed_stream, self.n_fields)
 
     def _column_plan(self, z_pieces: int):
         """``(z_pieces, order tensor)`` for this geometry: enough workgroups to fill the chip (a workgroup is one column
@@ -214,7 +192,7 @@ class CsrGridder:
         nz = self.grid_shape[0]
         n_cols = c.chunks.nsx * c.chunks.nyg
         if z_pieces <= 0:
-            z_pieces = max(1, min(nz, -(-_COLUMNS_MIN_WORKGROUPS // max(n_cols, 1))))
+            z_pieces = pass_policy.column_pieces(nz, n_cols)
         z_pieces = max(1, min(int(z_pieces), nz))
         cache = c._column_orders
         order = cache.get(z_pieces)
@@ -333,7 +311,7 @@ class CsrGridder:
             return None
         nbytes = int(c.rec.numel()) * c.rec.element_size()
         free_b, _ = torch.cuda.mem_get_info(self.dev)
-        if free_b < (tries - 1) * nbytes + 4 * self.n_fields * self.n_vox + (8 << 30):
+        if not pass_policy.settle_copies_fit(nbytes, tries, 4 * self.n_fields * self.n_vox, free_b):
             return None
         with torch.cuda.device(self.dev):
             if out is None:
@@ -378,64 +356,42 @@ class CsrGridder:
                 + self.n_fields * (5 * self.n_gates + 4 * self.n_vox))
 
 
-_COLUMNS_MIN_WORKGROUPS = 8192      # column kernel: cut columns into level pieces until the launch has about this many workgroups
-_PIPELINE_TILES = (128, 192, 256, 320, 384, 512)   # pairs per pipeline step the tile kernels accept (0 = their default)
-_COMPACT_MIN_PAIRS = 50_000_000     # below this a pass takes well under a millisecond either way
-_COMPACT_MAX_WINDOW_BYTES = 24576  # LDS window beyond which the standard kernel is the faster one (CsrGridder.__init__)
-_COMPACT_MAX_FALLBACK = 0.02        # share of pairs allowed on the per-pair path before the standard kernel is preferred
+def _policy_facts(geometry: GridGeometry, dev):
+    """``(device CSR, copy_of)``: what ``pass_policy`` asks about ``geometry`` on ``dev``.  ``copy_of()`` builds (once) the
+    compact copy and yields its ``pass_policy.CopyFacts``, or ``None`` when the geometry cannot be compacted."""
+    csr = geometry.device_csr(dev)
+
+    def copy_of():
+        c = geometry.device_compact(dev)
+        return None if c is None else pass_policy.CopyFacts(c.window_cap, c.fallback_fraction, lambda: c.ensure_packed(csr), c)
+    return csr, copy_of
 
 
 def _use_compact(geometry: GridGeometry, dev) -> bool:
-    """Policy of ``grid_fields_device`` / ``apply_geometry``: a geometry large enough to matter grids through the compact
-    copy of its CSR from its FIRST pass on, provided the memory is there -- the one-time conversion costs about as much
-    as building the geometry did (15 ms per 1e9 pairs for the copy, as much again for the packed records), and deciding by
-    size alone means that every pass of a geometry runs the same kernel and returns the same bits.  Once built the copy is
-    always used.  ``GridGeometry.device_compact()`` builds it explicitly ahead of time."""
-    cached = getattr(geometry, "_compact", None)
-    if cached is not None and cached[0] is geometry.device_csr(dev):
-        return cached[1] is not None
-    n_pairs = geometry.device_csr(dev).n_pairs
-    if n_pairs < _COMPACT_MIN_PAIRS:
-        return False
-    free_b, _ = _native.torch_mod().cuda.mem_get_info(dev)
-    return free_b > 3.2 * n_pairs + (8 << 30)
-
-
-def _fields_per_pass(geometry: GridGeometry, dev, use_compact: bool) -> int:
-    """Fields one CSR pass should fuse.  Through the packed records (the row-wise kernel, 1-8 fields): 8 where the geometry's
-    LDS window holds 40-byte entries (bench grid: one pass of eight 15.5 ms against two of four 2 x 10.5), 4 where it does not
-    (config 2's 1792-entry window: one pass of eight 3.4-3.9 ms against 2 x 1.4); 8 (``RG_MAX_FIELDS``) through the other
-    kernels."""
+    """``pass_policy.use_compact`` for ``geometry`` on ``dev``: do its passes run through the compact copy of its CSR?
+    (``GridGeometry.device_compact()`` builds the copy explicitly ahead of time.)"""
     csr = geometry.device_csr(dev)
-    compact = None
-    if csr.weights is None:                 # packed-only geometry
-        compact = geometry.device_compact(dev)
-    elif use_compact and csr.n_pairs:
-        compact = geometry.device_compact(dev)
-        if compact is not None and not compact.ensure_packed(csr):
-            compact = None
-    if compact is not None:
-        return 8 if compact.window_cap * compact.entry_bytes(8, rowwise=True) <= 32768 else 4    # 5 workgroups per CU
-    return _native.RG_MAX_FIELDS
+    cached = getattr(geometry, "_compact", None)
+    state = (cached[1] is not None) if (cached is not None and cached[0] is csr) else None
+    return pass_policy.use_compact(state, csr.n_pairs, lambda: _native.torch_mod().cuda.mem_get_info(dev)[0])
+
+
+def _pass_size(policy, geometry: GridGeometry, dev, use_compact: bool) -> int:
+    csr, copy_of = _policy_facts(geometry, dev)
+    return policy(csr.n_pairs, csr.weights is not None, use_compact, copy_of)
 
 
 def fields_per_pass(geometry: GridGeometry, device=None) -> int:
     """How many fields (or field-volumes of a batch) ``grid_fields_device`` fuses into one pass over this geometry on
-    ``device`` (builds the device copy if it does not exist yet)."""
+    ``device`` (builds the device copy if it does not exist yet): ``pass_policy.fields_per_pass``."""
     dev = _native.canonical_device(device)
-    return _fields_per_pass(geometry, dev, _use_compact(geometry, dev))
+    return _pass_size(pass_policy.fields_per_pass, geometry, dev, _use_compact(geometry, dev))
 
 
 def volumes_per_pass_cap(geometry: GridGeometry, device=None) -> int:
-    """Field-volumes of a batch one pass should fuse (``batch.VolumeBatch``): what the packed records take (8 or 4, see
-    ``_fields_per_pass``); 4 through ``rg_csr_apply_f32`` (bench grid: 20.7 ms for four, 55.1 for eight)."""
+    """Field-volumes of a batch one pass should fuse (``batch.VolumeBatch``): ``pass_policy.volumes_per_pass_cap``."""
     dev = _native.canonical_device(device)
-    use_compact = _use_compact(geometry, dev)
-    csr = geometry.device_csr(dev)
-    if csr.weights is None or (use_compact and csr.n_pairs and geometry.device_compact(dev) is not None
-                               and geometry.device_compact(dev).ensure_packed(csr)):
-        return _fields_per_pass(geometry, dev, use_compact)
-    return min(4, _native.RG_MAX_FIELDS)
+    return _pass_size(pass_policy.volumes_per_pass_cap, geometry, dev, _use_compact(geometry, dev))
 
 
 def _cached_gridder(geometry: GridGeometry, n_gates: int, n_fields: int, dev, compact: bool) -> "CsrGridder":
@@ -451,6 +407,18 @@ def _cached_gridder(geometry: GridGeometry, n_gates: int, n_fields: int, dev, co
             cache.clear()
         gridder = cache[key] = CsrGridder(geometry, n_gates, n_fields, device=dev, compact=compact)
     return gridder
+
+
+def _pass_groups(geometry: GridGeometry, n_gates: int, n_fields: int, dev, cap: Optional[int] = None):
+    """Cut ``n_fields`` fields into the passes ``pass_policy`` chooses for ``geometry`` on ``dev`` (at most ``cap`` fields
+    each): yields ``(f0, f1, gridder)`` per pass, the gridder from :func:`_cached_gridder`."""
+    use_compact = _use_compact(geometry, dev)
+    per_pass = _pass_size(pass_policy.fields_per_pass, geometry, dev, use_compact)
+    if cap is not None:
+        per_pass = min(per_pass, cap)
+    for f0 in range(0, n_fields, per_pass):
+        f1 = min(n_fields, f0 + per_pass)
+        yield f0, f1, _cached_gridder(geometry, n_gates, f1 - f0, dev, compact=use_compact)
 
 
 def grid_fields_device(geometry: GridGeometry, fields: Sequence, masks: Optional[Sequence] = None,
@@ -485,11 +453,7 @@ def grid_fields_device(geometry: GridGeometry, fields: Sequence, masks: Optional
         raise ValueError("out must be a contiguous cuda float32 tensor of shape [F, nz, ny, nx]")
     n_gates = int(fields[0].numel())
     with torch.cuda.device(dev):
-        use_compact = _use_compact(geometry, dev)
-        per_pass = _fields_per_pass(geometry, dev, use_compact)
-        for f0 in range(0, n_fields, per_pass):
-            f1 = min(n_fields, f0 + per_pass)
-            gridder = _cached_gridder(geometry, n_gates, f1 - f0, dev, compact=use_compact)
+        for f0, f1, gridder in _pass_groups(geometry, n_gates, n_fields, dev):
             gridder.pack(fields[f0:f1], masks[f0:f1], shared_mask)
             gridder.apply(out.view(n_fields, n_vox)[f0:f1], fill_value)
     return out.view(n_fields, nz, ny, nx)
@@ -517,8 +481,8 @@ class PlaneProducts:
                  ke: float = EFFECTIVE_RADIUS_FACTOR, echo_top: Sequence[float] = (), echo_base: Sequence[float] = (),
                  vil: bool = False, vil_max_dbz: float = 56.0, profile_interpolation: str = "linear"):
         """``fused``: ``True`` = take the planes out of the gridding kernel (no 3-D grid in HBM: the memory-saving way),
-        ``False`` = grid, then reduce with the separate kernels, ``None`` = whichever the build measured faster (the same
-        planes either way, bit for bit).  ``ppi``: elevation angles (degrees); ``ppi_interpolation`` / ``earth_curvature`` /
+        ``False`` and ``None`` (the default) = grid, then reduce with the separate kernels: measured, the epilogue saves
+        memory, not time (``pass_policy.run_fused``).  The same planes either way, bit for bit.  ``ppi``: elevation angles (degrees); ``ppi_interpolation`` / ``earth_curvature`` /
         ``ke`` as in ``constant_elevation_ppi`` ('linear' planes are float64, 'nearest' float32).  ``echo_top`` /
         ``echo_base``: thresholds; ``vil`` with ``vil_max_dbz``; ``profile_interpolation`` as ``column_profile``'s
         ``interpolation``."""

@@ -15,15 +15,12 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import _native
+from . import _native, pass_policy
 from . import grid_products as gp
 from .grid_geometry import GridGeometry
-from .gridding import CsrGridder, PlaneProducts, _cached_gridder, _fields_per_pass, _use_compact
+from .gridding import CsrGridder, PlaneProducts, _pass_groups
 
 RECORD_KEYS = ("colmax", "argmax", "colmin", "colmean", "cappi", "ppi", "echo_top", "echo_base", "vil")
-
-_COLUMNS_FUSE_MIN_FIELDS = 5        # grid_products_device(fused=None): field-volumes per pass from which the products epilogue pays
-                                    # in TIME -- more than a pass can hold: never by default (see grid_products_device)
 
 
 def ordered_record(planes: dict) -> dict:
@@ -157,21 +154,12 @@ def grid_products_device(geometry: GridGeometry, fields: Sequence, masks: Option
     n_gates = int(fields[0].numel())
     results = []
     with torch.cuda.device(dev):
-        use_compact = _use_compact(geometry, dev)
-        per_pass = _fields_per_pass(geometry, dev, use_compact)
-        if fused:                                # the products epilogue (column mode of the row-wise kernel) takes 1-4 fields
-            per_pass = min(per_pass, 4)
-        for f0 in range(0, n_fields, per_pass):
-            f1 = min(n_fields, f0 + per_pass)
+        # the products epilogue (column mode of the row-wise kernel) takes 1-4 fields
+        cap = pass_policy.COLUMNS_MAX_FIELDS if fused else None
+        for f0, f1, gridder in _pass_groups(geometry, n_gates, n_fields, dev, cap):
             nf = f1 - f0
-            gridder = _cached_gridder(geometry, n_gates, nf, dev, compact=use_compact)
             gridder.pack(fields[f0:f1], masks[f0:f1], shared_mask)
-            # measured (profiles/r04_columns_variants_*.json, r04_nf4_lds_rowsums.json): walking columns costs what the store it
-            # saves costs -- 8.2 vs 8.1 ms for one field, 10.7 vs 10.5 for three, 11.4 vs 11.2 for four on the bench grid --
-            # so the epilogue is the MEMORY-saving choice (no F x 640 MB of grid) and is taken on request, not by default
-            run_fused = (gridder.has_columns_kernel and not products.profile      # the profile products need the stored grid
-                         and (nf >= _COLUMNS_FUSE_MIN_FIELDS if fused is None else bool(fused)))
-            if not run_fused:
+            if not pass_policy.run_fused(gridder.has_columns_kernel, products.profile, nf, fused):
                 grids = torch.empty((nf, nz, ny, nx), dtype=torch.float32, device=dev)
                 gridder.apply(grids.view(nf, -1), fill_value)
                 results += plan.planes_of_grids(grids)

@@ -661,11 +661,12 @@ def test_interchange_file_of_the_packed_only_geometry(rg, wide, tmp_path):
 
 
 def test_layout_policy_on_a_small_grid(rg, wide, tmp_path, monkeypatch):
-    """With the packed layout's threshold lowered to 1000 pairs: ``layout="auto"`` keeps records only for Barnes and uniform
-    weights and the reference's arrays for Cressman; ``layout="packed"`` with Cressman falls to ``"compact"``; and
-    ``apply_geometry`` on each equals the ``layout="csr"`` result to rounding (conftest.assert_same_to_rounding)."""
-    from radar_processor_amd import geometry_builder
-    monkeypatch.setattr(geometry_builder, "_AUTO_PACKED_MIN_PAIRS", 1000)
+    """With the large-geometry threshold lowered to 1000 pairs (``pass_policy.LARGE_GEOMETRY_PAIRS``: the packed layout's, and
+    with it the one from which ``apply_geometry`` asks for the compact copy): ``layout="auto"`` keeps records only for Barnes
+    and uniform weights and the reference's arrays for Cressman; ``layout="packed"`` with Cressman falls to ``"compact"``;
+    and ``apply_geometry`` on each equals the ``layout="csr"`` result to rounding (conftest.assert_same_to_rounding)."""
+    from radar_processor_amd import pass_policy
+    monkeypatch.setattr(pass_policy, "LARGE_GEOMETRY_PAIRS", 1000)
     v = wide.vol
     name = sorted(v.fields)[0]
     radar = v.as_radar()
