@@ -41,7 +41,8 @@ extern "C" {
  * (rg_geom_bin_levels_count / rg_geom_bin_gates_levels_f32); still 104: the packed records' two codings -- no signature
  * changed, rg_csr_compact_pack_dense was ADDED (a library without it fails to bind by name) and rg_csr_compact_pack refuses work; the
  * mosaic combine rules -- rg_roi_grid_mosaic_combine_f32 and rg_roi_section_mosaic_combine_f32 were ADDED, no signature changed; the column profile -- rg_column_profile_f32 was ADDED;
- * georeferencing -- rg_gates_to_frame_f32 and rg_frame_to_lonlat_f64 were ADDED. */
+ * georeferencing -- rg_gates_to_frame_f32 and rg_frame_to_lonlat_f64 were ADDED; the Web Mercator warp and the overview
+ * pyramid -- rg_warp_mercator_f32, rg_warp_mercator_rgba8, rg_overview_f32 and rg_overview_rgba8 were ADDED. */
 #define RG_VERSION 104
 #define RG_MAX_FIELDS 8
 
@@ -828,6 +829,73 @@ int rg_gates_to_frame_f32(const float* x, const float* y, int64_t n, const rg_ge
  * nx == 0 returns RG_OK without a launch. */
 int rg_frame_to_lonlat_f64(const float* xc, const float* yc, int32_t ny, int32_t nx, const rg_georef* grid, double* lon,
                            double* lat, rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Onto a web map: a product plane (or its RGBA image) resampled north-up into a Web Mercator (EPSG:3857) raster, and the
+ * overview pyramid of such an image.  (Reference: radar_processor/processor.py:229-303 shells out to gdalwarp and :306-420
+ * lets rasterio build the overviews; radar_grid/geotiff.py:238-291 does not resample at all.)
+ *
+ * Two HOST structs, passed by value to the kernels like rg_georef:
+ *   rg_mercator_raster  the destination.  The pixel is square; row 0 is the NORTHERNMOST row; the centre of pixel (r, c) is
+ *                       X = x_min + (c + 0.5) * pixel,  Y = y_max - (r + 0.5) * pixel   (EPSG:3857 metres).
+ *   rg_warp_source      the float64 lattice of a plane [ny, nx]: node (iy, ix) lies at (x_lo + ix * step_x, y_lo + iy * step_y)
+ *                       of the grid's AEQD plane, step = (hi - lo) / (n - 1) > 0; row iy grows NORTHWARDS, as in every grid
+ *                       here.  The gridders' float32 node tables (np.linspace(..., dtype='float32')) differ from this lattice
+ *                       by at most half a float32 ulp of the limits -- millimetres for any grid a radar fills.
+ * The map of one destination pixel, float64, unfused, in this order:
+ *     a = 6378137 (the EPSG:3857 sphere);  t = Y / a;  sp = tanh(t);  cp = 1 / cosh(t);  lam = X / a
+ *     (sd, cd) = sincos(lam - lon_to)
+ *     (Xg, Yg) = the AEQD forward map above about (lon_to, lat_to) of the rg_georef, fed sp, cp, sd and cd;  c = atan2(s, q)
+ *     c >= pi/2 - 0.1  ->  the pixel is fill (georef.MAX_ANGULAR_DISTANCE: without it the far hemisphere folds back into
+ *                          the grid's plane)
+ *     fx = (Xg - x_lo) / step_x;  fy = (Yg - y_lo) / step_y          (plane coordinates in nodes)
+ * sp and cp are the sine and cosine of the latitude whose Mercator ordinate is Y, so no latitude is ever formed.  The map is
+ * periodic in lam: x_min may lie beyond +-pi * a (a grid across the antimeridian gets one connected raster).
+ * Longitude and latitude are carried UNCHANGED from the 6370997 m sphere of the grid to the 6378137 m sphere of EPSG:3857 --
+ * what a PROJ pipeline with no datum shift does.  Parity with gdalwarp is UNPINNED: GDAL, pyproj and rasterio are not in the
+ * tree; the tests pin the map against a 40-digit evaluation of these formulas.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rg_mercator_raster {
+  double x_min, y_max;                         /* outer edge of the west-most column / of the north-most row, metres: finite */
+  double pixel;                                /* side of a pixel, metres: finite, > 0 */
+  int32_t width, height;                       /* >= 0 */
+} rg_mercator_raster;
+
+typedef struct rg_warp_source {
+  double x_lo, y_lo;                           /* node (0, 0) in the grid's plane, metres: finite */
+  double step_x, step_y;                       /* node spacing, metres: finite, > 0 */
+  int32_t ny, nx;                              /* >= 2 */
+} rg_warp_source;
+
+/* out[p][r][c] for p < n_planes: plane p of src ([n_planes, ny, nx] float32) sampled at (fx, fy) of pixel (r, c); one
+ * coordinate evaluation serves all planes of a pixel.  out is [n_planes, height, width].
+ *   method 0, nearest:  ix = floor(fx + 0.5), iy = floor(fy + 0.5); outside 0 <= ix < nx, 0 <= iy < ny the pixel is `fill`,
+ *     inside it the source value is copied bit for bit (NaN and inf included).
+ *   method 1, bilinear: x0 = floor(fx), tx = fx - x0, likewise y.  The taps (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1), in
+ *     that order, carry the float64 weights (1-ty)(1-tx), (1-ty)tx, ty(1-tx), ty*tx.  A tap outside the plane, or one that
+ *     is NaN, is missing; wsum and vsum (weight * value) are summed in float64 over the taps present, in that order;
+ *     out = (float)(vsum / wsum) if wsum >= 0.5, else `fill` -- an echo's edge stays where nearest keeps it.
+ * Refused with RG_EINVAL before any launch: null pointers, n_planes < 1, a struct member that is not finite or not positive
+ * where it must be (a negative width or height included), ny or nx below 2, an unknown method, out overlapping src.
+ * width == 0 or height == 0 returns RG_OK without a launch.  Rasters of more than 2^31 pixels take several launches. */
+int rg_warp_mercator_f32(const float* src, int32_t n_planes, const rg_warp_source* source, const rg_georef* grid,
+                         const rg_mercator_raster* raster, int32_t method, float fill, float* out, rg_stream_t stream);
+/* The same map for an RGBA image: src [ny, nx, 4] uint8 -> out [height, width, 4] uint8 (both 4-byte aligned, RG_EALIGN
+ * otherwise), nearest only, one 32-bit load and store per pixel.  A sample outside the plane, or beyond the angular limit,
+ * gives 0, 0, 0, 0.  Refusals as above. */
+int rg_warp_mercator_rgba8(const uint8_t* src, const rg_warp_source* source, const rg_georef* grid,
+                           const rg_mercator_raster* raster, uint8_t* out, rg_stream_t stream);
+/* One overview level of src [n_planes, h, w] float32: out is [n_planes, ceil(h / factor), ceil(w / factor)].  Every level
+ * is computed from the base image, never from another level.
+ *   method 0, nearest: out[r][c] = src[min(r * f + f / 2, h - 1)][min(c * f + f / 2, w - 1)], bit for bit.
+ *   method 1, average: the mean of the FINITE values of the block [r * f, min((r + 1) * f, h)) x [c * f, min((c + 1) * f, w)),
+ *     accumulated in float64 in row-major order and rounded once to float32; a block with no finite value gives NaN.
+ * 2 <= factor <= 64.  Refused with RG_EINVAL: null pointers, n_planes < 1, h or w negative, a factor out of range, an unknown
+ * method, out overlapping src.  h == 0 or w == 0 returns RG_OK without a launch. */
+int rg_overview_f32(const float* src, int32_t n_planes, int32_t h, int32_t w, int32_t factor, int32_t method, float* out,
+                    rg_stream_t stream);
+/* The nearest rule of rg_overview_f32 for an RGBA image [h, w, 4] uint8 (4-byte aligned): one 32-bit load and store. */
+int rg_overview_rgba8(const uint8_t* src, int32_t h, int32_t w, int32_t factor, uint8_t* out, rg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,8 @@ from .section import (compute_section_geometry, section_fields_device, section_p
                       vertical_section)
 from .georef import (AEQD_EARTH_RADIUS, geographic_to_grid, grid_lonlat_device, grid_to_geographic, place_gates_device,
                      place_radar, place_radars, section_path_lonlat)
+from .warp import (MercatorRaster, lonlat_to_mercator, mercator_raster_for, mercator_tile, mercator_to_lonlat,
+                   overview_pyramid_device, warp_to_mercator_device, web_mercator_rgba)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -60,6 +62,8 @@ __all__ = [
     "section_path", "section_rectangle", "section_fields_device", "compute_section_geometry", "vertical_section",
     "AEQD_EARTH_RADIUS", "geographic_to_grid", "grid_to_geographic", "place_gates_device", "place_radar", "place_radars",
     "section_path_lonlat", "grid_lonlat_device",
+    "MercatorRaster", "lonlat_to_mercator", "mercator_to_lonlat", "mercator_raster_for", "mercator_tile",
+    "warp_to_mercator_device", "overview_pyramid_device", "web_mercator_rgba",
     "column_profile", "echo_top", "echo_base", "vertically_integrated_liquid",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",

@@ -81,6 +81,17 @@ class Georef(Structure):
                 ("reserved", c_int32)]
 
 
+class MercatorRaster(Structure):
+    """``rg_mercator_raster``: a north-up Web Mercator raster (``warp.MercatorRaster`` is the Python-side tuple)."""
+    _fields_ = [("x_min", c_double), ("y_max", c_double), ("pixel", c_double), ("width", c_int32), ("height", c_int32)]
+
+
+class WarpSource(Structure):
+    """``rg_warp_source``: the float64 node lattice of the plane a warp samples."""
+    _fields_ = [("x_lo", c_double), ("y_lo", c_double), ("step_x", c_double), ("step_y", c_double), ("ny", c_int32),
+                ("nx", c_int32)]
+
+
 RG_MAX_SEL_PLANES = 4       # level selections (constant-elevation PPIs) one planes-mode launch samples
 RG_PPI_SEL_NONE = -1
 
@@ -208,6 +219,12 @@ SIGNATURES = {
     "rg_gates_to_frame_f32": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(Georef), c_void_p, c_void_p, c_void_p]),
     "rg_frame_to_lonlat_f64": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, POINTER(Georef), c_void_p, c_void_p,
                                          c_void_p]),
+    "rg_warp_mercator_f32": (c_int32, [c_void_p, c_int32, POINTER(WarpSource), POINTER(Georef), POINTER(MercatorRaster),
+                                       c_int32, c_float, c_void_p, c_void_p]),
+    "rg_warp_mercator_rgba8": (c_int32, [c_void_p, POINTER(WarpSource), POINTER(Georef), POINTER(MercatorRaster), c_void_p,
+                                         c_void_p]),
+    "rg_overview_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "rg_overview_rgba8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -35,6 +35,7 @@ SOURCES = [
     ("rg_roi_section.hip", []),
     ("rg_raster.hip", []),
     ("rg_georef.hip", []),
+    ("rg_warp.hip", []),
 ]
 
 # Every translation unit is built with FP contraction OFF: the parity contract is NumPy's arithmetic, which

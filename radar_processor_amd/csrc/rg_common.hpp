@@ -25,6 +25,15 @@ inline int check_launch(const char* what) {
   return RG_OK;
 }
 
+// every double of an rg_georef is finite (the entry points that take one refuse it otherwise)
+inline bool georef_finite(const rg_georef& g) {
+  const double m[] = {g.radius, g.lon_from, g.lat_from, g.sin_lat_from, g.cos_lat_from, g.lon_to, g.lat_to,
+                      g.sin_lat_to, g.cos_lat_to, g.ox, g.oy};
+  for (double v : m)
+    if (!__builtin_isfinite(v)) return false;
+  return true;
+}
+
 constexpr int kWave = 64;        // CDNA4 wavefront
 constexpr int kBlock = 256;      // 4 waves per workgroup
 

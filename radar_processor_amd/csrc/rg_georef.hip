@@ -88,14 +88,6 @@ __global__ __launch_bounds__(rg::kBlock) void frame_to_lonlat_kernel(const float
   lat_deg[i] = lat;
 }
 
-bool members_finite(const rg_georef& g) {
-  const double m[] = {g.radius, g.lon_from, g.lat_from, g.sin_lat_from, g.cos_lat_from, g.lon_to, g.lat_to,
-                      g.sin_lat_to, g.cos_lat_to, g.ox, g.oy};
-  for (double v : m)
-    if (!isfinite(v)) return false;
-  return true;
-}
-
 // two arrays of `bytes` bytes each share a byte without being the same array
 bool overlap_apart(const void* a, const void* b, int64_t bytes) {
   const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
@@ -112,7 +104,7 @@ extern "C" int rg_gates_to_frame_f32(const float* x, const float* y, int64_t n, 
   RG_REQUIRE(n >= 0, RG_EINVAL, "rg_gates_to_frame_f32: negative size");
   const rg_georef g = *radar_to_grid;
   RG_REQUIRE(isfinite(g.radius) && g.radius > 0.0, RG_EINVAL, "rg_gates_to_frame_f32: radius must be finite and positive");
-  RG_REQUIRE(members_finite(g), RG_EINVAL, "rg_gates_to_frame_f32: a member of rg_georef is not finite");
+  RG_REQUIRE(rg::georef_finite(g), RG_EINVAL, "rg_gates_to_frame_f32: a member of rg_georef is not finite");
   RG_REQUIRE(g.same_centre == 0 || g.same_centre == 1, RG_EINVAL, "rg_gates_to_frame_f32: same_centre must be 0 or 1");
   const int64_t bytes = n * (int64_t)sizeof(float);
   RG_REQUIRE(!overlap_apart(x_out, y_out, bytes) && (x_out != y_out || n == 0), RG_EINVAL,
@@ -135,7 +127,7 @@ extern "C" int rg_frame_to_lonlat_f64(const float* xc, const float* yc, int32_t 
   RG_REQUIRE(ny >= 0 && nx >= 0, RG_EINVAL, "rg_frame_to_lonlat_f64: negative size");
   const rg_georef g = *grid;
   RG_REQUIRE(isfinite(g.radius) && g.radius > 0.0, RG_EINVAL, "rg_frame_to_lonlat_f64: radius must be finite and positive");
-  RG_REQUIRE(members_finite(g), RG_EINVAL, "rg_frame_to_lonlat_f64: a member of rg_georef is not finite");
+  RG_REQUIRE(rg::georef_finite(g), RG_EINVAL, "rg_frame_to_lonlat_f64: a member of rg_georef is not finite");
   const int64_t n = (int64_t)ny * nx;
   RG_REQUIRE(!overlap_apart(lon, lat, n * (int64_t)sizeof(double)) && (lon != lat || n == 0), RG_EINVAL,
              "rg_frame_to_lonlat_f64: lon and lat overlap");
