@@ -418,9 +418,13 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
       }
     };
     auto consume = [&](const Step& r, const rg_u32x4& q4, int k) {     // k: slot of the step's batch (compile-time)
-      // the record's pairs i = 0, 1, 2 belong to the lane's row iff lo <= i < lo + len (len = 0 for a lane without record)
-      const int lo = r.lo0 - 3 * (k << lgl);
-      const unsigned len = (kDense ? 2 * (k << lgl) + 1 < r.rem : (k << lgl) < r.rem) ? r.len : 0u;
+      // The record's pairs i = 0, 1, 2 belong to the lane's row iff lo <= i < lo + len, lo = lo0 - 3 * k * L.  Taken against
+      // wave-uniform constants: 3 * k * L + i < lo0 + len, and lo0 <= i where that can fail at all -- lo0 = (first pair mod 3)
+      // - 3 * sub <= 2 in a row's first step and lower in every later one, so only pairs 0 and 1 of slot 0 need the test.  A
+      // slot past the row's last record needs no test of its own (issue() keeps one: its loads are real bytes): its pairs'
+      // numbers in the segment are >= 3 * ceil(row end / 3) >= the row's end; a lane without a row has len = 0.
+      // (tests/test_rowwise_prologue_scenes.py holds this against the definition.)
+      const int hi = r.lo0 + (int)r.len;
       float w[3];
       int pos[3];
       // dense: bit 0 of rem is the parity of q; the record's number is q + k * L (k * L is odd only for odd k and L = 1)
@@ -433,7 +437,7 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
       }
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        const bool mine = (unsigned)(i - lo) < len;
+        const bool mine = 3 * (k << lgl) + i < hi && (k > 0 || i == 2 || r.lo0 <= i);
         // windowed: no clamp -- a position is 16 bits by construction, and an LDS read beyond the workgroup's allocation
         // returns zeros instead of faulting (a corrupt record cannot do worse than a wrong value)
         const int p = kWindowed ? pos[i] : (pos[i] < nd_last ? pos[i] : nd_last);
