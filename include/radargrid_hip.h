@@ -42,7 +42,8 @@ extern "C" {
  * changed, rg_csr_compact_pack_dense was ADDED (a library without it fails to bind by name) and rg_csr_compact_pack refuses work; the
  * mosaic combine rules -- rg_roi_grid_mosaic_combine_f32 and rg_roi_section_mosaic_combine_f32 were ADDED, no signature changed; the column profile -- rg_column_profile_f32 was ADDED;
  * georeferencing -- rg_gates_to_frame_f32 and rg_frame_to_lonlat_f64 were ADDED; the Web Mercator warp and the overview
- * pyramid -- rg_warp_mercator_f32, rg_warp_mercator_rgba8, rg_overview_f32 and rg_overview_rgba8 were ADDED. */
+ * pyramid -- rg_warp_mercator_f32, rg_warp_mercator_rgba8, rg_overview_f32 and rg_overview_rgba8 were ADDED; connected echo regions -- rg_components_workspace_bytes,
+ * rg_label_components_f32, rg_component_stats_f32 and rg_despeckle_select_f32 were ADDED. */
 #define RG_VERSION 104
 #define RG_MAX_FIELDS 8
 
@@ -896,6 +897,64 @@ int rg_overview_f32(const float* src, int32_t n_planes, int32_t h, int32_t w, in
                     rg_stream_t stream);
 /* The nearest rule of rg_overview_f32 for an RGBA image [h, w, 4] uint8 (4-byte aligned): one 32-bit load and store. */
 int rg_overview_rgba8(const uint8_t* src, int32_t h, int32_t w, int32_t factor, uint8_t* out, rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Connected echo regions: labelling, the per-cell table and despeckling.  (No reference counterpart in radar_grid; the
+ * numbering is scipy.ndimage.label's, the sweep use with wrap_rows is PyART's despeckle_field.  Neither is in the tree: the
+ * tests pin the contract against a flood fill, tests/components_oracle.py.)
+ *
+ * Input: n_planes independent float32 planes [h][w], row-major, n_planes * h * w < 2^31 (RG_EINVAL otherwise).
+ *   foreground   v >= lo && v <= hi in float32, and mask (optional uint8 of the planes' shape) zero at the pixel.  lo is
+ *                inclusive; hi may be +inf, and then +inf is foreground; NaN never is (both comparisons fail).
+ *   neighbours   connectivity 4: (y +- 1, x), (y, x +- 1); 8: the diagonals too.  wrap_rows != 0: row 0 and row h - 1 of the
+ *                SAME plane are neighbours (with 8, their diagonals included) -- the azimuth wrap of a sweep [n_rays, n_gates].
+ *                Planes never connect to each other.
+ * How it runs: one workgroup labels a tile of RG_CC_TILE_H x RG_CC_TILE_W pixels with a union-find in LDS; a second launch
+ * unites the pixel pairs across tile borders (the corner diagonals and the wrap seam included) with agent-scope atomic
+ * minima; further launches resolve every pixel to its root, rank the roots with a scan and write the ids.  The larger root is
+ * always linked under the smaller, so a cell's root is its smallest flat index = its first pixel in raster order, and ranking
+ * the roots in index order IS the raster-order numbering.  No workgroup ever waits for another.
+ * ------------------------------------------------------------------------------------------------- */
+#define RG_CC_TILE_H 32
+#define RG_CC_TILE_W 64
+
+/* bytes of `workspace` rg_label_components_f32 needs for these sizes (a multiple of 16), or RG_EINVAL (as int64) */
+int64_t rg_components_workspace_bytes(int32_t n_planes, int32_t h, int32_t w);
+/* labels: int32 [n_planes][h][w], 0 = background, the cells of plane p numbered 1 .. (cells of p) in raster order of each
+ * cell's FIRST pixel.  cell_ptr: int32 [n_planes + 1] on the device, the exclusive running count of cells: cell k of plane p
+ * is row cell_ptr[p] + k - 1 of any per-cell array, cell_ptr[n_planes] the number of cells.  mask may be NULL.  workspace:
+ * 4-byte aligned, at least rg_components_workspace_bytes (RG_EWORKSPACE otherwise), contents undefined before and after.
+ * Refused with RG_EINVAL: null pointers, n_planes < 1, h or w negative, the size limit, lo or hi NaN, connectivity not 4 or 8,
+ * labels overlapping src.  h == 0 or w == 0 zeroes cell_ptr and returns. */
+int rg_label_components_f32(const float* src, const uint8_t* mask, int32_t n_planes, int32_t h, int32_t w, float lo, float hi,
+                            int32_t connectivity, int32_t wrap_rows, int32_t* labels, int32_t* cell_ptr, void* workspace,
+                            int64_t workspace_bytes, rg_stream_t stream);
+/* The table of the cells of `labels` / `cell_ptr` (as written by rg_label_components_f32) over the values of `src`: per-cell
+ * arrays of n_cells rows (n_cells = cell_ptr[n_planes], read by the caller); any output pointer may be NULL.
+ *   area     int32      pixels of the cell
+ *   bbox     int32 [4]  y_min, y_max, x_min, x_max
+ *   sum_yx   int64 [2]  sum of y, sum of x over the cell's pixels (integers: sum / area is the exact centroid)
+ *   vmax     float32    the largest value;  argmax int32: its flat index y * w + x within the plane, the smallest index among
+ *                       ties.  Order: the IEEE total order of the non-NaN values (-0 below +0); a NaN pixel takes no part, a
+ *                       cell with no other value gets vmax = NaN, argmax = -1.  argmax needs vmax (RG_EINVAL without it): the
+ *                       maximum is formed in vmax's own words as an order-preserving 32-bit key with atomic maxima, then the
+ *                       pixels that hold it race for the smallest index with atomic minima -- two order-independent steps.
+ *   vsum     float64    sum of the cell's values (float64 atomic adds of per-run partial sums: the one output that depends
+ *                       on the order of arrival, within n * 2^-53 * sum|v|)
+ * Every other output is bit-reproducible.  Indices are RAW: under wrap_rows a cell across the seam is NOT unwrapped -- its
+ * bbox spans 0 .. h - 1 and its centroid lies between its two parts.  Equal-label runs of a wavefront's 64 consecutive pixels
+ * are combined first and issue ONE atomic per run and output, so a plane that is one cell is not one atomic per pixel.
+ * n_cells == 0 returns RG_OK without a launch; a label that points beyond n_cells is ignored. */
+int rg_component_stats_f32(const float* src, const int32_t* labels, const int32_t* cell_ptr, int32_t n_planes, int32_t h,
+                           int32_t w, int32_t n_cells, int32_t* area, int32_t* bbox, int64_t* sum_yx, float* vmax,
+                           int32_t* argmax, double* vsum, rg_stream_t stream);
+/* out[p][i] = fill where labels[p][i] > 0 and area[cell_ptr[p] + labels[p][i] - 1] < min_size, else src[p][i] bit for bit
+ * (background pixels are never touched).  out_mask (optional uint8 of the planes' shape): 1 where the pixel was removed, else
+ * 0 -- the kind of mask the gridders' `masks` arguments take.  src == out is allowed (in place); any other overlap is not
+ * checked.  min_size < 1 is RG_EINVAL. */
+int rg_despeckle_select_f32(const float* src, const int32_t* labels, const int32_t* cell_ptr, const int32_t* area,
+                            int32_t n_planes, int32_t h, int32_t w, int32_t min_size, float fill, float* out,
+                            uint8_t* out_mask, rg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,8 @@ from .georef import (AEQD_EARTH_RADIUS, geographic_to_grid, grid_lonlat_device, 
                      place_radar, place_radars, section_path_lonlat)
 from .warp import (MercatorRaster, lonlat_to_mercator, mercator_raster_for, mercator_tile, mercator_to_lonlat,
                    overview_pyramid_device, warp_to_mercator_device, web_mercator_rgba)
+from .components import (CellTable, cell_table_device, despeckle, despeckle_device, identify_cells,
+                         label_components_device)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -65,6 +67,7 @@ __all__ = [
     "MercatorRaster", "lonlat_to_mercator", "mercator_to_lonlat", "mercator_raster_for", "mercator_tile",
     "warp_to_mercator_device", "overview_pyramid_device", "web_mercator_rgba",
     "column_profile", "echo_top", "echo_base", "vertically_integrated_liquid",
+    "label_components_device", "cell_table_device", "despeckle_device", "despeckle", "identify_cells", "CellTable",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

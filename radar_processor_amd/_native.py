@@ -39,6 +39,7 @@ RG_COMPACT_ROTATION = 5       # block -> chunk column rotation per line group (h
 RG_REC_ORDER_SEGMENT, RG_REC_ORDER_DISPATCH = 0, 1
 RG_ROW_END16_MAX = 65534      # largest segment span the row-end table holds (header: RG_ROW_END16_MAX)
 RG_ROW_END16_WIDE = 0xFFFF    # table entries of a segment beyond it, which reads the row pointers (header: RG_ROW_END16_WIDE)
+RG_CC_TILE_H, RG_CC_TILE_W = 32, 64   # tile of the connected-component labelling (header: RG_CC_TILE_H / RG_CC_TILE_W)
 RG_DENSE_MAX_DICT = 2048      # chunks with at most this many dictionary entries keep 14-byte records (header: RG_DENSE_MAX_DICT)
 
 
@@ -225,6 +226,13 @@ SIGNATURES = {
                                          c_void_p]),
     "rg_overview_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "rg_overview_rgba8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "rg_components_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "rg_label_components_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_int32, c_int32,
+                                          c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rg_component_stats_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rg_despeckle_select_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
+                                          c_void_p, c_void_p, c_void_p]),
 }
 
 _lock = threading.Lock()

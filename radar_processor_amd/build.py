@@ -35,6 +35,7 @@ SOURCES = [
     ("rg_roi_section.hip", []),
     ("rg_raster.hip", []),
     ("rg_georef.hip", []),
+    ("rg_components.hip", []),
     ("rg_warp.hip", []),
 ]
 
