@@ -43,7 +43,8 @@ extern "C" {
  * mosaic combine rules -- rg_roi_grid_mosaic_combine_f32 and rg_roi_section_mosaic_combine_f32 were ADDED, no signature changed; the column profile -- rg_column_profile_f32 was ADDED;
  * georeferencing -- rg_gates_to_frame_f32 and rg_frame_to_lonlat_f64 were ADDED; the Web Mercator warp and the overview
  * pyramid -- rg_warp_mercator_f32, rg_warp_mercator_rgba8, rg_overview_f32 and rg_overview_rgba8 were ADDED; connected echo regions -- rg_components_workspace_bytes,
- * rg_label_components_f32, rg_component_stats_f32 and rg_despeckle_select_f32 were ADDED. */
+ * rg_label_components_f32, rg_component_stats_f32 and rg_despeckle_select_f32 were ADDED; echo motion and nowcasts --
+ * rg_motion_quantize_f32, rg_block_match_u8 and rg_advect_f32 were ADDED. */
 #define RG_VERSION 104
 #define RG_MAX_FIELDS 8
 
@@ -955,6 +956,91 @@ int rg_component_stats_f32(const float* src, const int32_t* labels, const int32_
 int rg_despeckle_select_f32(const float* src, const int32_t* labels, const int32_t* cell_ptr, const int32_t* area,
                             int32_t n_planes, int32_t h, int32_t w, int32_t min_size, float fill, float* out,
                             uint8_t* out_mask, rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Echo motion and nowcasts: the motion field between two successive product planes by block matching, and the plane
+ * extrapolated along it (semi-Lagrangian advection).  (No reference counterpart in radar_grid; the tests pin the three
+ * kernels to the NumPy restatement of exactly these formulas, tests/motion_oracle.py.)  rg_motion_quantize_f32,
+ * rg_block_match_u8 and rg_advect_f32 were ADDED; no signature changed, RG_VERSION stays 104.
+ *
+ * SIGN AND UNITS: echo at pixel p of `prev` is found at p + motion in `next`; motion is (dy, dx) in pixels per interval
+ * between the two planes.  Row index grows NORTHWARDS, as in every grid here, so dy > 0 is northward and dx > 0 eastward.
+ * Planes are [n][h][w], row-major, pitch w, no padding, n * h * w < 2^31 (RG_EINVAL otherwise).
+ * ------------------------------------------------------------------------------------------------- */
+#define RG_MOTION_MAX_BLOCK 64
+#define RG_MOTION_MAX_SEARCH 32
+#define RG_MAX_LEADS 16
+
+/* Planes to 8-bit levels: src float32 [n][h][w], mask (optional, may be NULL) uint8 of the same shape, out uint8 of the
+ * same shape.  inv_step is float32(254 / (hi - lo)), formed by the host from doubles.  Per pixel, in float32:
+ *     q = 0                                      where mask != 0 or `v >= lo` is false (NaN and -inf included)
+ *     t = (v - lo) * inv_step                    two float32 operations, unfused
+ *     q = 1 + (t >= 254 ? 254 : (int)t)          otherwise
+ * Level 0 is "no echo", 1 .. 255 are echo; +inf and everything above hi give 255.
+ * RG_EINVAL: a null src or out, n < 1, h or w negative, the size limit, lo or inv_step not finite, inv_step <= 0.
+ * h == 0 or w == 0 returns RG_OK without a launch. */
+int rg_motion_quantize_f32(const float* src, const uint8_t* mask, int32_t n, int32_t h, int32_t w, float lo, float inv_step,
+                           uint8_t* out, rg_stream_t stream);
+
+/* One motion vector per block of `prev`, searched in `next` (both uint8 [n][h][w] as written by rg_motion_quantize_f32; they
+ * may be the views q[:-1] and q[1:] of one stack of n + 1 planes).
+ *   block B      4 <= B <= RG_MOTION_MAX_BLOCK, B % 4 == 0;  N = B * B
+ *   stride S     >= 1;  nby = (h - B) / S + 1, nbx = (w - B) / S + 1;  h < B or w < B is RG_EINVAL
+ *   search R     0 <= R <= RG_MOTION_MAX_SEARCH
+ *   min_echo     1 <= min_echo <= N
+ * Block (by, bx) is prev[by*S : by*S + B, bx*S : bx*S + B].  With a the block's levels and b those of a shifted window of
+ * `next`, all sums exact integers (Sa = sum a, Saa = sum a*a, Sb, Sbb, Sab likewise; Sab <= 4096 * 255^2 < 2^31):
+ *   valid block    at least min_echo non-zero levels, and va = N*Saa - Sa*Sa > 0
+ *   candidates     (dy, dx) in [-R, R]^2 whose window next[by*S + dy : .. + B, bx*S + dx : .. + B] lies wholly inside the
+ *                  plane and has vb = N*Sbb - Sb*Sb > 0 ("qualified")
+ *   score          s = (double)(N*Sab - Sa*Sb) / sqrt((double)va * (double)vb)     the numerator an int64; the float64
+ *                  product, square root and quotient are each rounded once, so s has the bits NumPy computes
+ *   winner         the largest s; ties go to the smallest dy*dy + dx*dx, then the smallest dy, then the smallest dx
+ *   sub-pixel      per axis, float64: m and p the scores of the winner's two neighbours on that axis; if both are qualified
+ *                  candidates inside [-R, R] and den = m - 2*s0 + p < 0 then off = clamp(0.5 * (m - p) / den, -0.5, 0.5),
+ *                  else off = 0
+ * Outputs per block:  disp int16 [n][nby][nbx][2] = (dy, dx);  motion float32 [n][nby][nbx][2] = ((float)(dy + off_y),
+ * (float)(dx + off_x));  score float32 [n][nby][nbx] = (float)s0.  An invalid block, or one with no qualified candidate,
+ * gives disp = (0, 0) and NaN in motion and score.
+ * How it runs: one workgroup per block; the block and its (B + 2R)^2 window are staged in LDS (window bytes outside the
+ * plane as 0: no qualified candidate reads them); Sab, Sb and Sbb come from the packed 8-bit dot product, a dx that is no
+ * multiple of 4 by byte-aligning two LDS dwords; the scores of all (2R + 1)^2 candidates stay in LDS for the arg-max over the
+ * full tie key and for the parabola.  No byte outside [0, n*h*w) of either input is read (rows are not 4-byte aligned when
+ * w % 4 != 0: staging loads bytes).  No atomics, no workgroup waits for another, every output is bit-reproducible.
+ * RG_EINVAL before any launch: null pointers, n < 1, h or w negative, the size limit, a parameter outside its range. */
+int rg_block_match_u8(const uint8_t* prev, const uint8_t* next, int32_t n, int32_t h, int32_t w, int32_t block, int32_t stride,
+                      int32_t search, int32_t min_echo, int16_t* disp, float* motion, float* score, rg_stream_t stream);
+
+/* The node lattice of a motion field [ny][nx][2], components (v, u) = (dy, dx): node (j, i) lies at pixel
+ * (origin_y + j * step_y, origin_x + i * step_x).  For a block-match lattice origin = (B - 1) / 2.0 and step = S; a dense
+ * per-pixel field is 0, 0, 1, 1.  A HOST struct, passed by value. */
+typedef struct rg_motion_lattice {
+  double origin_y, origin_x;                   /* pixel coordinates of node (0, 0): finite */
+  double step_y, step_x;                       /* node spacing in pixels: finite, > 0 */
+  int32_t ny, nx;                              /* >= 1 */
+} rg_motion_lattice;
+
+/* Semi-Lagrangian extrapolation: out[l][p][y][x] = plane p of src ([n_planes][h][w] float32) sampled where the echo that
+ * reaches pixel (y, x) after leads_host[l] intervals sits now.  One displacement per pixel and lead serves all planes.
+ * `motion` float32 [ny][nx][2] on the device, ALL FINITE (the caller's duty; a NaN vector makes the pixels it reaches
+ * `fill`, never a fault).  Everything up to the sample is float64, unfused, in this order.
+ *   motion at a point (py, px):   ly = clamp((py - origin_y) / step_y, 0, ny - 1);  j0 = min(floor(ly), max(ny - 2, 0));
+ *       j1 = min(j0 + 1, ny - 1);  ty = ly - j0;  likewise lx, i0, i1, tx;  per component
+ *       V = (V[j0,i0]*(1-tx) + V[j0,i1]*tx)*(1-ty) + (V[j1,i0]*(1-tx) + V[j1,i1]*tx)*ty
+ *       -- constant extrapolation beyond the outermost nodes
+ *   displacement:   d = (0, 0);  `substeps` times:  d = d + (lead / substeps) * V(p - d);  the source position is p - d
+ *   sampling (fy, fx) = p - d:   exactly the two rules of rg_warp_mercator_f32 (the kernels share csrc/rg_sample.hpp):
+ *       method 0, nearest: iy = floor(fy + 0.5), ix = floor(fx + 0.5), the value copied bit for bit, `fill` outside the plane;
+ *       method 1, bilinear: the four taps in that order, NaN and outside taps missing, wsum and vsum in float64,
+ *       out = (float)(vsum / wsum) if wsum >= 0.5, else `fill`.
+ * leads_host: n_leads <= RG_MAX_LEADS finite doubles in units of the interval, read on the host and passed by value.
+ * 1 <= substeps <= 16.  Lead 0 returns src bit for bit under nearest.
+ * RG_EINVAL before any launch: null pointers, n_planes < 1, h or w negative, the size limit, n_leads outside
+ * 0 .. RG_MAX_LEADS, a lead or a lattice member that is not finite, a step <= 0, ny or nx < 1, substeps out of range, an
+ * unknown method, out overlapping src.  h == 0, w == 0 or n_leads == 0 returns RG_OK without a launch. */
+int rg_advect_f32(const float* src, int32_t n_planes, int32_t h, int32_t w, const float* motion, rg_motion_lattice lattice,
+                  const double* leads_host, int32_t n_leads, int32_t substeps, int32_t method, float fill, float* out,
+                  rg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,8 @@ from .warp import (MercatorRaster, lonlat_to_mercator, mercator_raster_for, merc
                    overview_pyramid_device, warp_to_mercator_device, web_mercator_rgba)
 from .components import (CellTable, cell_table_device, despeckle, despeckle_device, identify_cells,
                          label_components_device)
+from .motion import (MotionGrid, advect_device, estimate_motion_device, fill_motion_device, motion_to_velocity, nowcast,
+                     nowcast_device, quantize_planes_device)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -68,6 +70,8 @@ __all__ = [
     "warp_to_mercator_device", "overview_pyramid_device", "web_mercator_rgba",
     "column_profile", "echo_top", "echo_base", "vertically_integrated_liquid",
     "label_components_device", "cell_table_device", "despeckle_device", "despeckle", "identify_cells", "CellTable",
+    "quantize_planes_device", "estimate_motion_device", "fill_motion_device", "advect_device", "nowcast_device", "nowcast",
+    "motion_to_velocity", "MotionGrid",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

@@ -93,6 +93,15 @@ class WarpSource(Structure):
                 ("nx", c_int32)]
 
 
+class MotionLattice(Structure):
+    """``rg_motion_lattice``: the node lattice of a motion field, in pixels; passed to ``rg_advect_f32`` BY VALUE."""
+    _fields_ = [("origin_y", c_double), ("origin_x", c_double), ("step_y", c_double), ("step_x", c_double), ("ny", c_int32),
+                ("nx", c_int32)]
+
+
+RG_MOTION_MAX_BLOCK = 64    # largest block side of rg_block_match_u8 (header: RG_MOTION_MAX_BLOCK)
+RG_MOTION_MAX_SEARCH = 32   # largest search radius (header: RG_MOTION_MAX_SEARCH)
+RG_MAX_LEADS = 16           # lead times one rg_advect_f32 launch takes (header: RG_MAX_LEADS)
 RG_MAX_SEL_PLANES = 4       # level selections (constant-elevation PPIs) one planes-mode launch samples
 RG_PPI_SEL_NONE = -1
 
@@ -233,6 +242,11 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rg_despeckle_select_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
                                           c_void_p, c_void_p, c_void_p]),
+    "rg_motion_quantize_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p]),
+    "rg_block_match_u8": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rg_advect_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, MotionLattice, POINTER(c_double), c_int32,
+                                c_int32, c_int32, c_float, c_void_p, c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -36,6 +36,7 @@ SOURCES = [
     ("rg_raster.hip", []),
     ("rg_georef.hip", []),
     ("rg_components.hip", []),
+    ("rg_motion.hip", []),
     ("rg_warp.hip", []),
 ]
 

@@ -15,6 +15,12 @@ void set_error(const char* fmt, ...);
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// [a, a + a_bytes) and [b, b + b_bytes) share a byte
+inline bool overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + (uintptr_t)b_bytes && pb < pa + (uintptr_t)a_bytes;
+}
+
 // checks the launch that was just enqueued; does not synchronise
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();

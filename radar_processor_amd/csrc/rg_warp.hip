@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "rg_common.hpp"
+#include "rg_sample.hpp"
 
 namespace {
 
@@ -75,30 +76,11 @@ __global__ __launch_bounds__(rg::kBlock) void warp_kernel(const uint32_t* __rest
     const bool visible = plane_coords(g, s, sp, cp, sd, cd, &fx, &fy);
     uint32_t* o = out + (size_t)r * m.width + c;
     if constexpr (MODE == kBilinear) {
-      const bool near = visible && fx > -1.0 && fx < (double)s.nx && fy > -1.0 && fy < (double)s.ny;   // else no tap is inside
-      const double x0f = floor(fx), y0f = floor(fy);
-      const double tx = fx - x0f, ty = fy - y0f;
-      const int x0 = near ? (int)x0f : 0, y0 = near ? (int)y0f : 0;
-      const double w[4] = {(1.0 - ty) * (1.0 - tx), (1.0 - ty) * tx, ty * (1.0 - tx), ty * tx};
-      const bool in_x[2] = {x0 >= 0, x0 + 1 < s.nx}, in_y[2] = {y0 >= 0, y0 + 1 < s.ny};
-      for (int p = 0; p < n_planes; ++p) {
-        double wsum = 0.0, vsum = 0.0;
-        if (near) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            if (!(in_y[t >> 1] && in_x[t & 1])) continue;
-            const float v = rg::bits_f32(src[p * plane_in + (size_t)(y0 + (t >> 1)) * s.nx + (x0 + (t & 1))]);
-            if (isnan(v)) continue;
-            wsum += w[t];
-            vsum += w[t] * (double)v;
-          }
-        }
-        o[p * plane_out] = wsum >= 0.5 ? rg::f32_bits((float)(vsum / wsum)) : fill;
-      }
+      const rg::BilinearTaps taps = rg::bilinear_taps(fx, fy, s.nx, s.ny, visible);
+      for (int p = 0; p < n_planes; ++p) o[p * plane_out] = rg::bilinear_sample(src + p * plane_in, s.nx, taps, fill);
     } else {
-      const double gx = floor(fx + 0.5), gy = floor(fy + 0.5);
-      const bool inside = visible && gx >= 0.0 && gx < (double)s.nx && gy >= 0.0 && gy < (double)s.ny;
-      const size_t at = inside ? (size_t)gy * s.nx + (size_t)gx : 0;
+      size_t at;
+      const bool inside = rg::nearest_node(fx, fy, s.nx, s.ny, visible, &at);
       for (int p = 0; p < n_planes; ++p) o[p * plane_out] = inside ? src[p * plane_in + at] : fill;
     }
   }
@@ -134,12 +116,6 @@ __global__ __launch_bounds__(rg::kBlock) void overview_kernel(const uint32_t* __
   }
 }
 
-// [a, a + a_bytes) and [b, b + b_bytes) share a byte
-bool overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + (uintptr_t)b_bytes && pb < pa + (uintptr_t)a_bytes;
-}
-
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // every refusal the two warp entry points share (a plane element is 4 bytes: a float, or an RGBA pixel)
@@ -159,7 +135,7 @@ int check_warp(const char* who, const void* src, int n_planes, const rg_warp_sou
              "%s: a member of rg_mercator_raster is not finite", who);
   RG_REQUIRE(m.pixel > 0.0, RG_EINVAL, "%s: pixel must be positive", who);
   RG_REQUIRE(m.width >= 0 && m.height >= 0, RG_EINVAL, "%s: negative width or height", who);
-  RG_REQUIRE(!overlap(src, (int64_t)n_planes * s.ny * s.nx * 4, out, (int64_t)n_planes * m.height * m.width * 4), RG_EINVAL,
+  RG_REQUIRE(!rg::overlap(src, (int64_t)n_planes * s.ny * s.nx * 4, out, (int64_t)n_planes * m.height * m.width * 4), RG_EINVAL,
              "%s: out overlaps src", who);
   return RG_OK;
 }
@@ -184,7 +160,7 @@ int launch_overview(const char* who, const void* src, int32_t n_planes, int32_t 
   RG_REQUIRE(h >= 0 && w >= 0, RG_EINVAL, "%s: negative size", who);
   RG_REQUIRE(factor >= 2 && factor <= 64, RG_EINVAL, "%s: factor must lie in 2 .. 64", who);
   const int oh = (int)(((long)h + factor - 1) / factor), ow = (int)(((long)w + factor - 1) / factor);
-  RG_REQUIRE(!overlap(src, (int64_t)n_planes * h * w * 4, out, (int64_t)n_planes * oh * ow * 4), RG_EINVAL,
+  RG_REQUIRE(!rg::overlap(src, (int64_t)n_planes * h * w * 4, out, (int64_t)n_planes * oh * ow * 4), RG_EINVAL,
              "%s: out overlaps src", who);
   const long n = (long)n_planes * oh * ow;
   for (long first = 0; first < n; first += kPerLaunch) {
