@@ -38,7 +38,14 @@ namespace {
 constexpr int kRowwiseChunksPerBlock = 1;   // consecutive chunks one workgroup takes (see the kernel: 1 measured best)
 
 // Workgroups per CU the compiler must leave room for (= wavefronts per SIMD: a workgroup is one wavefront per SIMD); 1 = no
-// constraint, which is what the row-wise kernel itself measured best with.  COLS == 2 (planes mode): the wider epilogue is
+// constraint, which is what the row-wise kernel itself measured best with.  How many the hardware then ADMITS is decided by
+// two register files, not by VGPRs alone (EXPERIMENTS R5.3): 512 / (VGPR allocation rounded up to 8) wavefronts per SIMD, and
+// min(8, 800 / (ceil(.sgpr_count / 16) * 16 + 16)) 256-thread workgroups per CU -- .sgpr_count <= 80 admits eight, <= 96
+// seven, anything above six, whatever the compiler's Occupancy remark says.  COLS == 0, one field (what bench.py times): 64
+// VGPRs and 94 SGPRs since the grid mode has no chunk loop, so SEVEN workgroups per CU are resident (measured: 6.55 wavefronts
+// per SIMD of a busy CU against 5.65 before).  A bound of 7 to hold it there, and a bound of 8 with amdgpu_num_sgpr(80) (62
+// VGPRs, 78 SGPRs, 7.47 resident), measured no faster than no bound at all, so it has none.
+// COLS == 2 (planes mode): the wider epilogue is
 // held to the column mode's wavefronts per SIMD for two to four fields (5, 4, 4) and to at least 5 for one field.  Measured
 // (-Rpass-analysis=kernel-resource-usage, no scratch): 80 / 90 / 112 / 120 VGPRs for 1-4 fields, i.e. 6 / 5 / 4 / 4
 // wavefronts per SIMD -- the column mode's 77 / 83 / 101 / 107 keep the same counts.
@@ -143,7 +150,10 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   }
   long col_xy = 0;                                    // COLS: (y, x) of lane == row, the same on every level
   int col_nrows = 0;
-  for (int cb = 0; cb < chunks_per_block; ++cb) {
+  // Grid mode: the launcher's chunks per workgroup is the compile-time kRowwiseChunksPerBlock, so that with 1 the loop, its
+  // counter and the block arithmetic fold away (scalars that would otherwise live across the streaming loops).
+  const int n_cb = COLS ? chunks_per_block : kRowwiseChunksPerBlock;
+  for (int cb = 0; cb < n_cb; ++cb) {
   unsigned bid, chunk;
   if constexpr (COLS) {
     const unsigned grp = (unsigned)(col_z0 + cb) * cg.nyg + col_yg;
@@ -151,7 +161,7 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
     const unsigned shift = ((grp + cg.grp0) * cg.rot_step) % cg.nsx;      // the block whose rotated column is col_sx
     bid = grp * cg.nsx + (col_sx >= shift ? col_sx - shift : col_sx + cg.nsx - shift);
   } else {
-    bid = blockIdx.x * (unsigned)chunks_per_block + (unsigned)cb;
+    bid = blockIdx.x * (unsigned)kRowwiseChunksPerBlock + (unsigned)cb;
     if (bid >= n_chunks) break;                       // workgroup-uniform
     chunk = block_chunk(cg, bid);
   }
@@ -180,11 +190,8 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   const int nd_all = (int)(dict_ptr[chunk + 1] - d0);
   const bool split = nd_all > 65536;
   const bool windowed = nd_all <= window_cap;        // the window holds window_cap + 1 entries: the sentinel
-  const int w_lo = split ? dict[d0 + wv] : 0;
-  const int w_hi = split ? (wv + 1 < kH ? dict[d0 + wv + 1] : nd_all) : nd_all;
-  const int nd = w_hi - w_lo;
-  const int nd_last = nd > 0 ? nd - 1 : 0;
-  const int32_t* __restrict__ cdict = dict + d0 + w_lo;
+  // (a split chunk's per-wavefront dictionary window -- w_lo, w_hi -- is read where the per-pair path needs it: run(); the
+  // window fill never sees a split chunk, whose dictionary is wider than any window)
 
   const Segment sg = chunk_segment(cg, chunk, wv);
   const int nrows = sg.nrows;
@@ -254,7 +261,7 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   if (windowed) {
     constexpr int kFillBatch = 4;                // 1 / 2 / 8 measured: +2 % / +0.3 % / +0.5 % on config 2 (A/B builds)
     const int last_entry = nd_all > 0 ? nd_all - 1 : 0;
-    const int32_t* __restrict__ cd = nd_all > 0 ? cdict : (const int32_t*)dict_ptr;   // never dereference an empty dictionary
+    const int32_t* __restrict__ cd = nd_all > 0 ? dict + d0 : (const int32_t*)dict_ptr;   // never dereference an empty dictionary
     for (int i0 = threadIdx.x; i0 <= nd_all; i0 += 64 * kH * kFillBatch) {
       unsigned gate[kFillBatch];
 #pragma unroll
@@ -366,6 +373,12 @@ __global__ RG_ROWWISE_BOUNDS void csr_compact_rowwise_kernel(
   auto run = [&](auto wtag, auto dtag) {
     constexpr bool kWindowed = decltype(wtag)::value;
     constexpr bool kDense = decltype(dtag)::value;
+    // per-pair path: the wavefront's part of the chunk's dictionary (a split chunk -- more than 65536 entries -- gives every
+    // wavefront a window of its own, whose bounds are the dictionary's first kH entries)
+    const int w_lo = !kWindowed && split ? dict[d0 + wv] : 0;
+    const int w_hi = !kWindowed && split && wv + 1 < kH ? dict[d0 + wv + 1] : nd_all;
+    const int nd_last = w_hi - w_lo > 0 ? w_hi - w_lo - 1 : 0;
+    const int32_t* __restrict__ cdict = dict + d0 + w_lo;
     // The running sums of the lane's row, across the round's steps: TWO chains -- batch slot k of every step adds into
     // chain k mod 2's (sum w*v, sum w) --, added up when the round ends.  Two independent chains half as long as round 2's
     // single one: worst relative error against the reference's ZDR fixtures 8.7e-6 -> 6.5e-6 at no cost (bench grid
