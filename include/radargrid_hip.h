@@ -1042,6 +1042,54 @@ int rg_advect_f32(const float* src, int32_t n_planes, int32_t h, int32_t w, cons
                   const double* leads_host, int32_t n_leads, int32_t substeps, int32_t method, float fill, float* out,
                   rg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Cell overlap and tracking: which cell of one labelling is which cell of another -- the contingency table of two label
+ * planes -- and the map from a label plane to any per-cell integer (a track id).  (No reference counterpart in radar_grid;
+ * every output is an integer and the tests pin them to np.unique, tests/tracking_oracle.py.)  rg_cell_overlap_workspace_bytes,
+ * rg_cell_overlap_i32 and rg_relabel_cells_i32 were ADDED; no signature changed, RG_VERSION stays 104.
+ *
+ * labels_* int32 [n_planes][h][w] and cell_ptr_* int32 [n_planes + 1] are what rg_label_components_f32 writes;
+ * n_planes * h * w < 2^31 (RG_EINVAL otherwise).  Plane p of `prev` is paired with plane p of `next`; the two may be the views
+ * L[:-1] and L[1:] of one stack, each with its own cell_ptr.
+ *   pairs      a pixel with labels a > 0 and b > 0 belongs to the pair (row_prev, row_next) = (cell_ptr_prev[p] + a - 1,
+ *              cell_ptr_next[p] + b - 1): the rows of the two cell tables.  A pixel with a <= 0 or b <= 0 takes no part, nor
+ *              does a label above its plane's cell count cell_ptr[p + 1] - cell_ptr[p].
+ *   table      open addressing in `workspace`, capacity C = the smallest power of two >= max(2 * max_pairs, 64): 64-bit keys
+ *              (uint64)row_prev << 32 | row_next, all ones = empty (unreachable: rows stay below 2^31), and 32-bit counts.
+ * How it runs: the entry point clears the table and totals on `stream` (hipMemsetAsync).  One thread per pixel, a wavefront
+ * covering 64 consecutive flat indices; runs of lanes with an equal pair are found with one ballot (csrc/rg_lane_runs.hpp, shared
+ * with the cell table) and only a run's last lane inserts, with the run's length.  It claims a slot with an agent-scope relaxed
+ * 64-bit compare-and-swap and adds the length with a relaxed 32-bit atomic add; probing is linear, visits at most C slots, then
+ * bumps totals[1] and gives up.  A compare-and-swap finds the slot empty and claims it, finds the key equal, or moves on: no
+ * thread waits for another, no loop is unbounded.  A second launch compacts the occupied slots into the outputs behind an atomic
+ * cursor (totals[0], one atomic per wavefront).  The hash (splitmix64's finaliser) shows in nothing but the order of the entries.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* bytes of `workspace` rg_cell_overlap_i32 needs for max_pairs (12 * C, a multiple of 16), or RG_EINVAL (as int64) for
+ * max_pairs < 1 or max_pairs >= 2^30 */
+int64_t rg_cell_overlap_workspace_bytes(int64_t max_pairs);
+/* pair_rows int32 [max_pairs][2] = (row_prev, row_next) and pair_count int32 [max_pairs] = the pixels the two cells share: one
+ * entry per distinct pair, in unspecified order; only min(totals[0], max_pairs) entries are written.  totals int32 [2]:
+ *   totals[0]   the number of distinct pairs held in the table; it may exceed max_pairs (up to C)
+ *   totals[1]   the number of insertions that found the table full and were dropped
+ * The result is COMPLETE iff totals[0] <= max_pairs && totals[1] == 0; then the SET of (row_prev, row_next, count) triples is
+ * bit-reproducible.  An incomplete result is still RG_OK, and every entry written is a true pair whose count holds the
+ * insertions that reached the table (the full count while totals[1] == 0).  workspace: 8-byte aligned, at least
+ * rg_cell_overlap_workspace_bytes(max_pairs) (RG_EWORKSPACE otherwise), contents undefined before and after.
+ * RG_EINVAL before any launch: null pointers, n_planes < 1, h or w negative, the size limit, max_pairs < 1 or >= 2^30, an output
+ * or the workspace overlapping an input.  h == 0 or w == 0 zeroes totals and returns. */
+int rg_cell_overlap_i32(const int32_t* labels_prev, const int32_t* cell_ptr_prev, const int32_t* labels_next,
+                        const int32_t* cell_ptr_next, int32_t n_planes, int32_t h, int32_t w, int64_t max_pairs,
+                        int32_t* pair_rows, int32_t* pair_count, int32_t* totals, void* workspace, int64_t workspace_bytes,
+                        rg_stream_t stream);
+/* out[p][i] = lut[cell_ptr[p] + labels[p][i] - 1] where 0 < labels[p][i] <= cell_ptr[p + 1] - cell_ptr[p] and that row lies
+ * below n_cells, else 0.  lut: int32 [n_cells], any per-cell integer -- track ids give the track plane for display.
+ * out == labels is allowed (in place); any other overlap of out with an input is RG_EINVAL.  n_cells == 0 writes zeros (lut may
+ * then be NULL).  RG_EINVAL: null pointers, n_planes < 1, h or w negative, the size limit, n_cells < 0.  h == 0 or w == 0
+ * returns RG_OK without a launch. */
+int rg_relabel_cells_i32(const int32_t* labels, const int32_t* cell_ptr, int32_t n_planes, int32_t h, int32_t w,
+                         const int32_t* lut, int32_t n_cells, int32_t* out, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

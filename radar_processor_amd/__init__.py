@@ -36,6 +36,8 @@ from .components import (CellTable, cell_table_device, despeckle, despeckle_devi
                          label_components_device)
 from .motion import (MotionGrid, advect_device, estimate_motion_device, fill_motion_device, motion_to_velocity, nowcast,
                      nowcast_device, quantize_planes_device)
+from .tracking import (CellMatch, CellOverlap, CellTracker, TrackFrame, advect_labels_device, cell_overlap_device, match_cells,
+                       relabel_cells_device)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -72,6 +74,8 @@ __all__ = [
     "label_components_device", "cell_table_device", "despeckle_device", "despeckle", "identify_cells", "CellTable",
     "quantize_planes_device", "estimate_motion_device", "fill_motion_device", "advect_device", "nowcast_device", "nowcast",
     "motion_to_velocity", "MotionGrid",
+    "advect_labels_device", "cell_overlap_device", "match_cells", "relabel_cells_device", "CellTracker", "CellOverlap", "CellMatch",
+    "TrackFrame",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

@@ -247,6 +247,10 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "rg_advect_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, MotionLattice, POINTER(c_double), c_int32,
                                 c_int32, c_int32, c_float, c_void_p, c_void_p]),
+    "rg_cell_overlap_workspace_bytes": (c_int64, [c_int64]),
+    "rg_cell_overlap_i32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rg_relabel_cells_i32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "rg_common.hpp"
+#include "rg_lane_runs.hpp"
 
 namespace {
 
@@ -278,12 +279,7 @@ constexpr uint32_t kNoKey = 0u;
 constexpr uint32_t kNanBits = 0x7FC00000u;
 
 // runs of equal `cell` among the wavefront's lanes: start = first lane of my run, tail = I am its last lane
-__device__ __forceinline__ void run_of(int cell, int lane, int* start, bool* tail) {
-  const int prev = __shfl_up(cell, 1);
-  const unsigned long long heads = __ballot(lane == 0 || prev != cell);
-  *start = 63 - __builtin_clzll(heads & ((2ull << lane) - 1ull));
-  *tail = lane == rg::kWave - 1 || ((heads >> (lane + 1)) & 1ull);
-}
+using rg::run_of;
 
 __device__ __forceinline__ long shfl_up_i64(long v, int d) {
   const int lo = __shfl_up((int)(v & 0xFFFFFFFFl), d), hi = __shfl_up((int)(v >> 32), d);
