@@ -44,7 +44,8 @@ extern "C" {
  * georeferencing -- rg_gates_to_frame_f32 and rg_frame_to_lonlat_f64 were ADDED; the Web Mercator warp and the overview
  * pyramid -- rg_warp_mercator_f32, rg_warp_mercator_rgba8, rg_overview_f32 and rg_overview_rgba8 were ADDED; connected echo regions -- rg_components_workspace_bytes,
  * rg_label_components_f32, rg_component_stats_f32 and rg_despeckle_select_f32 were ADDED; echo motion and nowcasts --
- * rg_motion_quantize_f32, rg_block_match_u8 and rg_advect_f32 were ADDED. */
+ * rg_motion_quantize_f32, rg_block_match_u8 and rg_advect_f32 were ADDED; rain rate and accumulation -- rg_rain_rate_f32 and
+ * rg_accumulate_advected_f32 were ADDED. */
 #define RG_VERSION 104
 #define RG_MAX_FIELDS 8
 
@@ -1089,6 +1090,70 @@ int rg_cell_overlap_i32(const int32_t* labels_prev, const int32_t* cell_ptr_prev
  * returns RG_OK without a launch. */
 int rg_relabel_cells_i32(const int32_t* labels, const int32_t* cell_ptr, int32_t n_planes, int32_t h, int32_t w,
                          const int32_t* lut, int32_t n_cells, int32_t* out, rg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Rain rate and accumulation: reflectivity planes as rain rates (Z = a R^b), and the rainfall depth of the interval between
+ * two rate planes summed ALONG the echo's motion, so that a cell moving several pixels per scan leaves a swath and not a row
+ * of separate blobs.  (No reference counterpart in radar_grid; the tests pin both kernels to the NumPy restatement of exactly
+ * these formulas, tests/accumulation_oracle.py.)  rg_rain_rate_f32 and rg_accumulate_advected_f32 were ADDED; no signature
+ * changed, RG_VERSION stays 104.
+ *
+ * Planes are [n][h][w], row-major, pitch w, no padding, n * h * w < 2^31 (RG_EINVAL otherwise).  Motion, its sign, its units
+ * and rg_motion_lattice are those of "Echo motion and nowcasts".  A rate plane has three kinds of pixel: NaN = no coverage
+ * (never measured), 0 = covered and dry, > 0 = rain in mm/h.
+ * ------------------------------------------------------------------------------------------------- */
+#define RG_MAX_ACC_STEPS 64
+
+/* dBZ to mm/h under Z = a R^b: src float32 [n][h][w] in dBZ, mask (optional, may be NULL) uint8 of the same shape, out float32
+ * of the same shape.  The host passes the doubles p = ln(10) / (10 b) and q = ln(a) / b, so that R = exp(dBZ * p - q).
+ * Per pixel, v = src:
+ *     out = quiet NaN 0x7FC00000                 where mask != 0 or v is NaN                      "no coverage"
+ *     out = 0.0f                                 where `v >= min_dbz` is false (-inf included)    "covered, dry"
+ *     c = min((double)v, max_dbz);  out = (float)exp(c * p - q)       otherwise: one float64 multiply, one subtract and one
+ *                                                exp, unfused; +inf and everything above max_dbz give the rate at max_dbz
+ * The multiply and the subtract are rounded once each, so the argument of exp has NumPy's bits; the device's exp and the
+ * host's each lie within 1 ulp(float64) of the true value, so the float32 result is the host's or its float32 neighbour.
+ * RG_EINVAL: a null src or out, n < 1, h or w negative, the size limit, p not finite or not positive, q, min_dbz or max_dbz not
+ * finite, max_dbz < min_dbz.  h == 0 or w == 0 returns RG_OK without a launch. */
+int rg_rain_rate_f32(const float* src, const uint8_t* mask, int32_t n, int32_t h, int32_t w, double p, double q, double min_dbz,
+                     double max_dbz, float* out, rg_stream_t stream);
+
+/* Advection-corrected accumulation over one interval: rate_prev and rate_next float32 [n_planes][h][w] are the rates at the two
+ * ends of an interval of `hours` (finite, > 0); out float32 [n_planes][h][w] is the depth (rate unit * hours: mm for mm/h);
+ * out_steps (optional, may be NULL) uint8 [n_planes][h][w] is the number of sub-instants that contributed.  rate_prev and
+ * rate_next may be the same plane.  `motion` float32 [ny][nx][2] on the device and `lattice` are exactly those of rg_advect_f32:
+ * the motion from prev to next, ALL FINITE (the caller's duty; a NaN vector makes the samples it reaches missing, never a fault
+ * -- the same clamp before any index).
+ *   pos(p, lead)   the source position of rg_advect_f32 for pixel p: d = (0, 0);  `substeps` times
+ *                  d = d + (lead / substeps) * V(p - d);  pos = p - d, with the same lattice interpolant V, all float64, in that
+ *                  order.  A negative lead moves the sample FORWARD along the motion.
+ *   for k = 0 .. n_steps - 1, in this order:
+ *       s = ((double)k + 0.5) / (double)n_steps
+ *       a = the sample of rate_prev at pos(p, s);   b = the sample of rate_next at pos(p, s - 1.0)
+ *           -- by `method` (0 nearest, 1 bilinear), the two rules of rg_advect_f32 with NaN as the fill: each sample is bit for
+ *           bit the float32 rg_advect_f32 writes for that lead.  A sample is MISSING when it is NaN: a position outside the
+ *           plane, a NaN source pixel, bilinear wsum < 0.5
+ *       both present:   r = (1.0 - s) * (double)a + s * (double)b
+ *       one present:    r = (double) that sample
+ *       none present:   the step is missing
+ *       a present step: total = total + r;  n = n + 1
+ *   out = n >= min_steps ? (float)(hours * (total / (double)n)) : fill;      out_steps = n
+ * All float64, unfused, each operation rounded once.  One set of positions serves all planes.  With zero motion this is the
+ * midpoint rule of the linear blend in time -- the trapezoid rule's value; with n_steps = 1 and prev == next it is hours * rate.
+ *   1 <= n_steps <= RG_MAX_ACC_STEPS;  1 <= substeps <= 16;  1 <= min_steps <= n_steps
+ * How it runs: one thread per pixel, a workgroup per tile of 8 x 32 pixels; the loop over k and the totals of up to four planes
+ * stay in registers (more planes: further workgroups); V(p), the first step of every displacement of a pixel, is evaluated once,
+ * so substeps == 1 reads the lattice once per pixel for all 2 * n_steps positions; s, s / substeps and (s - 1) / substeps are the
+ * same for every pixel and are formed by the entry point on the host, in float64 as written above, and passed by value.  Every
+ * index is formed after its inside test.  No atomics, no LDS, no workgroup waits for another, no loop beyond n_steps * substeps; every output is
+ * bit-reproducible.
+ * RG_EINVAL before any launch: a null rate_prev, rate_next, motion or out, n_planes < 1, h or w negative, the size limit, a
+ * lattice member that is not finite, a step <= 0, ny or nx < 1, hours not finite or <= 0, n_steps, substeps or min_steps out of
+ * range, an unknown method, out or out_steps overlapping an input or each other.  h == 0 or w == 0 returns RG_OK without a
+ * launch. */
+int rg_accumulate_advected_f32(const float* rate_prev, const float* rate_next, int32_t n_planes, int32_t h, int32_t w,
+                               const float* motion, rg_motion_lattice lattice, double hours, int32_t n_steps, int32_t substeps,
+                               int32_t method, int32_t min_steps, float fill, float* out, uint8_t* out_steps, rg_stream_t stream);
 
 #ifdef __cplusplus
 }

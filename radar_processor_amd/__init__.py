@@ -38,6 +38,7 @@ from .motion import (MotionGrid, advect_device, estimate_motion_device, fill_mot
                      nowcast_device, quantize_planes_device)
 from .tracking import (CellMatch, CellOverlap, CellTracker, TrackFrame, advect_labels_device, cell_overlap_device, match_cells,
                        relabel_cells_device)
+from .accumulation import (AccumulationFrame, RainAccumulator, accumulate, accumulate_device, rain_rate_device)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -76,6 +77,7 @@ __all__ = [
     "motion_to_velocity", "MotionGrid",
     "advect_labels_device", "cell_overlap_device", "match_cells", "relabel_cells_device", "CellTracker", "CellOverlap", "CellMatch",
     "TrackFrame",
+    "rain_rate_device", "accumulate_device", "accumulate", "RainAccumulator", "AccumulationFrame",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

@@ -102,6 +102,7 @@ class MotionLattice(Structure):
 RG_MOTION_MAX_BLOCK = 64    # largest block side of rg_block_match_u8 (header: RG_MOTION_MAX_BLOCK)
 RG_MOTION_MAX_SEARCH = 32   # largest search radius (header: RG_MOTION_MAX_SEARCH)
 RG_MAX_LEADS = 16           # lead times one rg_advect_f32 launch takes (header: RG_MAX_LEADS)
+RG_MAX_ACC_STEPS = 64       # sub-instants one rg_accumulate_advected_f32 launch sums (header: RG_MAX_ACC_STEPS)
 RG_MAX_SEL_PLANES = 4       # level selections (constant-elevation PPIs) one planes-mode launch samples
 RG_PPI_SEL_NONE = -1
 
@@ -247,6 +248,10 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "rg_advect_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, MotionLattice, POINTER(c_double), c_int32,
                                 c_int32, c_int32, c_float, c_void_p, c_void_p]),
+    "rg_rain_rate_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_double, c_double, c_double, c_void_p,
+                                   c_void_p]),
+    "rg_accumulate_advected_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, MotionLattice, c_double,
+                                             c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
     "rg_cell_overlap_workspace_bytes": (c_int64, [c_int64]),
     "rg_cell_overlap_i32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

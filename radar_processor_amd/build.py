@@ -37,6 +37,7 @@ SOURCES = [
     ("rg_georef.hip", []),
     ("rg_components.hip", []),
     ("rg_motion.hip", []),
+    ("rg_accumulate.hip", []),
     ("rg_tracking.hip", []),
     ("rg_warp.hip", []),
 ]

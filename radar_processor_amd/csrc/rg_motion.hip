@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "rg_common.hpp"
+#include "rg_motion_field.hpp"
 #include "rg_sample.hpp"
 
 namespace {
@@ -213,24 +214,6 @@ struct Leads {
   double v[RG_MAX_LEADS];
 };
 
-__device__ __forceinline__ double clamp_node(double l, int n) {        // NaN -> 0: no index is ever formed from a NaN
-  const double hi = (double)(n - 1);
-  return !(l >= 0.0) ? 0.0 : (l > hi ? hi : l);
-}
-
-// the header's "motion at a point": both components of the lattice's bilinear interpolant, constant beyond its rim
-__device__ __forceinline__ void motion_at(const float* __restrict__ motion, const rg_motion_lattice& L, double py, double px,
-                                          double* vy, double* vx) {
-  const double ly = clamp_node((py - L.origin_y) / L.step_y, L.ny), lx = clamp_node((px - L.origin_x) / L.step_x, L.nx);
-  const int j0 = min((int)floor(ly), max(L.ny - 2, 0)), i0 = min((int)floor(lx), max(L.nx - 2, 0));
-  const int j1 = min(j0 + 1, L.ny - 1), i1 = min(i0 + 1, L.nx - 1);
-  const double ty = ly - (double)j0, tx = lx - (double)i0;
-  const float* v00 = motion + 2 * ((size_t)j0 * L.nx + i0), *v01 = motion + 2 * ((size_t)j0 * L.nx + i1);
-  const float* v10 = motion + 2 * ((size_t)j1 * L.nx + i0), *v11 = motion + 2 * ((size_t)j1 * L.nx + i1);
-  *vy = ((double)v00[0] * (1.0 - tx) + (double)v01[0] * tx) * (1.0 - ty) + ((double)v10[0] * (1.0 - tx) + (double)v11[0] * tx) * ty;
-  *vx = ((double)v00[1] * (1.0 - tx) + (double)v01[1] * tx) * (1.0 - ty) + ((double)v10[1] * (1.0 - tx) + (double)v11[1] * tx) * ty;
-}
-
 // one thread per pixel and lead (blockIdx.y); src / out as bits where the value is only copied
 template <int METHOD>
 __global__ __launch_bounds__(rg::kBlock) void advect_kernel(const uint32_t* __restrict__ src, int n_planes, int h, int w,
@@ -241,14 +224,9 @@ __global__ __launch_bounds__(rg::kBlock) void advect_kernel(const uint32_t* __re
   if (i >= (long)plane) return;
   const int y = (int)(i / w), x = (int)(i - (long)y * w);
   const double py = (double)y, px = (double)x;
-  const double dt = leads.v[blockIdx.y] / (double)substeps;
-  double dy = 0.0, dx = 0.0;
-  for (int k = 0; k < substeps; ++k) {
-    double vy, vx;
-    motion_at(motion, L, py - dy, px - dx, &vy, &vx);
-    dy = dy + dt * vy;
-    dx = dx + dt * vx;
-  }
+  double v0y, v0x, dy, dx;
+  rg::motion_at(motion, L, py, px, &v0y, &v0x);
+  rg::displacement(motion, L, py, px, v0y, v0x, leads.v[blockIdx.y] / (double)substeps, substeps, &dy, &dx);
   const double fy = py - dy, fx = px - dx;
   uint32_t* o = out + (size_t)blockIdx.y * n_planes * plane + i;
   if constexpr (METHOD == kBilinear) {
