@@ -1155,6 +1155,82 @@ int rg_accumulate_advected_f32(const float* rate_prev, const float* rate_next, i
                                const float* motion, rg_motion_lattice lattice, double hours, int32_t n_steps, int32_t substeps,
                                int32_t method, int32_t min_steps, float fill, float* out, uint8_t* out_steps, rg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Nowcast verification: how good a forecast plane is against the observation it was made for -- categorical counts at
+ * thresholds, the three sums of the fractions skill score (FSS) over a ladder of neighbourhood sizes, and the neighbourhood
+ * exceedance fraction as a product.  (No reference counterpart in radar_grid.  Every sum is an integer and every atomic an
+ * integer add, so every output is bit-reproducible; the tests hold them EQUAL to the NumPy restatement of exactly these
+ * definitions, tests/verification_oracle.py.  The window is scipy.ndimage.uniform_filter(size=n, mode="constant", cval=0)
+ * times n^2, the convention of pysteps' fss; parity with pysteps unpinned.)  rg_contingency_f32, rg_exceedance_sat_i32,
+ * rg_fss_sums_i32 and rg_box_fraction_f32 were ADDED; no signature changed, RG_VERSION stays 104.
+ *
+ * Planes are float32 [n_planes][h][w], row-major, pitch w, no padding; h * w < 2^31 (RG_EINVAL otherwise).  mask (optional, may
+ * be NULL) is uint8 of the same shape, non-zero = leave out.
+ *   valid      a pixel where neither the forecast nor the observation is NaN and the mask is 0.  +-inf are valid values.
+ *   exceeds    a pixel exceeds threshold t when it is valid and `v >= t` in float32.  An invalid pixel exceeds nothing in EITHER
+ *              field: the masking is pairwise, so neither side gets credit for it.
+ *   thresholds 1 .. RG_MAX_VERIFY_THRESHOLDS finite floats, read on the HOST and passed by value; NaN or inf is RG_EINVAL.
+ *   layer      one (plane, threshold) pair, p * n_thr + t.
+ *   window     of scale n (1 .. RG_MAX_VERIFY_SCALE, even sizes allowed) at pixel (y, x): rows y - n/2 .. y - n/2 + n - 1
+ *              (integer division) and the same span of columns, cut to the plane.  Its count is the number of exceeding pixels
+ *              inside; pixels beyond the rim count as 0 (zero padding).
+ * All four launch on `stream`, none allocates, none synchronises.  The outputs that are summed into are cleared with
+ * hipMemsetAsync on `stream` first.  No float atomics, no workgroup waits for another, no unbounded loop, every index is formed
+ * after its bounds test, and a width that is no multiple of 4 or 64 reads nothing outside the plane.
+ * ------------------------------------------------------------------------------------------------- */
+#define RG_MAX_VERIFY_THRESHOLDS 8
+#define RG_MAX_VERIFY_SCALES 16
+#define RG_MAX_VERIFY_SCALE 255
+
+/* counts int64 [n_planes][n_thr][3] = (hits: both exceed, false alarms: the forecast only, misses: the observation only) and
+ * valid int64 [n_planes] = the valid pixels of the plane pair.  Correct negatives are valid - hits - false alarms - misses.
+ * How it runs: a grid-stride pass per plane (blockIdx.y), forecast, observation and mask read once for all thresholds; per
+ * threshold three ballots whose popcounts are wave-uniform; the four wavefronts of a workgroup meet in LDS and the workgroup
+ * issues one relaxed agent-scope 64-bit integer atomic add per non-zero counter; at most 1024 workgroups per plane.
+ * RG_EINVAL before anything touches the device: a null fcst, obs, thresholds_host, counts or valid, n_planes < 1 or > 65535, h
+ * or w negative, the size limit, n_thr outside 1 .. 8, a threshold that is not finite, counts or valid overlapping an input or
+ * each other.  h == 0 or w == 0 zeroes the outputs and returns. */
+int rg_contingency_f32(const float* fcst, const float* obs, const uint8_t* mask, int32_t n_planes, int32_t h, int32_t w,
+                       const float* thresholds_host, int32_t n_thr, int64_t* counts, int64_t* valid, rg_stream_t stream);
+
+/* sat int32 [n_planes][n_thr][h][w]: sat[p][t][y][x] = the number of pixels (y', x') of plane p of src with y' <= y, x' <= x that
+ * exceed threshold t -- the INCLUSIVE summed-area table.  `partner` (optional, may be NULL) float32 of src's shape supplies only
+ * validity: a pixel whose partner is NaN exceeds nothing.  Called once for the forecast with the observation as partner and once
+ * the other way round, with the same mask.
+ * How it runs: pass 1, one wavefront per row in trips of 64 pixels; the predicate is one bit, so per threshold the inclusive
+ * prefix is popcount(ballot & lanes up to me) + carry and carry += popcount(ballot): no shuffles, no LDS; it writes int32 row
+ * prefixes.  Pass 2, one thread per (layer, column) adds down the rows in place, the loads of eight rows issued ahead of the adds.
+ * RG_EINVAL before anything touches the device: a null src, thresholds_host or sat, n_planes < 1, h or w negative, the size
+ * limit, n_thr outside 1 .. 8, a threshold that is not finite, n_planes * n_thr > 65535, sat overlapping an input.  h == 0 or
+ * w == 0 returns RG_OK without a launch. */
+int rg_exceedance_sat_i32(const float* src, const float* partner, const uint8_t* mask, int32_t n_planes, int32_t h, int32_t w,
+                          const float* thresholds_host, int32_t n_thr, int32_t* sat, rg_stream_t stream);
+
+/* sums int64 [n_layers][n_scales][3]: for every layer of the two tables (int32 [n_layers][h][w], as rg_exceedance_sat_i32 writes
+ * them) and every scale n, over ALL h * w pixels,
+ *     sums[0] = sum (cf - co)^2      sums[1] = sum cf^2      sums[2] = sum co^2
+ * with cf and co the window counts of the forecast's and the observation's table: with ya = max(y - n/2, 0) - 1,
+ * yb = min(y - n/2 + n - 1, h - 1), likewise xa and xb,  count = S[yb][xb] - S[ya][xb] - S[yb][xa] + S[ya][xa], a corner at index
+ * -1 contributing 0.  FSS = 1 - sums[0] / (sums[1] + sums[2]).
+ * scales_host: 1 .. RG_MAX_VERIFY_SCALES values in 1 .. RG_MAX_VERIFY_SCALE, read on the HOST and passed by value.
+ * OVERFLOW RULE: a window count is at most m = min(n^2, h * w) and each sum at most m^2 * h * w; a shape and scale for which
+ * m^2 * h * w can reach 2^63 is RG_EINVAL.  (With n <= 255 the size limit h * w < 2^31 implies it: 65025^2 * 2^31 < 2^63.  The rule
+ * is checked on its own all the same, so it keeps holding if either limit moves.)
+ * How it runs: one launch spans (strips of pixels, layer, scale); a thread keeps three 64-bit accumulators over its pixels (eight
+ * table reads each), a wavefront reduces them with shuffles, the four wavefronts of a workgroup through LDS, and the workgroup
+ * issues up to three relaxed agent-scope 64-bit integer atomic adds; at most 1024 workgroups add into one (layer, scale).
+ * RG_EINVAL before anything touches the device: null pointers, n_layers < 1, h or w negative, the size limit, n_scales outside
+ * 1 .. 16, a scale outside 1 .. 255, the overflow rule, sums overlapping a table.  h == 0 or w == 0 zeroes sums and returns. */
+int rg_fss_sums_i32(const int32_t* sat_f, const int32_t* sat_o, int32_t n_layers, int32_t h, int32_t w, const int32_t* scales_host,
+                    int32_t n_scales, int64_t* sums, rg_stream_t stream);
+
+/* out float32 [n_layers][h][w] = (float)((double)count / (double)(scale * scale)) with count the window count of `sat` (above):
+ * the zero-padded neighbourhood exceedance fraction, "the probability of >= t within scale pixels".  One correctly rounded
+ * float64 division and one rounding to float32: NumPy's bits.  One thread per pixel.
+ * RG_EINVAL: a null sat or out, n_layers < 1, h or w negative, the size limit, n_layers * h * w >= 2^40, scale outside 1 .. 255,
+ * out overlapping sat.  h == 0 or w == 0 returns RG_OK without a launch. */
+int rg_box_fraction_f32(const int32_t* sat, int32_t n_layers, int32_t h, int32_t w, int32_t scale, float* out, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

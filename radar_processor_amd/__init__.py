@@ -39,6 +39,8 @@ from .motion import (MotionGrid, advect_device, estimate_motion_device, fill_mot
 from .tracking import (CellMatch, CellOverlap, CellTracker, TrackFrame, advect_labels_device, cell_overlap_device, match_cells,
                        relabel_cells_device)
 from .accumulation import (AccumulationFrame, RainAccumulator, accumulate, accumulate_device, rain_rate_device)
+from .verification import (ContingencyTable, FSSSums, NowcastVerifier, Verification, VerifierFrame, categorical_scores,
+                           contingency_device, exceedance_sat_device, fss_device, neighbourhood_fraction_device, verify_nowcast)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -78,6 +80,8 @@ __all__ = [
     "advect_labels_device", "cell_overlap_device", "match_cells", "relabel_cells_device", "CellTracker", "CellOverlap", "CellMatch",
     "TrackFrame",
     "rain_rate_device", "accumulate_device", "accumulate", "RainAccumulator", "AccumulationFrame",
+    "contingency_device", "categorical_scores", "exceedance_sat_device", "neighbourhood_fraction_device", "fss_device",
+    "verify_nowcast", "NowcastVerifier", "ContingencyTable", "FSSSums", "Verification", "VerifierFrame",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

@@ -103,7 +103,10 @@ RG_MOTION_MAX_BLOCK = 64    # largest block side of rg_block_match_u8 (header: R
 RG_MOTION_MAX_SEARCH = 32   # largest search radius (header: RG_MOTION_MAX_SEARCH)
 RG_MAX_LEADS = 16           # lead times one rg_advect_f32 launch takes (header: RG_MAX_LEADS)
 RG_MAX_ACC_STEPS = 64       # sub-instants one rg_accumulate_advected_f32 launch sums (header: RG_MAX_ACC_STEPS)
-RG_MAX_SEL_PLANES = 4       # level selections (constant-elevation PPIs) one planes-mode launch samples
+RG_MAX_VERIFY_THRESHOLDS = 8   # thresholds one verification launch takes (header: RG_MAX_VERIFY_THRESHOLDS)
+RG_MAX_VERIFY_SCALES = 16      # window sizes one rg_fss_sums_i32 launch takes (header: RG_MAX_VERIFY_SCALES)
+RG_MAX_VERIFY_SCALE = 255      # largest window size (header: RG_MAX_VERIFY_SCALE)
+RG_MAX_SEL_PLANES = 4      # level selections (constant-elevation PPIs) one planes-mode launch samples
 RG_PPI_SEL_NONE = -1
 
 
@@ -256,6 +259,12 @@ SIGNATURES = {
     "rg_cell_overlap_i32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "rg_relabel_cells_i32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "rg_contingency_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), c_int32, c_void_p,
+                                     c_void_p, c_void_p]),
+    "rg_exceedance_sat_i32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), c_int32,
+                                        c_void_p, c_void_p]),
+    "rg_fss_sums_i32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32, c_void_p, c_void_p]),
+    "rg_box_fraction_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -39,6 +39,7 @@ SOURCES = [
     ("rg_motion.hip", []),
     ("rg_accumulate.hip", []),
     ("rg_tracking.hip", []),
+    ("rg_verify.hip", []),
     ("rg_warp.hip", []),
 ]
 
