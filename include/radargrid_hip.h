@@ -1231,6 +1231,89 @@ int rg_fss_sums_i32(const int32_t* sat_f, const int32_t* sat_o, int32_t n_layers
  * out overlapping sat.  h == 0 or w == 0 returns RG_OK without a launch. */
 int rg_box_fraction_f32(const int32_t* sat, int32_t n_layers, int32_t h, int32_t w, int32_t scale, float* out, rg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Convective / stratiform classification after Steiner, Houze and Yuter 1995: the background reflectivity as the mean of LINEAR
+ * reflectivity over a disk, the convective centres (intensity or peakedness over the background), and the convective area as
+ * the union of disks whose radius depends on the centre's background.  (No reference counterpart in radar_grid.  The contract
+ * is build-defined and restated in NumPy, tests/convection_oracle.py; the relations are those PyART's steiner_conv_strat
+ * carries, parity with PyART unpinned.)  rg_echo_table_bytes, rg_echo_table_f32, rg_disk_background, rg_convective_centres_f32,
+ * rg_convective_area_workspace_bytes and rg_convective_area_u8 were ADDED; no signature changed, RG_VERSION stays 104.
+ *
+ * Planes are float32 [n][h][w], row-major, pitch w, no padding; 1 <= n <= 65535 and h * w < 2^31 (RG_EINVAL otherwise).  mask
+ * (optional, may be NULL) is uint8 of the same shape, non-zero = leave out.
+ *   echo       a pixel that is not NaN, whose mask is 0, and with `dBZ >= min_dbz` in float32.  +inf is an echo.
+ *   q          the pixel's linear reflectivity in 2^-16 fixed point: llrint(65536 * 10^(clamp((double)dBZ, -10, 80) / 10)) for an
+ *              echo pixel, 0 otherwise; 6554 .. 6.6e12 < 2^43.  10^x is the device's float64 exp10, so q may differ from
+ *              NumPy's by one unit at a rounding tie and nowhere else.  Every later sum is an INTEGER sum of these q: exact, and
+ *              independent of the order.  Differences of 64-bit row prefixes are exact modulo 2^64 even where a prefix wraps, and
+ *              a disk sum is at most 255^2 * 2^43 < 2^59.
+ *   footprint  half-widths hw[0 .. ry] on the HOST, passed by value; ry in 0 .. RG_MAX_DISK_RADIUS, every hw[d] in
+ *              0 .. RG_MAX_DISK_RADIUS.  At pixel (y, x) it covers columns x - hw[|dy|] .. x + hw[|dy|] of the rows y + dy,
+ *              |dy| <= ry, cut to the plane: pixels beyond the rim contribute nothing.  Any table is taken -- it need not be
+ *              monotone, so boxes and ellipses work too.
+ *   background S int64 = the sum of q over the footprint, N int32 = the echo pixels in it,
+ *              bkg = (float)(10 * log10((double)S / (double)N / 65536.0)), NaN where N == 0; defined for EVERY pixel, echo or not.
+ *   centre     with v = dBZ and b = bkg as float64 and every operation IEEE float64, unfused: an echo pixel with
+ *              `v >= intense`, or `(v - b) >= delta`, delta = peak_a for b < 0 and otherwise c = peak_a - b * b / peak_b where
+ *              c > 0, else 0 (Steiner: peak_a = 10, peak_b = 180).  Its class is k = 1 + (the number of edges e with b >= e) over
+ *              the n_classes - 1 ascending finite edges, n_classes <= RG_MAX_CONV_CLASSES.  A NaN background makes no centre by
+ *              peakedness and class 1 by intensity.  The plane: 0 = no centre, k = a centre of class k.
+ *   area       0 = no echo; 2 = an echo pixel with some centre of class k inside footprint k around it (footprints are symmetric:
+ *              the pixel lies in the centre's disk); 1 = any other echo pixel (stratiform).  One footprint per class.
+ * All launch on `stream`, none allocates, none synchronises.  No atomics, no workgroup waits for another, no unbounded loop, every
+ * index is formed after its bounds test, a width that is no multiple of 4 or 64 reads nothing outside the plane, and there is ONE
+ * launch path, so the same bits come out of every call.  h == 0 or w == 0 returns RG_OK without a launch.
+ * ------------------------------------------------------------------------------------------------- */
+#define RG_MAX_DISK_RADIUS 127
+#define RG_MAX_CONV_CLASSES 8
+
+/* The bytes of the echo table of n planes of h x w (0 for an empty plane), or a negative rg_status for a shape out of range.
+ * The table holds, per row, the exclusive prefixes of q and of the echo count; its layout is opaque (today: one 16-byte entry
+ * per pixel plus one per row). */
+int64_t rg_echo_table_bytes(int32_t n, int32_t h, int32_t w);
+
+/* Builds the echo table of `dbz` into `table` (16-byte aligned device memory of at least rg_echo_table_bytes bytes).
+ * How it runs: one wavefront per row in trips of 64 pixels; the 64-bit prefix of q by a shuffle ladder, the count by one ballot,
+ * the carries in scalar registers.
+ * RG_EINVAL before anything touches the device: a null dbz or table, the shape limits, a min_dbz that is not finite, the table
+ * overlapping an input; RG_EWORKSPACE for table_bytes below the need; RG_EALIGN for a table that is not 16-byte aligned. */
+int rg_echo_table_f32(const float* dbz, const uint8_t* mask, int32_t n, int32_t h, int32_t w, float min_dbz, void* table,
+                      int64_t table_bytes, rg_stream_t stream);
+
+/* The footprint sums of an echo table: out_sum int64 [n][h][w] = S, out_count int32 = N, out_bkg float32 = bkg; each may be NULL,
+ * not all three.  hw_host holds ry + 1 half-widths.  ry = 0 with hw = {0} returns q and the echo flag themselves.
+ * How it runs: one wavefront per 64 pixels of a row, four rows per workgroup; per covered row two loads of one 16-byte entry each,
+ * whose row distance and half-width are wave-uniform; the sum through the shared core of csrc/rg_disk.hpp.
+ * RG_EINVAL: a null table or hw_host, no output, the shape limits, ry or a half-width out of range, an output overlapping the
+ * table or another output; RG_EALIGN for a table that is not 16-byte aligned. */
+int rg_disk_background(const void* table, int32_t n, int32_t h, int32_t w, const int32_t* hw_host, int32_t ry, int64_t* out_sum,
+                       int32_t* out_count, float* out_bkg, rg_stream_t stream);
+
+/* out_class uint8 [n][h][w]: 0, or the class of the convective centre at the pixel (above).  edges_host: n_classes - 1 ascending
+ * finite doubles on the HOST (may be NULL for one class).  One thread per pixel.
+ * RG_EINVAL: a null dbz, bkg or out_class, the shape limits, n_classes outside 1 .. 8, null edges for more than one class,
+ * min_dbz, intense, peak_a, peak_b or an edge that is not finite, peak_b <= 0, a descending edge, out_class overlapping an input. */
+int rg_convective_centres_f32(const float* dbz, const uint8_t* mask, const float* bkg, int32_t n, int32_t h, int32_t w, float min_dbz,
+                              double intense, double peak_a, double peak_b, const double* edges_host, int32_t n_classes,
+                              uint8_t* out_class, rg_stream_t stream);
+
+/* The bytes of the workspace of rg_convective_area_u8 (the row prefixes of the centre count of every class), or a negative
+ * rg_status. */
+int64_t rg_convective_area_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t n_classes);
+
+/* out uint8 [n][h][w] = the area plane (above) of the centre plane `centres` (values beyond n_classes are no centre).  hw_host
+ * int32 [n_classes][RG_MAX_DISK_RADIUS + 1] holds footprint k in row k (its first ry_host[k] + 1 entries are read), ry_host
+ * int32 [n_classes].  Echo is judged from dbz, mask and min_dbz as everywhere.
+ * How it runs: one wavefront per row writes the per-class row prefixes of "is a centre of class k" (one ballot per class and
+ * trip); then per echo pixel the count of every class over its footprint through the SAME core as the background, stopping at
+ * the first class that has one.
+ * RG_EINVAL: null pointers, the shape limits, n_classes, ry or a half-width out of range, a min_dbz that is not finite, a
+ * workspace that is null or not 4-byte aligned, out or the workspace overlapping an operand; RG_EWORKSPACE for a workspace below
+ * the need. */
+int rg_convective_area_u8(const uint8_t* centres, const float* dbz, const uint8_t* mask, int32_t n, int32_t h, int32_t w,
+                          float min_dbz, int32_t n_classes, const int32_t* hw_host, const int32_t* ry_host, void* workspace,
+                          int64_t workspace_bytes, uint8_t* out, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

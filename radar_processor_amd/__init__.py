@@ -41,6 +41,8 @@ from .tracking import (CellMatch, CellOverlap, CellTracker, TrackFrame, advect_l
 from .accumulation import (AccumulationFrame, RainAccumulator, accumulate, accumulate_device, rain_rate_device)
 from .verification import (ContingencyTable, FSSSums, NowcastVerifier, Verification, VerifierFrame, categorical_scores,
                            contingency_device, exceedance_sat_device, fss_device, neighbourhood_fraction_device, verify_nowcast)
+from .convection import (ConvectiveStratiform, classify_grid, convective_stratiform, convective_stratiform_device, disk_footprint,
+                         echo_background_device, rain_rate_by_class_device)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -82,6 +84,8 @@ __all__ = [
     "rain_rate_device", "accumulate_device", "accumulate", "RainAccumulator", "AccumulationFrame",
     "contingency_device", "categorical_scores", "exceedance_sat_device", "neighbourhood_fraction_device", "fss_device",
     "verify_nowcast", "NowcastVerifier", "ContingencyTable", "FSSSums", "Verification", "VerifierFrame",
+    "disk_footprint", "echo_background_device", "convective_stratiform_device", "convective_stratiform", "classify_grid",
+    "rain_rate_by_class_device", "ConvectiveStratiform",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

@@ -106,6 +106,8 @@ RG_MAX_ACC_STEPS = 64       # sub-instants one rg_accumulate_advected_f32 launch
 RG_MAX_VERIFY_THRESHOLDS = 8   # thresholds one verification launch takes (header: RG_MAX_VERIFY_THRESHOLDS)
 RG_MAX_VERIFY_SCALES = 16      # window sizes one rg_fss_sums_i32 launch takes (header: RG_MAX_VERIFY_SCALES)
 RG_MAX_VERIFY_SCALE = 255      # largest window size (header: RG_MAX_VERIFY_SCALE)
+RG_MAX_DISK_RADIUS = 127       # largest footprint radius and half-width in pixels (header: RG_MAX_DISK_RADIUS)
+RG_MAX_CONV_CLASSES = 8        # radius classes of the convective centres (header: RG_MAX_CONV_CLASSES)
 RG_MAX_SEL_PLANES = 4      # level selections (constant-elevation PPIs) one planes-mode launch samples
 RG_PPI_SEL_NONE = -1
 
@@ -265,6 +267,15 @@ SIGNATURES = {
                                         c_void_p, c_void_p]),
     "rg_fss_sums_i32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32, c_void_p, c_void_p]),
     "rg_box_fraction_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "rg_echo_table_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "rg_echo_table_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_int64, c_void_p]),
+    "rg_disk_background": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "rg_convective_centres_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_double, c_double,
+                                            c_double, POINTER(c_double), c_int32, c_void_p, c_void_p]),
+    "rg_convective_area_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "rg_convective_area_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_int32, POINTER(c_int32),
+                                        POINTER(c_int32), c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 _lock = threading.Lock()

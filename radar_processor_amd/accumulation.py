@@ -179,15 +179,31 @@ class RainAccumulator:
     used as it is for every interval.  ``steps``: sub-instants per interval, see :func:`accumulate_device`; ``None`` means the
     estimate's ``search`` under ``"auto"`` -- no vector is longer, so a step moves the echo by at most about a pixel and
     nothing has to be read back -- and 1 without motion.  ``window_seconds``: how far back :meth:`total` reaches, and how long
-    an interval is kept.  ``max_gap_seconds``: two scans further apart are not joined.
+    an interval is kept.  ``max_gap_seconds``: two scans further apart are not joined.  ``convective_zr``: an ``(a, b)`` pair
+    for the convective pixels -- every scan is then classified (:func:`~radar_processor_amd.convection.convective_stratiform_device`
+    with the keywords of ``classify``, which must hold the spacing: ``dx`` / ``dy`` or ``geometry``) and ``a``, ``b`` stay the
+    stratiform relation (:func:`~radar_processor_amd.convection.rain_rate_by_class_device`); ``None`` (the default) classifies
+    nothing and applies ``a``, ``b`` everywhere.
 
     Nothing here synchronises with the host."""
 
     def __init__(self, *, a: float = 200.0, b: float = 1.6, min_dbz: float = 5.0, max_dbz: float = 55.0, motion="auto",
                  steps: Optional[int] = None, method: str = "bilinear", window_seconds: float = 3600.0,
-                 max_gap_seconds: float = 900.0, min_score: float = 0.5, **estimate):
+                 max_gap_seconds: float = 900.0, min_score: float = 0.5, convective_zr=None, classify: Optional[dict] = None,
+                 **estimate):
         _check_zr(a, b, min_dbz, max_dbz)
         self._zr = dict(a=float(a), b=float(b), min_dbz=float(min_dbz), max_dbz=float(max_dbz))
+        self._convective_zr, self._classify = None, None
+        if convective_zr is not None:
+            from .convection import _check_classify                  # convection imports this module
+            try:
+                conv_a, conv_b = convective_zr
+            except (TypeError, ValueError):
+                raise ValueError(f"convective_zr must be an (a, b) pair, not {convective_zr!r}") from None
+            _check_zr(conv_a, conv_b, min_dbz, max_dbz)
+            self._convective_zr, self._classify = (float(conv_a), float(conv_b)), _check_classify(classify)
+        elif classify is not None:
+            raise ValueError("classify holds the keywords of the classification, which runs only with convective_zr")
         unknown = sorted(set(estimate) - set(_TRACKER_ESTIMATE_KEYS))
         if unknown:
             raise ValueError(f"unknown keyword(s) {unknown}: expected some of {list(_TRACKER_ESTIMATE_KEYS)}")
@@ -260,7 +276,13 @@ class RainAccumulator:
         dev = _device_of(plane_dbz, mask) if self._last is None else self._last[1].device
         dbz = _to_device(plane_dbz, dev)
         mask_t = None if mask is None else _to_device(mask, dev, torch.uint8)
-        rate = rain_rate_device(dbz, mask=mask_t, **self._zr)
+        if self._convective_zr is None:
+            rate = rain_rate_device(dbz, mask=mask_t, **self._zr)
+        else:
+            from .convection import convective_stratiform_device, rain_rate_by_class_device
+            classes = convective_stratiform_device(dbz, mask=mask_t, **self._classify)
+            rate = rain_rate_by_class_device(dbz, classes, stratiform=(self._zr["a"], self._zr["b"]), convective=self._convective_zr,
+                                             min_dbz=self._zr["min_dbz"], max_dbz=self._zr["max_dbz"], mask=mask_t)
         last, self._last = self._last, (now, dbz, mask_t, rate)
         if last is None or now - last[0] > self.max_gap_seconds:
             self._intervals = []

@@ -40,6 +40,7 @@ SOURCES = [
     ("rg_accumulate.hip", []),
     ("rg_tracking.hip", []),
     ("rg_verify.hip", []),
+    ("rg_convection.hip", []),
     ("rg_warp.hip", []),
 ]
 
