@@ -1142,7 +1142,7 @@ int rg_rain_rate_f32(const float* src, const uint8_t* mask, int32_t n, int32_t h
  * midpoint rule of the linear blend in time -- the trapezoid rule's value; with n_steps = 1 and prev == next it is hours * rate.
  *   1 <= n_steps <= RG_MAX_ACC_STEPS;  1 <= substeps <= 16;  1 <= min_steps <= n_steps
  * How it runs: one thread per pixel, a workgroup per tile of 8 x 32 pixels; the loop over k and the totals of up to four planes
- * stay in registers (more planes: further workgroups); V(p), the first step of every displacement of a pixel, is evaluated once,
+ * stay in registers (more planes: further workgroups, and beyond 65535 groups of four further launches); V(p), the first step of every displacement of a pixel, is evaluated once,
  * so substeps == 1 reads the lattice once per pixel for all 2 * n_steps positions; s, s / substeps and (s - 1) / substeps are the
  * same for every pixel and are formed by the entry point on the host, in float64 as written above, and passed by value.  Every
  * index is formed after its inside test.  No atomics, no LDS, no workgroup waits for another, no loop beyond n_steps * substeps; every output is

@@ -20,6 +20,7 @@ namespace {
 enum { kNearest = 0, kBilinear = 1 };
 constexpr int kTileW = 32, kTileH = 8;           // kTileW * kTileH == rg::kBlock; a wavefront covers 2 rows of 32 pixels
 constexpr int kPlanes = 4;                       // planes whose sums one thread keeps in registers
+constexpr int kMaxGroups = 65535;                // gridDim.y: groups of kPlanes planes per launch; more take further launches
 constexpr uint32_t kNaNBits = 0x7FC00000u;
 static_assert(kTileW * kTileH == rg::kBlock, "one thread per pixel of the tile");
 
@@ -205,18 +206,21 @@ extern "C" int rg_accumulate_advected_f32(const float* rate_prev, const float* r
   }
   const int groups = n_planes / kPlanes, rest = n_planes % kPlanes;
   const hipStream_t s = (hipStream_t)stream;
-  if (method == kNearest) {
-    if (groups)
-      launch_accumulate<kNearest, kPlanes>(groups, s, rate_prev, rate_next, 0, h, w, motion, lattice, steps, hours, n_steps, substeps,
-                                           min_steps, fill_bits, out, out_steps);
+  // the full groups in runs of at most kMaxGroups, each run one launch that starts at plane group0 * kPlanes; then the remainder
+  for (int group0 = 0; group0 < groups; group0 += kMaxGroups) {
+    const int run = groups - group0 < kMaxGroups ? groups - group0 : kMaxGroups;
+    if (method == kNearest)
+      launch_accumulate<kNearest, kPlanes>(run, s, rate_prev, rate_next, group0 * kPlanes, h, w, motion, lattice, steps, hours, n_steps,
+                                           substeps, min_steps, fill_bits, out, out_steps);
+    else
+      launch_accumulate<kBilinear, kPlanes>(run, s, rate_prev, rate_next, group0 * kPlanes, h, w, motion, lattice, steps, hours, n_steps,
+                                            substeps, min_steps, fill_bits, out, out_steps);
+  }
+  if (method == kNearest)
     launch_rest<kNearest>(rest, s, rate_prev, rate_next, groups * kPlanes, h, w, motion, lattice, steps, hours, n_steps, substeps, min_steps,
                           fill_bits, out, out_steps);
-  } else {
-    if (groups)
-      launch_accumulate<kBilinear, kPlanes>(groups, s, rate_prev, rate_next, 0, h, w, motion, lattice, steps, hours, n_steps, substeps,
-                                            min_steps, fill_bits, out, out_steps);
+  else
     launch_rest<kBilinear>(rest, s, rate_prev, rate_next, groups * kPlanes, h, w, motion, lattice, steps, hours, n_steps, substeps,
                            min_steps, fill_bits, out, out_steps);
-  }
   return rg::check_launch(who);
 }
