@@ -43,6 +43,25 @@ inline bool georef_finite(const rg_georef& g) {
 constexpr int kWave = 64;        // CDNA4 wavefront
 constexpr int kBlock = 256;      // 4 waves per workgroup
 
+// ---- clearing accumulators and scratch on the stream ----
+// A kernel, not hipMemsetAsync.  Observed with HIP 7.0 (tests/test_gpu_graph_replay.py; the cause inside the runtime is not
+// established): a captured graph zeroes through a memset node on its first replay only; from the second replay on the words
+// come out as a repeating 16 bytes of other data, as if the node's fill pattern were read from memory that has been reused.
+// A kernel node keeps `value` among its own arguments, so it does not depend on that.
+template <int = 0>
+__global__ __launch_bounds__(kBlock) void fill_words_kernel(uint32_t* __restrict__ p, long n, uint32_t value) {
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) p[i] = value;
+}
+
+// `bytes` (a multiple of 4, below 2^40) at the 4-byte aligned `p` become copies of the 32-bit `value`; enqueues, never waits
+inline void fill_words(void* p, int64_t bytes, uint32_t value, hipStream_t s) {
+  const long n = (long)(bytes / 4);
+  if (n > 0)
+    hipLaunchKernelGGL(fill_words_kernel<>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, static_cast<uint32_t*>(p),
+                       n, value);
+}
+
 // float32 slots per gate of the packed fields (rg_pack_fields_f32) for a pass of nf fields: the gather is one 4-, 8- or
 // 16-byte load, or two of 16
 constexpr int stride_for(int nf) { return nf == 1 ? 1 : nf == 2 ? 2 : nf <= 4 ? 4 : 8; }

@@ -458,8 +458,8 @@ extern "C" int rg_label_components_f32(const float* src, const uint8_t* mask, in
   hipStream_t s = (hipStream_t)stream;
   const long hw = (long)h * w, n = n_planes * hw;
   if (n == 0) {
-    RG_REQUIRE(hipMemsetAsync(cell_ptr, 0, ((size_t)n_planes + 1) * 4, s) == hipSuccess, RG_ELAUNCH, "%s: memset failed", who);
-    return RG_OK;
+    rg::fill_words(cell_ptr, ((int64_t)n_planes + 1) * 4, 0u, s);
+    return rg::check_launch(who);
   }
   RG_REQUIRE(src && labels && workspace, RG_EINVAL, "%s: null pointer", who);
   RG_REQUIRE(aligned_to(src, 4) && aligned_to(labels, 4) && aligned_to(workspace, 4), RG_EALIGN,

@@ -8,7 +8,7 @@
 //   counts  int32  [C]   pixels of the pair
 // A slot is claimed with one compare-and-swap; a thread that loses it looks at the key that won and either adds to it or moves
 // on.  Nobody waits for anybody: the probe loop ends after C slots at the latest and then counts a dropped insertion.
-//   clear    hipMemsetAsync of the table and of totals
+//   clear    rg::fill_words over the table and totals (a kernel: see rg_common.hpp)
 //   count    the pass over the pixels
 //   compact  one thread per slot; occupied slots take an output index from totals[0], one atomic per wavefront
 #include <limits.h>
@@ -168,14 +168,13 @@ extern "C" int rg_cell_overlap_i32(const int32_t* labels_prev, const int32_t* ce
     for (const auto& in : ins)
       RG_REQUIRE(!rg::overlap(o.p, o.bytes, in.p, in.bytes), RG_EINVAL, "%s: an output or the workspace overlaps an input", who);
   hipStream_t s = (hipStream_t)stream;
-  RG_REQUIRE(hipMemsetAsync(totals, 0, 8, s) == hipSuccess, RG_ELAUNCH, "%s: memset failed", who);
-  if (n == 0) return RG_OK;
+  rg::fill_words(totals, 8, 0u, s);
+  if (n == 0) return rg::check_launch(who);
   const int64_t capacity = capacity_of(max_pairs);
   unsigned long long* keys = static_cast<unsigned long long*>(workspace);
   int* counts = reinterpret_cast<int*>(keys + capacity);
-  RG_REQUIRE(hipMemsetAsync(keys, 0xFF, (size_t)capacity * 8, s) == hipSuccess &&
-                 hipMemsetAsync(counts, 0, (size_t)capacity * 4, s) == hipSuccess,
-             RG_ELAUNCH, "%s: memset failed", who);
+  rg::fill_words(keys, capacity * 8, 0xFFFFFFFFu, s);
+  rg::fill_words(counts, capacity * 4, 0u, s);
   hipLaunchKernelGGL(overlap_count_kernel, dim3(blocks_for(n)), dim3(rg::kBlock), 0, s, labels_prev, cell_ptr_prev, labels_next,
                      cell_ptr_next, hw, n, (unsigned)(capacity - 1), keys, counts, totals);
   hipLaunchKernelGGL(overlap_compact_kernel, dim3(blocks_for(capacity)), dim3(rg::kBlock), 0, s, keys, counts, (long)capacity,

@@ -254,10 +254,9 @@ extern "C" int rg_contingency_f32(const float* fcst, const float* obs, const uin
                  !rg::overlap(obs, in_bytes, counts, count_bytes) && !rg::overlap(obs, in_bytes, valid, (int64_t)n_planes * 8),
              RG_EINVAL, "%s: an output overlaps an input", who);
   const hipStream_t s = (hipStream_t)stream;
-  RG_REQUIRE(hipMemsetAsync(counts, 0, (size_t)count_bytes, s) == hipSuccess &&
-                 hipMemsetAsync(valid, 0, (size_t)n_planes * 8, s) == hipSuccess,
-             RG_ELAUNCH, "%s: memset failed", who);
-  if (hw == 0) return RG_OK;
+  rg::fill_words(counts, count_bytes, 0u, s);
+  rg::fill_words(valid, (int64_t)n_planes * 8, 0u, s);
+  if (hw == 0) return rg::check_launch(who);
   hipLaunchKernelGGL(contingency_kernel, dim3(strips_for(hw), (unsigned)n_planes), dim3(rg::kBlock), 0, s, fcst, obs, mask, (int)hw,
                      thr, n_thr, reinterpret_cast<long long*>(counts), reinterpret_cast<long long*>(valid));
   return rg::check_launch(who);
@@ -309,8 +308,8 @@ extern "C" int rg_fss_sums_i32(const int32_t* sat_f, const int32_t* sat_o, int32
   RG_REQUIRE(!rg::overlap(sat_f, sat_bytes, sums, sum_bytes) && !rg::overlap(sat_o, sat_bytes, sums, sum_bytes), RG_EINVAL,
              "%s: sums overlaps an input", who);
   const hipStream_t s = (hipStream_t)stream;
-  RG_REQUIRE(hipMemsetAsync(sums, 0, (size_t)sum_bytes, s) == hipSuccess, RG_ELAUNCH, "%s: memset failed", who);
-  if (hw == 0) return RG_OK;
+  rg::fill_words(sums, sum_bytes, 0u, s);
+  if (hw == 0) return rg::check_launch(who);
   for (int64_t layer0 = 0; layer0 < n_layers; layer0 += kLayersPerLaunch) {
     const unsigned layers = (unsigned)std::min<int64_t>(n_layers - layer0, kLayersPerLaunch);
     hipLaunchKernelGGL(fss_sums_kernel, dim3(strips_for(hw), layers, (unsigned)n_scales), dim3(rg::kBlock), 0, s, sat_f, sat_o,
