@@ -151,10 +151,10 @@ class VolumeBatch:
         return a.to(device=self.dev, dtype=dtype).contiguous()
 
     def _stage(self, volumes, group, slot_set, copy_stream):
-        """Device tensors of one group's fields and masks.  Inputs already on the device pass through; anything that has
-        to cross PCIe is copied on ``copy_stream`` into one of two persistent sets of staging buffers (no allocation per
-        step, nothing for the caching allocator to keep alive across streams).  Returns ``(fields, masks, event or
-        None)`` -- the event marks the end of the copies."""
+        """Device tensors of one group's fields and masks.  Inputs already on the device pass through (converted, where
+        they need it, on the current stream); anything that has to cross PCIe is copied on ``copy_stream`` into one of two
+        persistent sets of staging buffers (no allocation per step, nothing for the caching allocator to keep alive
+        across streams).  Returns ``(fields, masks, event or None)`` -- the event marks the end of the copies."""
         import torch
 
         def on_device(a):
@@ -171,22 +171,25 @@ class VolumeBatch:
             self._staging = [(torch.empty((slots, n_gates), dtype=torch.float32, device=self.dev),
                               torch.empty((slots, n_gates), dtype=torch.uint8, device=self.dev)) for _ in range(2)]
             self._staging_free = [None, None]
+            # the blocks come from the caller's stream's pool: work queued there earlier may still read their previous tenant
+            copy_stream.wait_stream(torch.cuda.current_stream())
         vals, msks = self._staging[slot_set]
-        fields, masks = [], []
+        fields, masks, uploads = [], [], []
+        k = 0
+        for b in group:
+            for name in self.field_names:
+                for a, buf, out in zip(volumes[b][name], (vals[k], msks[k]), (fields, masks)):
+                    if a is None or on_device(a):   # a conversion runs on the caller's stream, behind the tensor's producer
+                        out.append(a if a is None else self._to_dev(a, buf.dtype))
+                        continue
+                    uploads.append((buf, a if type(a).__module__.startswith("torch") else torch.from_numpy(np.ascontiguousarray(a))))
+                    out.append(buf)
+                k += 1
         with torch.cuda.stream(copy_stream):
             if self._staging_free[slot_set] is not None:      # the pass that last read this set must have finished
                 copy_stream.wait_event(self._staging_free[slot_set])
-            k = 0
-            for b in group:
-                for name in self.field_names:
-                    for a, buf, out in zip(volumes[b][name], (vals[k], msks[k]), (fields, masks)):
-                        if a is None or on_device(a):
-                            out.append(a if a is None else self._to_dev(a, buf.dtype))
-                            continue
-                        src = a if type(a).__module__.startswith("torch") else torch.from_numpy(np.ascontiguousarray(a))
-                        buf.copy_(src.reshape(-1), non_blocking=True)
-                        out.append(buf)
-                    k += 1
+            for buf, src in uploads:
+                buf.copy_(src.reshape(-1), non_blocking=True)
             event = copy_stream.record_event()
         return fields, masks, event
 
