@@ -43,6 +43,8 @@ from .verification import (ContingencyTable, FSSSums, NowcastVerifier, Verificat
                            contingency_device, exceedance_sat_device, fss_device, neighbourhood_fraction_device, verify_nowcast)
 from .convection import (ConvectiveStratiform, classify_grid, convective_stratiform, convective_stratiform_device, disk_footprint,
                          echo_background_device, rain_rate_by_class_device)
+from .ensemble import (EnsembleProducts, ProbabilityTable, ensemble_exceedance_device, ensemble_histogram_device,
+                       motion_perturbations, probabilistic_nowcast, probabilistic_nowcast_device, probability_scores)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -86,6 +88,8 @@ __all__ = [
     "verify_nowcast", "NowcastVerifier", "ContingencyTable", "FSSSums", "Verification", "VerifierFrame",
     "disk_footprint", "echo_background_device", "convective_stratiform_device", "convective_stratiform", "classify_grid",
     "rain_rate_by_class_device", "ConvectiveStratiform",
+    "motion_perturbations", "ensemble_exceedance_device", "probabilistic_nowcast_device", "probabilistic_nowcast",
+    "ensemble_histogram_device", "probability_scores", "EnsembleProducts", "ProbabilityTable",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

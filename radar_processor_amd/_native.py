@@ -108,6 +108,7 @@ RG_MAX_VERIFY_SCALES = 16      # window sizes one rg_fss_sums_i32 launch takes (
 RG_MAX_VERIFY_SCALE = 255      # largest window size (header: RG_MAX_VERIFY_SCALE)
 RG_MAX_DISK_RADIUS = 127       # largest footprint radius and half-width in pixels (header: RG_MAX_DISK_RADIUS)
 RG_MAX_CONV_CLASSES = 8        # radius classes of the convective centres (header: RG_MAX_CONV_CLASSES)
+RG_MAX_MEMBERS = 64            # ensemble members one rg_ensemble_exceedance_f32 launch takes (radargrid_ensemble.h: RG_MAX_MEMBERS)
 RG_MAX_SEL_PLANES = 4      # level selections (constant-elevation PPIs) one planes-mode launch samples
 RG_PPI_SEL_NONE = -1
 
@@ -278,6 +279,16 @@ SIGNATURES = {
                                         POINTER(c_int32), c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/radargrid_ensemble.h one to one.  A table of its own, bound after SIGNATURES from
+# the same library: the probabilistic nowcasts were added without touching radargrid_hip.h or the table above.
+ENSEMBLE_SIGNATURES = {
+    "rg_ensemble_exceedance_f32": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, MotionLattice, POINTER(c_double), c_int32, c_int32,
+                                             c_int32, c_void_p, c_int32, POINTER(c_float), c_int32, c_int32, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
+    "rg_ensemble_histogram_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                           POINTER(c_float), c_int32, c_void_p, c_void_p, c_void_p]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -308,7 +319,7 @@ def load_library(require_device: bool = True):
                 raise NativeUnavailable(
                     f"{LIB_PATH} was built from header version {built_for}, this package binds version {ABI_VERSION}: the "
                     "signatures differ, calling it would shift arguments. Rebuild it with `python -m radar_processor_amd.build`.")
-            for name, (restype, argtypes) in SIGNATURES.items():
+            for name, (restype, argtypes) in list(SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:

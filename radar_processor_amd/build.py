@@ -41,6 +41,7 @@ SOURCES = [
     ("rg_tracking.hip", []),
     ("rg_verify.hip", []),
     ("rg_convection.hip", []),
+    ("rg_ensemble.hip", []),
     ("rg_warp.hip", []),
 ]
 
@@ -48,6 +49,9 @@ SOURCES = [
 # never fuses a multiply with an add (on AMD, HIP's __fmul_rn/__fadd_rn are plain operators and do not stop the
 # compiler from contracting).  None of the kernels is FMA-throughput bound, so this costs nothing measurable.
 COMMON_FLAGS = ["-ffp-contract=off"]
+
+# the public headers: radargrid_hip.h, and radargrid_ensemble.h for the entry points of rg_ensemble.hip (two headers)
+PUBLIC_HEADERS = ["radargrid_hip.h", "radargrid_ensemble.h"]
 
 
 def _hipcc() -> str:
@@ -72,7 +76,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             force = f.read().strip() != source_digest() and all(
                 not _stale(os.path.join(CSRC, src.replace(".hip", ".o")), sources_and_headers()) for src, _ in SOURCES)
     headers = ([os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")]
-               + [os.path.join(INCLUDE, "radargrid_hip.h")])
+               + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS])
     common = ["-std=c++17", "-O3", f"--offload-arch={ARCH}", "-fPIC",
               f"-I{INCLUDE}", f"-I{CSRC}", "-Wall", "-Wno-unused-result", *COMMON_FLAGS]
     objs, jobs = [], []
@@ -107,7 +111,7 @@ def sources_and_headers() -> List[str]:
     """Every file the library is compiled from."""
     return ([os.path.join(CSRC, src) for src, _ in SOURCES if os.path.exists(os.path.join(CSRC, src))]
             + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")]
-            + [os.path.join(INCLUDE, "radargrid_hip.h")])
+            + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS])
 
 
 STAMP_PATH = LIB_PATH + ".stamp"
