@@ -45,6 +45,8 @@ from .convection import (ConvectiveStratiform, classify_grid, convective_stratif
                          echo_background_device, rain_rate_by_class_device)
 from .ensemble import (EnsembleProducts, ProbabilityTable, ensemble_exceedance_device, ensemble_histogram_device,
                        motion_perturbations, probabilistic_nowcast, probabilistic_nowcast_device, probability_scores)
+from .phase import (ATTENUATION_COEFFICIENTS, AttenuationCorrection, PhaseFit, PhaseProducts, correct_attenuation_device,
+                    fit_phidp_device, process_phase, process_phase_device, unfold_phidp_device)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -90,6 +92,8 @@ __all__ = [
     "rain_rate_by_class_device", "ConvectiveStratiform",
     "motion_perturbations", "ensemble_exceedance_device", "probabilistic_nowcast_device", "probabilistic_nowcast",
     "ensemble_histogram_device", "probability_scores", "EnsembleProducts", "ProbabilityTable",
+    "unfold_phidp_device", "fit_phidp_device", "correct_attenuation_device", "process_phase_device", "process_phase",
+    "ATTENUATION_COEFFICIENTS", "PhaseFit", "AttenuationCorrection", "PhaseProducts",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

@@ -289,6 +289,22 @@ ENSEMBLE_SIGNATURES = {
                                            POINTER(c_float), c_int32, c_void_p, c_void_p, c_void_p]),
 }
 
+RG_PHASE_MAX_GATES = 32768         # gates of one ray (radargrid_phase.h: RG_PHASE_MAX_GATES)
+RG_PHASE_MAX_CLASSES = 4           # half-window classes of rg_phidp_fit_f32 (radargrid_phase.h: RG_PHASE_MAX_CLASSES)
+RG_PHASE_MAX_HALF_WINDOW = 255     # largest half-window in gates (radargrid_phase.h: RG_PHASE_MAX_HALF_WINDOW)
+RG_PHASE_MAX_WORKGROUPS = 16777215 # workgroups of 256 one launch holds (radargrid_phase.h: RG_PHASE_MAX_WORKGROUPS)
+RG_PHASE_MAX_ABS_PHI = 16384       # |phi| in degrees beyond which a gate is left out of a fit (radargrid_phase.h)
+
+# name -> (restype, argtypes); mirrors include/radargrid_phase.h one to one.  The third table, bound after the other two from the
+# same library: the polar-domain phase processing was added without touching either header or either table above.
+PHASE_SIGNATURES = {
+    "rg_phidp_unfold_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
+    "rg_phidp_fit_f32": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, POINTER(c_double), POINTER(c_int32), c_int32, c_int32,
+                                   c_int32, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rg_attenuation_phidp_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -319,7 +335,8 @@ def load_library(require_device: bool = True):
                 raise NativeUnavailable(
                     f"{LIB_PATH} was built from header version {built_for}, this package binds version {ABI_VERSION}: the "
                     "signatures differ, calling it would shift arguments. Rebuild it with `python -m radar_processor_amd.build`.")
-            for name, (restype, argtypes) in list(SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()):
+            for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items())
+                                              + list(PHASE_SIGNATURES.items())):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:

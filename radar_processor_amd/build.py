@@ -42,6 +42,7 @@ SOURCES = [
     ("rg_verify.hip", []),
     ("rg_convection.hip", []),
     ("rg_ensemble.hip", []),
+    ("rg_phase.hip", []),
     ("rg_warp.hip", []),
 ]
 
@@ -50,8 +51,9 @@ SOURCES = [
 # compiler from contracting).  None of the kernels is FMA-throughput bound, so this costs nothing measurable.
 COMMON_FLAGS = ["-ffp-contract=off"]
 
-# the public headers: radargrid_hip.h, and radargrid_ensemble.h for the entry points of rg_ensemble.hip (two headers)
-PUBLIC_HEADERS = ["radargrid_hip.h", "radargrid_ensemble.h"]
+# the public headers: radargrid_hip.h, radargrid_ensemble.h for the entry points of rg_ensemble.hip and radargrid_phase.h for
+# those of rg_phase.hip (two headers, and K15 for the third)
+PUBLIC_HEADERS = ["radargrid_hip.h", "radargrid_ensemble.h", "radargrid_phase.h"]
 
 
 def _hipcc() -> str:
