@@ -47,6 +47,9 @@ from .ensemble import (EnsembleProducts, ProbabilityTable, ensemble_exceedance_d
                        motion_perturbations, probabilistic_nowcast, probabilistic_nowcast_device, probability_scores)
 from .phase import (ATTENUATION_COEFFICIENTS, AttenuationCorrection, PhaseFit, PhaseProducts, correct_attenuation_device,
                     fit_phidp_device, process_phase, process_phase_device, unfold_phidp_device)
+from .velocity import (DealiasedVelocity, RegionEdges, VelocityRegions, apply_folds_device, dealias_velocity,
+                       dealias_velocity_device, merge_regions, region_edges_device, split_velocity_device,
+                       velocity_regions_device)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -94,6 +97,8 @@ __all__ = [
     "ensemble_histogram_device", "probability_scores", "EnsembleProducts", "ProbabilityTable",
     "unfold_phidp_device", "fit_phidp_device", "correct_attenuation_device", "process_phase_device", "process_phase",
     "ATTENUATION_COEFFICIENTS", "PhaseFit", "AttenuationCorrection", "PhaseProducts",
+    "split_velocity_device", "velocity_regions_device", "region_edges_device", "merge_regions", "apply_folds_device",
+    "dealias_velocity_device", "dealias_velocity", "VelocityRegions", "RegionEdges", "DealiasedVelocity",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

@@ -305,6 +305,25 @@ PHASE_SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+RG_VELOCITY_MAX_ABS = 16384           # |v| in m/s beyond which a gate is not valid (radargrid_velocity.h: RG_VELOCITY_MAX_ABS)
+RG_VELOCITY_MAX_NYQUIST = 8192        # the largest Nyquist velocity in m/s (radargrid_velocity.h: RG_VELOCITY_MAX_NYQUIST)
+RG_VELOCITY_MIN_BANDS = 2             # n_bands from (radargrid_velocity.h: RG_VELOCITY_MIN_BANDS)
+RG_VELOCITY_MAX_BANDS = 8             # ... to (radargrid_velocity.h: RG_VELOCITY_MAX_BANDS)
+RG_VELOCITY_SWEEPS_PER_LAUNCH = 64    # Nyquist velocities one launch carries (radargrid_velocity.h)
+
+# name -> (restype, argtypes); mirrors include/radargrid_velocity.h one to one.  The fourth table, bound after the other three
+# from the same library: velocity dealiasing was added without touching a header or a table above.
+VELOCITY_SIGNATURES = {
+    "rg_velocity_split_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_double), c_int32, c_void_p,
+                                        c_void_p]),
+    "rg_velocity_regions_i32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "rg_region_edges_workspace_bytes": (c_int64, [c_int64]),
+    "rg_region_edges_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rg_velocity_apply_folds_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_double),
+                                              c_void_p, c_void_p, c_void_p]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -336,7 +355,7 @@ def load_library(require_device: bool = True):
                     f"{LIB_PATH} was built from header version {built_for}, this package binds version {ABI_VERSION}: the "
                     "signatures differ, calling it would shift arguments. Rebuild it with `python -m radar_processor_amd.build`.")
             for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items())
-                                              + list(PHASE_SIGNATURES.items())):
+                                              + list(PHASE_SIGNATURES.items()) + list(VELOCITY_SIGNATURES.items())):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:

@@ -43,6 +43,7 @@ SOURCES = [
     ("rg_convection.hip", []),
     ("rg_ensemble.hip", []),
     ("rg_phase.hip", []),
+    ("rg_velocity.hip", []),
     ("rg_warp.hip", []),
 ]
 
@@ -54,6 +55,9 @@ COMMON_FLAGS = ["-ffp-contract=off"]
 # the public headers: radargrid_hip.h, radargrid_ensemble.h for the entry points of rg_ensemble.hip and radargrid_phase.h for
 # those of rg_phase.hip (two headers, and K15 for the third)
 PUBLIC_HEADERS = ["radargrid_hip.h", "radargrid_ensemble.h", "radargrid_phase.h"]
+# the headers of the polar domain that came after those three: radargrid_velocity.h for the entry points of rg_velocity.hip
+# (DESIGN.md K16).  A list of its own, appended wherever the public headers are used.
+POLAR_HEADERS = ["radargrid_velocity.h"]
 
 
 def _hipcc() -> str:
@@ -78,7 +82,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             force = f.read().strip() != source_digest() and all(
                 not _stale(os.path.join(CSRC, src.replace(".hip", ".o")), sources_and_headers()) for src, _ in SOURCES)
     headers = ([os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")]
-               + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS])
+               + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS + POLAR_HEADERS])
     common = ["-std=c++17", "-O3", f"--offload-arch={ARCH}", "-fPIC",
               f"-I{INCLUDE}", f"-I{CSRC}", "-Wall", "-Wno-unused-result", *COMMON_FLAGS]
     objs, jobs = [], []
@@ -113,7 +117,7 @@ def sources_and_headers() -> List[str]:
     """Every file the library is compiled from."""
     return ([os.path.join(CSRC, src) for src, _ in SOURCES if os.path.exists(os.path.join(CSRC, src))]
             + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")]
-            + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS])
+            + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS + POLAR_HEADERS])
 
 
 STAMP_PATH = LIB_PATH + ".stamp"
