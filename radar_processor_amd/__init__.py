@@ -50,6 +50,8 @@ from .phase import (ATTENUATION_COEFFICIENTS, AttenuationCorrection, PhaseFit, P
 from .velocity import (DealiasedVelocity, RegionEdges, VelocityRegions, apply_folds_device, dealias_velocity,
                        dealias_velocity_device, merge_regions, region_edges_device, split_velocity_device,
                        velocity_regions_device)
+from .shear import (ShearWindow, VelocityShear, azimuthal_shear_device, llsd_window, median_filter_device, velocity_shear,
+                    velocity_shear_device)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -99,6 +101,8 @@ __all__ = [
     "ATTENUATION_COEFFICIENTS", "PhaseFit", "AttenuationCorrection", "PhaseProducts",
     "split_velocity_device", "velocity_regions_device", "region_edges_device", "merge_regions", "apply_folds_device",
     "dealias_velocity_device", "dealias_velocity", "VelocityRegions", "RegionEdges", "DealiasedVelocity",
+    "llsd_window", "median_filter_device", "velocity_shear_device", "azimuthal_shear_device", "velocity_shear", "ShearWindow",
+    "VelocityShear",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

@@ -324,6 +324,20 @@ VELOCITY_SIGNATURES = {
                                               c_void_p, c_void_p, c_void_p]),
 }
 
+RG_SHEAR_MEDIAN_MAX_HALF = 2          # half-widths of the median window from 0 to (radargrid_shear.h: RG_SHEAR_MEDIAN_MAX_HALF)
+RG_SHEAR_MAX_HALF_RAYS = 16           # the LLSD window: half-width in rays at most (radargrid_shear.h: RG_SHEAR_MAX_HALF_RAYS)
+RG_SHEAR_MAX_HALF_GATES = 16          # ... and in gates (radargrid_shear.h: RG_SHEAR_MAX_HALF_GATES)
+RG_SHEAR_MAX_WINDOW = 1089            # 33 * 33 gates: the largest count (radargrid_shear.h: RG_SHEAR_MAX_WINDOW)
+
+# name -> (restype, argtypes); mirrors include/radargrid_shear.h one to one.  The fifth table, bound after the other four from
+# the same library: the LLSD was added without touching a header or a table above.
+SHEAR_SIGNATURES = {
+    "rg_polar_median_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                      c_void_p, c_void_p]),
+    "rg_velocity_llsd_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_double,
+                                       c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -355,7 +369,8 @@ def load_library(require_device: bool = True):
                     f"{LIB_PATH} was built from header version {built_for}, this package binds version {ABI_VERSION}: the "
                     "signatures differ, calling it would shift arguments. Rebuild it with `python -m radar_processor_amd.build`.")
             for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items())
-                                              + list(PHASE_SIGNATURES.items()) + list(VELOCITY_SIGNATURES.items())):
+                                              + list(PHASE_SIGNATURES.items()) + list(VELOCITY_SIGNATURES.items())
+                                              + list(SHEAR_SIGNATURES.items())):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
