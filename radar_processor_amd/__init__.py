@@ -52,6 +52,9 @@ from .velocity import (DealiasedVelocity, RegionEdges, VelocityRegions, apply_fo
                        velocity_regions_device)
 from .shear import (ShearWindow, VelocityShear, azimuthal_shear_device, llsd_window, median_filter_device, velocity_shear,
                     velocity_shear_device)
+from .hydrometeor import (HYDROMETEOR_CLASSES, HYDROMETEOR_TABLE_S_BAND, HYDROMETEOR_VARIABLES, FuzzyClasses, HydrometeorClasses,
+                          MembershipTable, Texture, beam_temperature, class_mask_device, classify_device, classify_hydrometeors,
+                          classify_hydrometeors_device, texture, texture_device)
 from .processor_seam import build_grid3d_package
 from .raster import (PlaneTest, apply_colormap_to_array, apply_filter_masks, collapse_field_3d_to_2d,
                      collapse_grid_to_2d, collapse_plane_device, colormap_lut, colormap_rgba_device,
@@ -103,6 +106,9 @@ __all__ = [
     "dealias_velocity_device", "dealias_velocity", "VelocityRegions", "RegionEdges", "DealiasedVelocity",
     "llsd_window", "median_filter_device", "velocity_shear_device", "azimuthal_shear_device", "velocity_shear", "ShearWindow",
     "VelocityShear",
+    "texture_device", "texture", "MembershipTable", "classify_device", "beam_temperature", "classify_hydrometeors_device",
+    "classify_hydrometeors", "class_mask_device", "HYDROMETEOR_TABLE_S_BAND", "HYDROMETEOR_CLASSES", "HYDROMETEOR_VARIABLES",
+    "Texture", "FuzzyClasses", "HydrometeorClasses",
     "collapse_plane_device", "plane_filter_device", "PlaneTest", "colormap_lut", "colormap_rgba_device",
     "NativeUnavailable", "NativeError", "load_library",
 ]

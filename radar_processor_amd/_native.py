@@ -338,6 +338,26 @@ SHEAR_SIGNATURES = {
                                        c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+RG_HYDRO_TEXTURE_SHIFT = 10           # the fixed point of the texture: q = x * 2^10 (radargrid_hydro.h: RG_HYDRO_TEXTURE_SHIFT)
+RG_HYDRO_MAX_ABS = 8192               # |x| beyond which a gate is not valid for the texture (radargrid_hydro.h: RG_HYDRO_MAX_ABS)
+RG_HYDRO_MAX_HALF_GATES = 63          # the texture window: half-width in gates at most (radargrid_hydro.h)
+RG_HYDRO_TEXTURE_TILE = 512           # gates of one ray a workgroup of the texture takes at a time (radargrid_hydro.h)
+RG_HYDRO_MAX_VARS = 8                 # variables of the classifier (radargrid_hydro.h: RG_HYDRO_MAX_VARS)
+RG_HYDRO_MAX_CLASSES = 16             # classes (radargrid_hydro.h: RG_HYDRO_MAX_CLASSES)
+RG_HYDRO_MAX_BINS = 32                # bins of the condition variable (radargrid_hydro.h: RG_HYDRO_MAX_BINS)
+RG_HYDRO_MAX_CELLS = 1024             # B * C * V at most (radargrid_hydro.h: RG_HYDRO_MAX_CELLS)
+RG_HYDRO_UNCLASSIFIED = 0             # cls of a gate without a class (radargrid_hydro.h: RG_HYDRO_UNCLASSIFIED)
+
+# name -> (restype, argtypes); mirrors include/radargrid_hydro.h one to one.  The sixth table, bound after the other five from
+# the same library: the hydrometeor classification was added without touching a header or a table above.
+HYDRO_SIGNATURES = {
+    "rg_polar_texture_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "rg_fuzzy_classify_f32": (c_int32, [POINTER(c_void_p), POINTER(c_int32), c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                        c_int32, c_int32, POINTER(c_double), c_int32, c_void_p, c_int32, POINTER(c_double), c_double,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -370,7 +390,7 @@ def load_library(require_device: bool = True):
                     "signatures differ, calling it would shift arguments. Rebuild it with `python -m radar_processor_amd.build`.")
             for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items())
                                               + list(PHASE_SIGNATURES.items()) + list(VELOCITY_SIGNATURES.items())
-                                              + list(SHEAR_SIGNATURES.items())):
+                                              + list(SHEAR_SIGNATURES.items()) + list(HYDRO_SIGNATURES.items())):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:

@@ -45,6 +45,7 @@ SOURCES = [
     ("rg_phase.hip", []),
     ("rg_velocity.hip", []),
     ("rg_shear.hip", []),
+    ("rg_hydro.hip", []),
     ("rg_warp.hip", []),
 ]
 
@@ -61,6 +62,8 @@ PUBLIC_HEADERS = ["radargrid_hip.h", "radargrid_ensemble.h", "radargrid_phase.h"
 POLAR_HEADERS = ["radargrid_velocity.h"]
 # radargrid_shear.h for the entry points of rg_shear.hip: again a list of its own, appended where the others are
 SHEAR_HEADERS = ["radargrid_shear.h"]
+# radargrid_hydro.h for the entry points of rg_hydro.hip: the same again
+HYDRO_HEADERS = ["radargrid_hydro.h"]
 
 
 def _hipcc() -> str:
@@ -85,7 +88,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             force = f.read().strip() != source_digest() and all(
                 not _stale(os.path.join(CSRC, src.replace(".hip", ".o")), sources_and_headers()) for src, _ in SOURCES)
     headers = ([os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")]
-               + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS + POLAR_HEADERS + SHEAR_HEADERS])
+               + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS + POLAR_HEADERS + SHEAR_HEADERS + HYDRO_HEADERS])
     common = ["-std=c++17", "-O3", f"--offload-arch={ARCH}", "-fPIC",
               f"-I{INCLUDE}", f"-I{CSRC}", "-Wall", "-Wno-unused-result", *COMMON_FLAGS]
     objs, jobs = [], []
@@ -120,7 +123,7 @@ def sources_and_headers() -> List[str]:
     """Every file the library is compiled from."""
     return ([os.path.join(CSRC, src) for src, _ in SOURCES if os.path.exists(os.path.join(CSRC, src))]
             + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")]
-            + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS + POLAR_HEADERS + SHEAR_HEADERS])
+            + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS + POLAR_HEADERS + SHEAR_HEADERS + HYDRO_HEADERS])
 
 
 STAMP_PATH = LIB_PATH + ".stamp"
